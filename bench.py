@@ -480,6 +480,34 @@ def dry_run(args):
         dist.destroy_process_group()
 
 
+DUMP_BYTES = 63 << 20          # --dump-outputs: 64 MB in all, with room for the .npy headers
+
+
+def dump_outputs(out_dir, out, n_total, write):
+    """--dump-outputs: what explain() returned in the last timed step (R_tok, idx, logit, logits), every rank's prompts in global order (one
+    all-gather per array, after the timed region), written by rank 0 as out_dir/<name>.npy -- float32, idx as float64 -- so that two builds
+    can be compared output for output on the same seeded inputs.  An array beyond its share of DUMP_BYTES is replaced by a fixed, seeded
+    sample of its elements (flattened, in index order)."""
+    import numpy as np
+    import lxt_amd.dist as D
+    arrs = {}
+    for name in ("R_tok", "idx", "logit", "logits"):
+        a = out[name]
+        a = D.gather_relevance(a.reshape(a.shape[0], -1).contiguous(), n_total).reshape(n_total, *a.shape[1:])
+        arrs[name] = a.cpu().to(torch.float64 if name == "idx" else torch.float32)
+    if not write:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES
+    for i, (name, a) in enumerate(sorted(arrs.items(), key=lambda kv: kv[1].numel())):
+        share = budget // (len(arrs) - i)
+        if a.numel() * a.element_size() > share:
+            pick = torch.randint(a.numel(), (share // a.element_size(),), generator=torch.Generator().manual_seed(0)).sort().values
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.numpy())
+        budget -= a.numel() * a.element_size()
+
+
 def self_launch(n):
     """`python bench.py --gpus N` started bare (no RANK / WORLD_SIZE in the environment): become the launcher -- the same command the driver
     issues for N > 1, `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py <argv>`,
@@ -530,7 +558,11 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="plumbing self-test WITHOUT kernels or a GPU (gloo): rank env, sharding, barrier, max-over-ranks, gather, "
                          "one JSON line from rank 0 -- value is null; used by tests/test_dist_cpu.py for the N>1 launch contract")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step's explain() returned "
+                    "(R_tok, idx, logit, logits; all ranks' prompts) as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ and not args.single_rank_collectives:
         return self_launch(args.gpus)
     if args.dry_run:
@@ -596,10 +628,13 @@ def main():
     gen = torch.Generator().manual_seed(1234)
     ids_all = torch.randint(0, cfg["vocab"], (n_total * (args.steps + args.warmup), S), generator=gen).to(dev)
 
+    last = [None]                                           # explain()'s output of the latest step (--dump-outputs)
+
     def step(i):
         chunk = ids_all[i * n_total: (i + 1) * n_total]
         lo, hi = D.shard_range(n_total, rank, world)
-        r = eng.explain(chunk[lo:hi], graph=args.graph)["R_tok"]    # this rank's shard; the all-gather (C2) is per JOB, below
+        last[0] = eng.explain(chunk[lo:hi], graph=args.graph)
+        r = last[0]["R_tok"]                                # this rank's shard; the all-gather (C2) is per JOB, below
         return r.clone() if args.graph else r
 
     for i in range(args.warmup):
@@ -640,6 +675,8 @@ def main():
     elapsed = time.perf_counter() - t0
     ops.GEMM_TIMER = None
     assert R.shape[0] == n_total * args.steps and torch.isfinite(R).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last[0], n_total, write=rank == 0)
     per_rank = None
     if coll:
         # per-rank diagnostics for the first real N > 1 run: every rank's own wall time over the timed region and the share

@@ -14,6 +14,12 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 
 
+def pytest_collection_modifyitems(config, items):
+    # the GPU tests patch HuggingFace and torch.nn classes process-wide (lxt_amd.efficient.monkey_patch never un-patches, like the
+    # reference's); the CPU tests expect those classes as shipped, so they run first
+    items.sort(key=lambda item: item.get_closest_marker("gpu") is not None)
+
+
 @pytest.fixture(scope="session")
 def golden_dir():
     return GOLDEN

@@ -2,7 +2,11 @@
 (tests/golden/make_golden.py) and against the reference tests' closed forms
 (/root/reference tests/test_functional.py:16,41-42,70,91-92,117; tests/test_rules.py:9-24)."""
 import math
+import os
+import subprocess
+import sys
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -17,14 +21,44 @@ def fx():
     return load("rules.npz")
 
 
+# the oracle's Linear eps-rule in a fresh process under MKL's conditional numerical reproducibility mode (one thread): the same bits on every
+# x86 CPU, like the reference's in linear_eps_cnr.npz (tests/golden/make_golden_linear_cnr.py).  Under the default mode MKL picks its kernels
+# by CPU, so a fixture frozen on one host does not bit-compare on another.
+LIN_CNR_WORKER = """
+import sys
+import numpy as np
+import torch
+import torch.nn.functional as F
+sys.path.insert(0, %r)
+from oracle import rules as R
+from tests.util import load, t
+torch.set_num_threads(1)
+fx, out = load("rules.npz"), {}
+for tag in ("c1", "toy", "mid"):
+    x, W, b, g = (t(fx[f"lin_{tag}_{k}"]) for k in "xWbg")
+    for eps_tag, eps in (("f", 1e-6), ("r", 1e-8)):
+        out[f"lin_{tag}_{eps_tag}_Rin"] = R.linear_epsilon(x, W, b, F.linear(x, W, b) * g, eps)[1].numpy()
+np.savez(sys.argv[1], **out)
+"""
+
+
+@pytest.fixture(scope="module")
+def lin_cnr(tmp_path_factory):
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    path = str(tmp_path_factory.mktemp("lin_cnr") / "rin.npz")
+    env = dict(os.environ, MKL_CBWR="COMPATIBLE", MKL_NUM_THREADS="1", OMP_NUM_THREADS="1")
+    r = subprocess.run([sys.executable, "-c", LIN_CNR_WORKER % root, path], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    z = np.load(path)
+    return {k: z[k] for k in z.files}
+
+
 @pytest.mark.parametrize("tag", ["c1", "toy", "mid"])
 @pytest.mark.parametrize("eps_tag,eps", [("f", 1e-6), ("r", 1e-8)])
-def test_linear_epsilon_bitexact(fx, tag, eps_tag, eps):
+def test_linear_epsilon_bitexact(lin_cnr, tag, eps_tag, eps):
     # BASELINE config 1: Linear(768->768) eps-rule, batch 1, CPU, bit-compare
-    x, W, b, g = (t(fx[f"lin_{tag}_{k}"]) for k in "xWbg")
-    z = F.linear(x, W, b)
-    _, Rin = R.linear_epsilon(x, W, b, z * g, eps)
-    assert torch.equal(Rin, t(fx[f"lin_{tag}_{eps_tag}_Rin"]))
+    key = f"lin_{tag}_{eps_tag}_Rin"
+    assert torch.equal(t(lin_cnr[key]), t(load("linear_eps_cnr.npz")[key]))
 
 
 def test_linear_closed_form():
