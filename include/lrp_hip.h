@@ -463,6 +463,44 @@ int lrp_transpose(const void* in, void* out, int rows, int cols, int64_t ld_in, 
                   int batch, int64_t s_in, int64_t s_out, int dtype, void* stream);
 int lrp_cast(const void* in, void* out, int64_t n, int in_dtype, int out_dtype, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * MoE  routed experts of a sparse MoE layer (Qwen3-MoE's Qwen3MoeExperts) on grouped GEMMs (csrc/moe.hip; added in ABI 8, backward
+ *      compatible: no earlier entry changed).   ref: lxt/efficient/models/qwen3_moe.py:14-44 (experts_forward)
+ *   T tokens, k slots, E experts (<= 1024), hidden H, expert intermediate I; H and I multiples of 128 (LRP_ESHAPE otherwise).
+ *   idx: int64 [T, k] expert of each (token, slot) -- a value outside [0, E) (HF's e == E) skips the slot.  w: routing weights [T, k] in dtype.
+ *   Wgu [E, 2 I, H] (HF's gate_up_proj, [gate | up] rows) and Wd [E, H, I] (down_proj), contiguous, read as stored: no copy, no transpose.
+ *   Activation operands: row pitch ld* (elements, 16-byte multiple), base 16-byte aligned (LRP_EALIGN), ld >= the row width (LRP_ESHAPE).
+ *   lrp_moe_plan_ints(T, k, E)      -> int32 words of the routing plan (LRP_ESHAPE for sizes out of range)
+ *   lrp_moe_plan                    : plan = cnt[E] | off[E + 1] | toff[E + 1] | perm[T k] | inv[T k] | workspace; rows of an expert are
+ *                                     contiguous in plan order (off = exclusive scan of cnt), STABLE (token order inside an expert),
+ *                                     perm: plan row -> t k + s, inv: t k + s -> plan row (-1: skipped).  Three launches, no host sync,
+ *                                     deterministic.  Every R = T k below is a plan row count (only the first off[E] rows are written).
+ *   lrp_moe_gate_up_fwd             : per plan row p of expert e, token t:  g|u = x[t] Wgu[e]^T,  m[p] = act(g) u,
+ *                                     coef[p] = { cg = 1/2 u act(g) / (g + 1e-10) | cu = 1/2 act(g) }  ([R, 2 I]; identity rule on act,
+ *                                     uniform rule on the product; SiLU / tanh-GELU)
+ *   lrp_moe_down_fwd                : y[p] = m[p] Wd[e]^T  ([R, H])
+ *   lrp_moe_combine                 : out[t] = sum_s w[t, s] rows[inv[t k + s]]  (w NULL: weight 1), slots in order, fp32 accumulation,
+ *                                     one rounding, no atomics (bit-reproducible; a token with no live slot gets 0)
+ *   lrp_moe_down_dgrad              : D = G[t] Wd[e] (NN on the stored weight), Agu[p] = 1/2 w[t, s] D (*) { cg | cu }  ([R, 2 I], HF's
+ *                                     [gate | up] order), gw_part[p][I / 128] = fp32 partials of sum_i m[p]_i D_i ( = sum_j y_j G[t]_j )
+ *   lrp_moe_gw_reduce               : gw[t, s] = 1/2 sum of the partials of row inv[t k + s] (fixed order; 0 for a skipped slot)
+ *   lrp_moe_gate_up_dgrad           : gx_rows[p] = Agu[p] Wgu[e]  ([R, H]);  G_x = lrp_moe_combine(gx_rows, NULL)
+ * --------------------------------------------------------------------------------------- */
+int64_t lrp_moe_plan_ints(int T, int k, int E);
+int lrp_moe_plan(const void* idx, int* plan, int T, int k, int E, void* stream);
+int lrp_moe_gate_up_fwd(const void* x, const void* Wgu, const int* plan, void* coef, void* m, int T, int k, int E, int H, int I,
+                        int64_t ldx, int64_t ldcoef, int64_t ldm, int act, int dtype, void* stream);
+int lrp_moe_down_fwd(const void* m, const void* Wd, const int* plan, void* y, int T, int k, int E, int H, int I, int64_t ldm,
+                     int64_t ldy, int dtype, void* stream);
+int lrp_moe_combine(const void* rows, const void* w, const int* plan, void* out, int T, int k, int E, int H, int64_t ldr,
+                    int64_t ldo, int dtype, void* stream);
+int lrp_moe_down_dgrad(const void* G, const void* Wd, const void* coef, const void* m, const void* w, const int* plan, void* Agu,
+                       float* gw_part, int T, int k, int E, int H, int I, int64_t ldg, int64_t ldcoef, int64_t ldm,
+                       int64_t ldagu, int dtype, void* stream);
+int lrp_moe_gw_reduce(const float* gw_part, const int* plan, void* gw, int T, int k, int E, int I, int dtype, void* stream);
+int lrp_moe_gate_up_dgrad(const void* Agu, const void* Wgu, const int* plan, void* gx_rows, int T, int k, int E, int H, int I,
+                          int64_t ldagu, int64_t ldgx, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

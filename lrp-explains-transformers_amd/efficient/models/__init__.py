@@ -5,7 +5,7 @@ import importlib
 import warnings
 
 DEFAULT_MAP = {}
-_FAMILIES = ("llama", "qwen2", "qwen3", "gemma3", "gpt2", "bert", "vit_torch")
+_FAMILIES = ("llama", "qwen2", "qwen3", "qwen3_moe", "gemma3", "gpt2", "bert", "vit_torch")
 
 for _name in _FAMILIES:
     try:

@@ -1161,3 +1161,88 @@ def attn_bwd_dkv(q, k, v, q_t, Gho, Gho_t, lse, D, dk_h, dv_h, B, S, Hq, Hkv, d,
 def gqa_reduce(x, out, rows, Hkv, rep, d):
     check(lib.lrp_gqa_reduce(p(x), p(out), rows, Hkv, rep, d, x.stride(0), out.stride(0), dt(x), stream()), "lrp_gqa_reduce")
     return out
+
+
+# ------------------------------------------------------------------------------------------- MoE experts (csrc/moe.hip)
+class MoePlan:
+    """device-side routing plan of one MoE layer (lrp_moe_plan): int32 words, nothing read back to the host"""
+
+    def __init__(self, idx, E):
+        if idx.dim() != 2:
+            raise ValueError(f"lrp_moe_plan: top_k_index must be [T, k], got {tuple(idx.shape)}")
+        self.T, self.k, self.E = int(idx.shape[0]), int(idx.shape[1]), int(E)
+        n = lib.lrp_moe_plan_ints(self.T, self.k, self.E)
+        if n < 0:
+            check(int(n), "lrp_moe_plan_ints")
+        p(idx)
+        idx = idx.to(torch.int64).contiguous()
+        self.buf = torch.empty(int(n), device=idx.device, dtype=torch.int32)
+        check(lib.lrp_moe_plan(p(idx), p(self.buf), self.T, self.k, self.E, stream()), "lrp_moe_plan")
+
+    @property
+    def rows(self):
+        return self.T * self.k
+
+    def views(self):
+        """(cnt, off, perm, inv) as tensors (tests / tools; off has E + 1 entries, perm rows past off[E] are unwritten)"""
+        E, R, b = self.E, self.rows, self.buf
+        return b[:E], b[E:2 * E + 1], b[3 * E + 2:3 * E + 2 + R], b[3 * E + 2 + R:3 * E + 2 + 2 * R]
+
+
+def moe_gate_up_fwd(x, Wgu, plan, act="silu"):
+    """-> (coef [R, 2 I], m [R, I]) in plan-row order; x [T, H] rows are gathered through the plan inside the GEMM"""
+    E, I2, H = Wgu.shape
+    I, R = I2 // 2, plan.rows
+    same(x, Wgu)
+    coef = torch.empty(R, 2 * I, device=x.device, dtype=x.dtype)
+    m = torch.empty(R, I, device=x.device, dtype=x.dtype)
+    _timed(2.0 * R * 2 * I * H, "moe_gate_up_fwd", lambda: lib.lrp_moe_gate_up_fwd(
+        p(x), p(Wgu), p(plan.buf), p(coef), p(m), plan.T, plan.k, plan.E, H, I, x.stride(0), coef.stride(0), m.stride(0), ACT[act],
+        dt(x), stream()), "lrp_moe_gate_up_fwd")
+    return coef, m
+
+
+def moe_down_fwd(m, Wd, plan):
+    """-> y [R, H] = m Wd[e]^T per plan row"""
+    E, H, I = Wd.shape
+    same(m, Wd)
+    y = torch.empty(plan.rows, H, device=m.device, dtype=m.dtype)
+    _timed(2.0 * plan.rows * H * I, "moe_down_fwd", lambda: lib.lrp_moe_down_fwd(
+        p(m), p(Wd), p(plan.buf), p(y), plan.T, plan.k, plan.E, H, I, m.stride(0), y.stride(0), dt(m), stream()), "lrp_moe_down_fwd")
+    return y
+
+
+def moe_combine(rows, plan, w=None):
+    """-> out [T, H] = sum over live slots s of w[t, s] rows[row(t, s)] (w None: weight 1), fp32 accumulation in slot order"""
+    H = rows.shape[1]
+    same(rows, w)
+    out = torch.empty(plan.T, H, device=rows.device, dtype=rows.dtype)
+    check(lib.lrp_moe_combine(p(rows), p(w), p(plan.buf), p(out), plan.T, plan.k, plan.E, H, rows.stride(0), out.stride(0), dt(rows),
+                              stream()), "lrp_moe_combine")
+    return out
+
+
+def moe_down_dgrad(G, Wd, coef, m, w, plan):
+    """-> (Agu [R, 2 I] in [gate | up] order, G_w [T, k]) from the output gradient G [T, H] (gathered by token inside the GEMM)"""
+    E, H, I = Wd.shape
+    same(G, Wd, coef, m, w)
+    R = plan.rows
+    Agu = torch.empty(R, 2 * I, device=G.device, dtype=G.dtype)
+    part = torch.empty(R, I // 128, device=G.device, dtype=torch.float32)
+    gw = torch.empty(plan.T, plan.k, device=G.device, dtype=G.dtype)
+    _timed(2.0 * R * H * I, "moe_down_dgrad", lambda: lib.lrp_moe_down_dgrad(
+        p(G), p(Wd), p(coef), p(m), p(w), p(plan.buf), p(Agu), p(part), plan.T, plan.k, plan.E, H, I, G.stride(0), coef.stride(0),
+        m.stride(0), Agu.stride(0), dt(G), stream()), "lrp_moe_down_dgrad")
+    check(lib.lrp_moe_gw_reduce(p(part), p(plan.buf), p(gw), plan.T, plan.k, plan.E, I, dt(G), stream()), "lrp_moe_gw_reduce")
+    return Agu, gw
+
+
+def moe_gate_up_dgrad(Agu, Wgu, plan):
+    """-> per-row G_x [R, H] = Agu Wgu[e] (NN on the stored weight)"""
+    E, I2, H = Wgu.shape
+    same(Agu, Wgu)
+    gx = torch.empty(plan.rows, H, device=Agu.device, dtype=Agu.dtype)
+    _timed(2.0 * plan.rows * I2 * H, "moe_gate_up_dgrad", lambda: lib.lrp_moe_gate_up_dgrad(
+        p(Agu), p(Wgu), p(plan.buf), p(gx), plan.T, plan.k, plan.E, H, I2 // 2, Agu.stride(0), gx.stride(0), dt(Agu), stream()),
+        "lrp_moe_gate_up_dgrad")
+    return gx
