@@ -74,19 +74,18 @@ class FusedGatedMLPFn(Function):
     (identity rule on act, uniform rule on the product: G_g = 1/2 G_m u act(g)/(g + 1e-10), G_u = 1/2 G_m act(g)) in its epilogue, then ONE gate/up
     dgrad over the fused weight.  ref: lxt/efficient/patches.py:145-157.  Wgu: ops.interleave_gate_up(gate.weight, up.weight); Wd: down.weight or a
     pitch-padded view of a copy (patches._fused_mlp_weights).  Long-K operands m [M, I] and Agu [M, 2 I] get a row pitch that is no multiple of
-    4 KiB (engine.pitch_pad: +5 ... 14 % on those GEMMs)."""
+    4 KiB (engine.fused_layout: +5 ... 14 % on those GEMMs)."""
 
     @staticmethod
     def forward(ctx, x, Wgu, Wd, act):
-        from ..engine import pitch_pad
+        from ..engine import fused_layout
         shp = x.shape
         x2 = x.reshape(-1, shp[-1])
         if x2.stride(-1) != 1 or x2.stride(0) != x2.shape[1]:
             x2 = x2.contiguous()
         M, I = x2.shape[0], Wd.shape[1]
-        es = x2.element_size()
         gu = torch.empty(M, 2 * I, device=x.device, dtype=x.dtype)
-        m = torch.empty(M, I + pitch_pad(I, es), device=x.device, dtype=x.dtype)[:, :I]
+        m = torch.empty(M, fused_layout(x2.shape[1], I, 0, 0, 0, x.dtype)["m"], device=x.device, dtype=x.dtype)[:, :I]     # (the MLP's pitches)
         # M = B S rows: the backward's coefficients are stashed in gu's place (ops.gemm_gated_fwd_coef: no exp / rcp in the backward, g and u never
         # stored); otherwise the GEMM + element-wise pair on the stored gate/up output
         ctx.coef = ops.gated_coef_ok(M, I, x2.shape[1], x2.stride(0), Wgu.stride(0), Wd.shape[0], Wd.stride(0), act, x2.dtype)
@@ -101,14 +100,14 @@ class FusedGatedMLPFn(Function):
 
     @staticmethod
     def backward(ctx, gy):
-        from ..engine import pitch_pad
+        from ..engine import fused_layout
         Wgu, Wd, gu = ctx.saved_tensors
         shp = gy.shape
         g2 = gy.reshape(-1, shp[-1])
         if g2.stride(-1) != 1 or g2.stride(0) != g2.shape[1]:
             g2 = g2.contiguous()
         M, I2 = gu.shape
-        Agu = torch.empty(M, I2 + pitch_pad(I2, gu.element_size()), device=gu.device, dtype=gu.dtype)[:, :I2]
+        Agu = torch.empty(M, fused_layout(Wgu.shape[1], I2 // 2, 0, 0, 0, gu.dtype)["Agu"], device=gu.device, dtype=gu.dtype)[:, :I2]
         if ctx.coef:
             ops.gemm_gated_bwd_coef(g2, Wd, gu, Agu)
         else:
@@ -117,73 +116,38 @@ class FusedGatedMLPFn(Function):
         return gx.view(*shp[:-1], Wgu.shape[1]), None, None, None
 
 
+def _empty(device):
+    """allocator for the engine's fused-layer functions: a fresh tensor per request ("half": the cached 1/2 row scales)"""
+    return lambda tag, rows, cols, pad, dtype: (ops.const_rows(cols, 0.5, device)[None] if tag == "half" else
+                                                torch.empty(rows, cols + pad, device=device, dtype=dtype)[:, :cols])
+
+
 class DecoderLayerFn(Function):
-    """ONE Llama-type decoder layer (pre-norm attention block + pre-norm gated MLP, both with residuals) as the launch sequence of
-    lxt_amd.engine.LlamaLRP's dense layer -- for an adopted bf16 HF model at M = B S rows: the two RMSNorms and both residual sums inside the GEMM
-    epilogues (K1n: norm weights folded into the fused [q;k;v] and gate/up weights by patches._fused_layer_weights), one fused QKV GEMM, the
-    gated rule as a coefficient stash, flash attention; backward: 7 GEMM launches, the dQ kernel forms D and applies RoPE's backward in its store,
-    dK's group sum carries RoPE's backward too -- no attn_bwd_prep / rope_bwd / norm passes.  Rules as lxt.efficient places them (ref
-    lxt/efficient/patches.py:111-123 rms_norm_forward, :145-157 gated_mlp_forward, :193-203 wrap_attention_forward; HF modeling_llama's
-    LlamaDecoderLayer.forward for the wiring).  h [B, S, H]; cos / sin fp32 [S, d] (one table for every prompt: plain causal, un-padded batches);
-    rstd1 fp32 [B S]: 1 / rms of h's rows (from the previous layer's epilogue, or computed by the caller).  Returns (h_out, rstd of h_out's rows)."""
+    """ONE Llama-type decoder layer of an adopted bf16 HF model at M = B S rows on the fused layer of lxt_amd.engine (fused_qkv_fwd,
+    fused_layer_fwd, fused_layer_bwd: LlamaLRP's dense layers), rules as lxt.efficient places them (ref lxt/efficient/patches.py:111-123,
+    :145-157, :193-203).  h [B, S, H]; rstd1 fp32 [B S]: 1 / rms of h's rows; fw: patches._fused_layer_weights (norm weights folded in);
+    cos / sin fp32 [S, d] (plain causal, un-padded batches).  Returns (h_out, rstd of h_out's rows)."""
 
     @staticmethod
-    def forward(ctx, h, rstd1, Wqkv, Wo, Wgu, Wd, cos, sin, meta):
-        from ..engine import pitch_pad
-        nq, nk, d, eps, act, scale = meta
+    def forward(ctx, h, rstd1, fw, cos, sin):
+        from ..engine import fused_qkv_fwd, fused_layer_fwd
         B, S, H = h.shape
-        M, I = B * S, Wd.shape[1]
-        nqk, nqkv = (nq + nk) * d, (nq + 2 * nk) * d
-        dev, dt, es = h.device, h.dtype, h.element_size()
-        new = lambda r, c, pad=0: torch.empty(r, c + pad, device=dev, dtype=dt)[:, :c]          # noqa: E731
-        h2 = h.reshape(M, H)
-        if not h2.is_contiguous():
-            h2 = h2.contiguous()
-        qkv = new(M, nqkv)
-        if ops.gemm_nt_rs_rope_ok(h2, Wqkv, qkv, S, nqk, d):
-            qkr = ops.gemm_nt_rs_rope(h2, Wqkv, rstd1, cos, sin, qkv, S, nqk, d)[:, :nqk]      # RoPE in the GEMM's epilogue
-        else:
-            qkr = ops.rope_fwd(ops.gemm_nt_rs(h2, Wqkv, rstd1, qkv), new(M, nqk), cos, sin, S, nq + nk, d)
-        q, k, v = qkr[:, : nq * d], qkr[:, nq * d:], qkv[:, nqk:]
-        o, lse = new(M, nq * d), torch.empty(B, nq, S, device=dev, dtype=torch.float32)
-        ops.attn_fwd(q, k, v, None, o, lse, B, S, nq, nk, d, scale, True, 0)
-        ssq = torch.empty(H // 64, M, device=dev, dtype=torch.float32)
-        h1 = ops.gemm_res_ssq(o, Wo, h2, new(M, H), ssq)
-        rstd2 = ops.rms_rstd(ssq, M, H, eps, torch.empty(M, device=dev, dtype=torch.float32))
-        coef, m = ops.gemm_gated_fwd_coef(h1, Wgu, new(M, 2 * I), new(M, I, pitch_pad(I, es)), 1e-10, 0.0, act, rs=rstd2)
-        out = ops.gemm_res_ssq(m, Wd, h1, new(M, H), ssq)
-        rstd_out = ops.rms_rstd(ssq, M, H, eps, torch.empty(M, device=dev, dtype=torch.float32))
-        ctx.save_for_backward(rstd1, rstd2, qkv, qkr, o, lse, coef, Wqkv, Wo, Wgu, Wd, cos, sin)
-        ctx.meta = (B, S, H, I, nq, nk, d, scale)
-        ctx.mark_non_differentiable(rstd_out)
-        return out.view(B, S, H), rstd_out
+        h2, alloc = h.reshape(B * S, H).contiguous(), _empty(h.device)
+        qkv, qkr = fused_qkv_fwd(h2, rstd1, fw["wqkv"], cos, sin, S, fw["meta"], alloc)
+        st = fused_layer_fwd(h2, rstd1, qkv, qkr, fw, cos, sin, B, S, fw["meta"], alloc)
+        ctx.save_for_backward(rstd1, st["rstd2"], qkv, qkr, st["o"], st["lse"], st["gu"], cos, sin)
+        ctx.fw = fw
+        ctx.mark_non_differentiable(st["rstd_out"])
+        return st["h_out"].view(B, S, H), st["rstd_out"]
 
     @staticmethod
     def backward(ctx, gy, _g_rstd):
-        from ..engine import pitch_pad
-        rstd1, rstd2, qkv, qkr, o, lse, coef, Wqkv, Wo, Wgu, Wd, cos, sin = ctx.saved_tensors
-        B, S, H, I, nq, nk, d, scale = ctx.meta
-        M, rep = B * S, nq // nk
-        nqk, nqkv = (nq + nk) * d, (nq + 2 * nk) * d
-        dev, dt, es = gy.device, gy.dtype, gy.element_size()
-        new = lambda r, c, pad=0: torch.empty(r, c + pad, device=dev, dtype=dt)[:, :c]          # noqa: E731
-        G = gy.reshape(M, H)
-        if not G.is_contiguous():
-            G = G.contiguous()
-        Agu = ops.gemm_gated_bwd_coef(G, Wd, coef, new(M, 2 * I, pitch_pad(2 * I, es)))
-        Gs1 = ops.gemm_nn_rs_res(Agu, Wgu, rstd2, G, new(M, H))
-        half = ops.const_rows(M, 0.5, dev)
-        Gho = ops.gemm_nn_rs(Gs1, Wo, half, new(M, nq * d))                                       # 1/2 (uniform rule on P.V): exact row scale
-        q, k, v = qkr[:, : nq * d], qkr[:, nq * d:], qkv[:, nqk:]
-        D = torch.empty(B, nq, S, device=dev, dtype=torch.float32)
-        Aqkv = new(M, nqkv, 64 if (nqkv * es) % 4096 == 0 else 0)
-        ops.attn_bwd_dq_d(q, k, v, Gho, o, lse, D, Aqkv[:, : nq * d], B, S, nq, nk, d, scale, rope=(cos, sin))
-        dk_h, dv_h = new(M, nq * d), new(M, nq * d)
-        ops.attn_bwd_dkv(q, k, v, None, Gho, None, lse, D, dk_h, dv_h, B, S, nq, nk, d, scale, 0.0, 0.0)
-        ops.gqa_reduce_rope(dk_h, Aqkv[:, nq * d: nqk], M, S, nk, rep, d, cos, sin)
-        ops.gqa_reduce(dv_h, Aqkv[:, nqk:], M, nk, rep, d)
-        Gh = ops.gemm_nn_rs_res(Aqkv, Wqkv, rstd1, Gs1, new(M, H))
-        return Gh.view(B, S, H), None, None, None, None, None, None, None, None
+        from ..engine import fused_layer_bwd
+        *saved, cos, sin = ctx.saved_tensors
+        B, S, H = gy.shape
+        st = dict(zip(("rstd1", "rstd2", "qkv", "qkr", "o", "lse", "gu"), saved))
+        Gh = fused_layer_bwd(gy.reshape(B * S, H).contiguous(), st, ctx.fw, cos, sin, B, S, ctx.fw["meta"], _empty(gy.device))
+        return Gh.view(B, S, H), None, None, None, None
 
 
 class RopeFn(Function):

@@ -175,13 +175,13 @@ FUSE_MLP = True           # module attribute (no environment knob): False = thre
 def _fused_mlp_weights(mlp):
     """-> (Wgu interleaved [2 I, H], Wd [H, I]) of an ADOPTED bf16 gated MLP, built once and kept on the module (rebuilt when a weight is replaced
     or written): the fused-epilogue GEMMs want gate and up as one operand with its rows in blocks of [32 gate | 32 up] (ops.interleave_gate_up),
-    and the long-K down weight with a row pitch that is no multiple of 4 KiB (engine.pitch_pad).  Memory: the interleaved gate/up
+    and the long-K down weight with a row pitch that is no multiple of 4 KiB (engine.fused_layout).  Memory: the interleaved gate/up
     operand is a second copy of those two weights (Llama-3-8B: 7.5 GB; their row order cannot be expressed as a view); the pitch-padded down
     weight REPLACES the module's own storage (down_proj.weight.data becomes the padded view: no second copy).  The copy is only made while it
     leaves at least half of the device's currently free memory free -- a model that just fits keeps running, on the three-GEMM path --, and
     release_fused(model) drops it.  None where the fused kernels do not apply (fp32, biases, I % 32, trainable or foreign modules)."""
     from .. import ops
-    from ..engine import pitch_pad, weight_pitch_pad
+    from ..engine import fused_layout
     g, u, dn = mlp.gate_proj, mlp.up_proj, mlp.down_proj
     if not (FUSE_MLP and all(isinstance(t, torch.nn.Linear) and _owned(t) and t.bias is None and not t.weight.requires_grad for t in (g, u, dn))):
         return None
@@ -196,8 +196,8 @@ def _fused_mlp_weights(mlp):
     if hit is None and mlp.__dict__.get("_lrp_fused_mlp_refused"):
         return None
     with torch.no_grad():
-        wpad = weight_pitch_pad(wg.shape[1], wg.element_size(), 2 * wg.shape[0])      # NN (dgrad) reads stride over the rows: pitch off the 4-KiB grid
-        pad = pitch_pad(wd.shape[1], wd.element_size())
+        pt = fused_layout(wg.shape[1], wg.shape[0], 0, 0, 0, wg.dtype)                  # (the MLP's pitches)
+        wpad, pad = pt["Wgu"] - wg.shape[1], pt["Wd"] - wd.shape[1]
         need = 2 * wg.shape[0] * (wg.shape[1] + wpad) * wg.element_size() + (wd.shape[0] * (wd.shape[1] + pad) * wd.element_size() if pad else 0)
         if hit is None and need > torch.cuda.mem_get_info(wg.device)[0] // 2:
             mlp.__dict__["_lrp_fused_mlp_refused"] = True                              # (decided once per module: no per-call memory query)
@@ -247,27 +247,15 @@ def gated_mlp_forward(self, x):
 FUSE_LAYER = True         # module attribute (no environment knob): False = per-module patches only (A/B measurements, equality tests)
 
 
-def _fold_rows(dst, srcs, ln):
-    """dst [sum rows, cols] <- concat(srcs) * ln[None, :] (fp32 product, ONE rounding), block by block"""
-    lnf = ln.detach().float()
-    r0 = 0
-    for w in srcs:
-        for b0 in range(0, w.shape[0], 4096):
-            blk = w[b0: b0 + 4096].detach()
-            dst[r0 + b0: r0 + b0 + blk.shape[0]].copy_((blk.float() * lnf).to(dst.dtype))
-        r0 += w.shape[0]
-    return dst
-
-
 def _fused_layer_weights(layer):
-    """-> dict(Wqkv, Wo, Wgu, Wd, meta) of an ADOPTED bf16 Llama-type decoder layer for DecoderLayerFn, built once and kept on the module: the
+    """-> dict(wqkv, wo, wgu, wd, meta, ok, ok_rows) of an ADOPTED bf16 Llama-type decoder layer for DecoderLayerFn, built once and kept on the module: the
     fused [q; k; v] weight and the interleaved gate/up weight with the layer's two RMSNorm weights FOLDED into their columns (W' = W diag(w):
     the same network and the same relevance under every rule -- lxt_amd.engine.LlamaLRP does the same; the norm is then a row scale that runs in
-    the GEMM epilogues), stored-weight row pitches off the 4-KiB grid.  Memory: a second copy of q/k/v and gate/up (Llama-3-8B: 10.7 GB; the
+    the GEMM epilogues), stored-weight row pitches of engine.fused_layout.  Memory: a second copy of q/k/v and gate/up (Llama-3-8B: 10.7 GB; the
     padded down weight replaces the module's storage, o is used as stored), made only while it leaves half of the free device memory free;
-    release_fused(model) drops it.  None where the fused layer does not apply."""
+    release_fused(model) drops it.  None where the fused layer cannot apply; ok_rows[(B, S)]: engine.fused_layer_ok's latest answer (cache: ok)."""
     from .. import ops
-    from ..engine import pitch_pad, weight_pitch_pad
+    from ..engine import fold_rows, fused_layout
     hit = layer.__dict__.get("_lrp_fused_layer")
     att, mlp = getattr(layer, "self_attn", None), getattr(layer, "mlp", None)
     lins = [getattr(att, n, None) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] + [getattr(mlp, n, None) for n in ("gate_proj", "up_proj", "down_proj")]
@@ -293,31 +281,31 @@ def _fused_layer_weights(layer):
     ok = (wq.is_cuda and all(t.dtype == torch.bfloat16 for t in ws) and act in ("silu", "gelu_tanh") and I % ops.GATED_IL == 0 and H % 256 == 0
           and wq.shape == (nq * d, H) and wk.shape == wv.shape == (nk * d, H) and wo.shape == (H, nq * d) and wu.shape == wg.shape
           and wd.shape == (H, I) and d in (64, 128) and nq % nk == 0 and eps1 is not None and eps1 == eps2
-          and float(getattr(att, "scaling", d ** -0.5)) > 0 and not getattr(att, "sliding_window", None)
-          and ops.attn_dq_d_ok(torch.bfloat16, d) and not ops.attn_needs_transposed(wq, d))
+          and float(getattr(att, "scaling", d ** -0.5)) > 0 and not getattr(att, "sliding_window", None) and not ops.attn_needs_transposed(wq, d))
     if not ok:
         layer.__dict__["_lrp_fused_layer_refused"] = True
         return None
     es, nqkv = wq.element_size(), (nq + 2 * nk) * d
     with torch.no_grad():
-        pq, pg, pd = weight_pitch_pad(H, es, nqkv), weight_pitch_pad(H, es, 2 * I), pitch_pad(I, es)
-        need = (nqkv * (H + pq) + 2 * I * (H + pg)) * es + (H * (I + pd) * es if (pd and wd.stride(0) != I + pd) else 0)
+        pt = fused_layout(H, I, nq, nk, d, wq.dtype)
+        copy_wd = wd.stride(0) != pt["Wd"]
+        need = (nqkv * pt["Wqkv"] + 2 * I * pt["Wgu"]) * es + (H * pt["Wd"] * es if copy_wd else 0)
         if need > torch.cuda.mem_get_info(wq.device)[0] // 2:
             layer.__dict__["_lrp_fused_layer_refused"] = True                        # (decided once per layer)
             return None
-        Wqkv = _fold_rows(torch.empty(nqkv, H + pq, device=wq.device, dtype=wq.dtype)[:, :H], (wq, wk, wv), n1.weight)
-        tmp = _fold_rows(torch.empty(2 * I, H, device=wq.device, dtype=wq.dtype), (wg, wu), n2.weight)
-        Wgu = ops.interleave_gate_up(tmp[:I], tmp[I:], out=torch.empty(2 * I, H + pg, device=wq.device, dtype=wq.dtype)[:, :H])
+        Wqkv = fold_rows(torch.empty(nqkv, pt["Wqkv"], device=wq.device, dtype=wq.dtype)[:, :H], (wq, wk, wv), n1.weight)
+        tmp = fold_rows(torch.empty(2 * I, H, device=wq.device, dtype=wq.dtype), (wg, wu), n2.weight)
+        Wgu = ops.interleave_gate_up(tmp[:I], tmp[I:], out=torch.empty(2 * I, pt["Wgu"], device=wq.device, dtype=wq.dtype)[:, :H])
         del tmp
         Wd = wd.detach()
-        if pd and wd.stride(0) != I + pd:
-            Wd = torch.empty(H, I + pd, device=wd.device, dtype=wd.dtype)[:, :I]
+        if copy_wd:
+            Wd = torch.empty(H, pt["Wd"], device=wd.device, dtype=wd.dtype)[:, :I]
             Wd.copy_(wd)
             lins[6].weight.data = Wd                      # ONE down weight: the padded one (see _fused_mlp_weights)
         mlp.__dict__.pop("_lrp_fused_mlp", None)          # the MLP-level copy (if an earlier call made one) is superseded
     key = tuple((t.data_ptr(), t._version) for t in [t_.weight for t_ in lins] + [n1.weight, n2.weight])
-    hit = dict(key=key, Wqkv=Wqkv, Wo=wo.detach(), Wgu=Wgu, Wd=Wd, meta=(nq, nk, d, float(eps1), act, float(getattr(att, "scaling", d ** -0.5))),
-               H=H, I=I, ok_rows={})
+    hit = dict(key=key, wqkv=Wqkv, wo=wo.detach(), wgu=Wgu, wd=Wd, meta=(nq, nk, d, float(eps1), act, float(getattr(att, "scaling", d ** -0.5))),
+               ok={}, ok_rows={})
     layer.__dict__["_lrp_fused_layer"] = hit
     return hit
 
@@ -342,6 +330,7 @@ def decoder_layer_forward(self, hidden_states, attention_mask=None, position_ids
     of the engine (DecoderLayerFn).  Anything the fused layer does not cover -- fp32, biases, padded / packed batches, sliding windows, KV caches,
     few rows, extra keyword arguments that change the computation -- runs HF's own forward over the per-module patches, as before."""
     from .. import ops
+    from ..engine import fused_layer_ok
     h = hidden_states
     fw = None
     if (FUSE_LAYER and torch.is_tensor(h) and h.is_cuda and h.dtype == torch.bfloat16 and h.dim() == 3 and past_key_values is None
@@ -350,17 +339,8 @@ def decoder_layer_forward(self, hidden_states, attention_mask=None, position_ids
     if fw is not None:
         B, S, H = h.shape
         cos, sin = position_embeddings
-        nq, nk, d, eps, act, scale = fw["meta"]
-        ok = fw["ok_rows"].get((B, S))
-        if ok is None:
-            M, I = B * S, fw["I"]
-            ok = fw["ok_rows"][(B, S)] = bool(
-                ops.gated_coef_ok(M, I, H, H, fw["Wgu"].stride(0), H, fw["Wd"].stride(0), act, h.dtype)
-                and all(ops.norm_fused_ok(*a, h.dtype) for a in (
-                    (M, H, nq * d, nq * d, fw["Wo"].stride(0), False), (M, H, I, fw["Wd"].stride(0), fw["Wd"].stride(0), False),
-                    (M, (nq + 2 * nk) * d, H, H, fw["Wqkv"].stride(0), False), (M, 2 * I, H, H, fw["Wgu"].stride(0), False),
-                    (M, H, (nq + 2 * nk) * d, (nq + 2 * nk) * d, fw["Wqkv"].stride(0), True), (M, H, 2 * I, 2 * I, fw["Wgu"].stride(0), True),
-                    (M, nq * d, H, H, fw["Wo"].stride(0), True))))
+        d, eps = fw["meta"][2], fw["meta"][3]
+        ok = fw["ok_rows"][(B, S)] = fused_layer_ok(B * S, fw, fw["meta"], h.dtype, fw["ok"]).full     # (the engine's eligibility)
         if ok and cos.dim() == 3 and cos.shape[0] == 1 and cos.shape[1] == S and cos.shape[2] == d and not cos.requires_grad:
             causal, window, row_iv = _mask_plan(attention_mask, S, self.self_attn, 0)
             if causal and not window and row_iv is None:
@@ -372,7 +352,7 @@ def decoder_layer_forward(self, hidden_states, attention_mask=None, position_ids
                     _, r = ops.add_rmsnorm_fwd(h2 if h2.is_contiguous() else h2.contiguous(), None, ones, eps)
                 else:
                     r = rstd[0]
-                out, rstd_out = DecoderLayerFn.apply(h, r, fw["Wqkv"], fw["Wo"], fw["Wgu"], fw["Wd"], ct, st, fw["meta"])
+                out, rstd_out = DecoderLayerFn.apply(h, r, fw, ct, st)
                 out._lrp_rstd = (rstd_out, eps, out._version)     # the next layer's 1 / rms, left by this layer's down-projection epilogue
                 return out
     return self.original_forward(hidden_states, attention_mask=attention_mask, position_ids=position_ids, past_key_values=past_key_values,

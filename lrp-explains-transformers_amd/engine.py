@@ -21,6 +21,8 @@ MI355X-first decisions:
     + final norm backward is a single row per prompt.
 Python only sequences kernel launches on the current stream; it performs no arithmetic.
 """
+import collections
+
 import torch
 
 from . import ops
@@ -123,6 +125,120 @@ def weight_pitch_pad(cols, elem_size, rows=0):
     return 256 // elem_size
 
 
+# ---- the fused dense Llama layer (M = B S rows): ONE implementation for LlamaLRP and the drop-in's DecoderLayerFn
+
+def fused_layout(H, I, nq, nk, d, dtype):
+    """row pitches (elements) of the stored weights Wqkv, Wgu, Wd and the activations m, Agu, Aqkv of a fused layer, in ONE place (Aqkv: the dQ
+    kernel stores a row segment per lane into it; a pitch on the 4-KiB grid puts them all on the same channels)"""
+    es = dtype.itemsize
+    nqkv = (nq + 2 * nk) * d
+    return dict(Wqkv=H + weight_pitch_pad(H, es, nqkv), Wgu=H + weight_pitch_pad(H, es, 2 * I), Wd=I + pitch_pad(I, es),
+                m=I + pitch_pad(I, es), Agu=2 * I + pitch_pad(2 * I, es), Aqkv=nqkv + (64 if PITCH_PAD and (nqkv * es) % 4096 == 0 else 0))
+
+
+def fold_rows(dst, srcs, ln):
+    """dst <- concat(srcs) diag(ln) (a norm weight folded into the Linear after it): fp32 product, ONE rounding, in 4096-row blocks; srcs may be (dst,)"""
+    lnf = ln.detach().to(device=dst.device, dtype=torch.float32)
+    r0 = 0
+    for w in srcs:
+        for b0 in range(0, w.shape[0], 4096):
+            blk = w[b0: b0 + 4096].detach()
+            dst[r0 + b0: r0 + b0 + blk.shape[0]].copy_((blk.float() * lnf).to(dst.dtype))
+        r0 += w.shape[0]
+    return dst
+
+
+FusedOk = collections.namedtuple("FusedOk", "coef norm prep full")
+
+
+def fused_layer_ok(M, W, meta, dtype, cache):
+    """which parts of the fused layer apply at M rows, cached per (M, A/B knobs): coef -- the gated rules as a coefficient stash; norm -- coef and
+    the six GEMMs around the norms on the K1n epilogues, at fused_layout's pitches; prep -- the dQ kernel forms D and Gho = 1/2 (Aa Wo) runs on the
+    row-scale epilogue; full -- all of it, every NORM_FUSION part and RoPE's backward in the attention backward.  W: wqkv, wo, wgu, wd"""
+    key = (M, PITCH_PAD, repr(ops.NORM_FUSION), ops.GATED_FUSION, ops.PREP_FUSION, ops.ROPE_BWD_FUSION)
+    hit = cache.get(key)
+    if hit is None:
+        nq, nk, d, _, act, _ = meta
+        H, I, nqkv = W["wo"].shape[0], W["wd"].shape[1], (nq + 2 * nk) * d
+        pt = fused_layout(H, I, nq, nk, d, dtype)
+        ldo, ldqkv, ldgu, ldd = (W[k].stride(0) for k in ("wo", "wqkv", "wgu", "wd"))
+        coef = ops.gated_coef_ok(M, I, H, H, ldgu, H, ldd, act, dtype)
+        norm = coef and all(ops.norm_fused_ok(*a, dtype) for a in (
+            (M, H, nq * d, nq * d, ldo, False),             # h1 = h + o Wo^T
+            (M, H, I, pt["m"], ldd, False),                 # h' = h1 + m Wd^T
+            (M, nqkv, H, H, ldqkv, False),                  # qkv = rstd (h W'qkv^T)
+            (M, 2 * I, H, H, ldgu, False),                  # gate/up = rstd (h1 W'gu^T)
+            (M, H, nqkv, pt["Aqkv"], ldqkv, True),          # G_h = rstd (Aqkv W'qkv) + G_res
+            (M, H, 2 * I, pt["Agu"], ldgu, True)))          # G_h1 = rstd (Agu W'gu) + G
+        prep = ops.attn_dq_d_ok(dtype, d) and ops.norm_fused_ok(M, nq * d, H, H, ldo, True, dtype)        # (Aa [M, H] contiguous)
+        full = (norm and prep and all(ops.norm_fusion_part(p) for p in ("fwd", "bwd_gu", "bwd_qkv")) and ops.ROPE_BWD_FUSION
+                and d in (64, 128))
+        hit = cache[key] = FusedOk(bool(coef), bool(norm), bool(prep), bool(full))
+    return hit
+
+
+def fused_qkv_fwd(h, rstd1, Wqkv, cos, sin, S, meta, alloc, explicit=False):
+    """-> (qkv, qkr): rstd1 (.) (h Wqkv^T) with RoPE in the GEMM's epilogue where the kernel takes it, else a rope_fwd pass (always in the
+    explicit placement: RoPE's stabiliser needs the un-rotated q / k).  meta = (nq, nk, d, eps, act, scale); alloc(tag, rows, cols, pad, dtype)"""
+    nq, nk, d = meta[:3]
+    M, nqk = h.shape[0], (nq + nk) * d
+    qkv = alloc("qkv", M, (nq + 2 * nk) * d, 0, h.dtype)
+    if not explicit and ops.gemm_nt_rs_rope_ok(h, Wqkv, qkv, S, nqk, d):
+        return qkv, ops.gemm_nt_rs_rope(h, Wqkv, rstd1, cos, sin, qkv, S, nqk, d)[:, :nqk]
+    ops.gemm_nt_rs(h, Wqkv, rstd1, qkv)
+    return qkv, ops.rope_fwd(qkv, alloc("qkr", M, nqk, 0, h.dtype), cos, sin, S, nq + nk, d)
+
+
+def fused_layer_fwd(h, rstd1, qkv, qkr, W, cos, sin, B, S, meta, alloc, row_iv=None, explicit=False, eps=(EFFICIENT["act"], EFFICIENT["lin"]),
+                    chain=True):
+    """attention, h1 = h + o Wo^T with its sums of squares in the epilogue, the gate/up GEMM on rstd2 (.) h1 with the coefficient stash of the
+    gated rule (eps = (eps_g, eps_lin)); chain: the down projection leaves h_out and ITS rstd the same way, else dn = m Wd^T.  explicit: the
+    Linears' own outputs a / dn are kept for their stabilisers.  -> dict(o, lse, h1, a, rstd2, gu, dn[, h_out, rstd_out])"""
+    nq, nk, d, rms_eps, act, scale = meta
+    M, H, I, dt = B * S, h.shape[1], W["wd"].shape[1], h.dtype
+    new = lambda tag, cols, pitch=None: alloc(tag, M, cols, (pitch or cols) - cols, dt)      # noqa: E731
+    vec = lambda tag: alloc(tag, 1, M, 0, torch.float32)[0]                                  # noqa: E731
+    v = qkv[:, (nq + nk) * d:]
+    v_t = ops.transpose_heads(v, B, S, nk, d) if ops.attn_needs_transposed(v, d) else None
+    st = dict(o=new("o", nq * d), lse=alloc("lse", B * nq, S, 0, torch.float32).view(B, nq, S))
+    ops.attn_fwd(qkr[:, : nq * d], qkr[:, nq * d:], v, v_t, st["o"], st["lse"], B, S, nq, nk, d, scale, True, 0, row_iv=row_iv)
+    ssq, pt = alloc("ssq", H // 64, M, 0, torch.float32), fused_layout(H, I, nq, nk, d, dt)
+    st.update(h1=new("h1", H), a=new("a", H) if explicit else None)
+    ops.gemm_res_ssq(st["o"], W["wo"], h, st["h1"], ssq, raw=st["a"])
+    st["rstd2"] = ops.rms_rstd(ssq, M, H, rms_eps, vec("rstd2"))
+    st["gu"], m = ops.gemm_gated_fwd_coef(st["h1"], W["wgu"], new("gu", 2 * I), new("m", I, pt["m"]), *eps, act, rs=st["rstd2"])
+    if chain:
+        st["h_out"], st["dn"] = new("h_out", H), new("dn", H) if explicit else None
+        ops.gemm_res_ssq(m, W["wd"], st["h1"], st["h_out"], ssq, raw=st["dn"])
+        st["rstd_out"] = ops.rms_rstd(ssq, M, H, rms_eps, vec("rstd_out"))
+    else:
+        st["dn"] = ops.linear_fwd(m, W["wd"], out=new("dn", H))
+    return st
+
+
+def fused_layer_bwd(G, st, W, cos, sin, B, S, meta, alloc, row_iv=None):
+    """efficient placement: G at the layer's output -> G at its input in 7 GEMMs, rules / norms in their epilogues, D and RoPE's backward in the
+    attention backward.  st: what the forward left, plus rstd1; alloc("half", 1, M, ...) returns fp32 rows already set to 1/2 (no fill per layer)"""
+    nq, nk, d, _, _, scale = meta
+    M, H, I, dt, nqk, nqkv = B * S, G.shape[1], W["wd"].shape[1], G.dtype, (nq + nk) * d, (nq + 2 * nk) * d
+    pt = fused_layout(H, I, nq, nk, d, dt)
+    new = lambda tag, cols, pitch=None: alloc(tag, M, cols, (pitch or cols) - cols, dt)      # noqa: E731
+    Agu = ops.gemm_gated_bwd_coef(G, W["wd"], st["gu"], new("Agu", 2 * I, pt["Agu"]))
+    Gs1 = ops.gemm_nn_rs_res(Agu, W["wgu"], st["rstd2"], G, new("Gs1", H))
+    Gho = ops.gemm_nn_rs(Gs1, W["wo"], alloc("half", 1, M, 0, torch.float32)[0], new("Gho", nq * d))      # ("half": the allocator's 1/2 rows)
+    q, k, v = st["qkr"][:, : nq * d], st["qkr"][:, nq * d:], st["qkv"][:, nqk:]
+    D = alloc("D", B * nq, S, 0, torch.float32).view(B, nq, S)
+    Aqkv, dk_h, dv_h = new("Aqkv", nqkv, pt["Aqkv"]), new("dk_h", nq * d), new("dv_h", nq * d)
+    ops.attn_bwd_dq_d(q, k, v, Gho, st["o"], st["lse"], D, Aqkv[:, : nq * d], B, S, nq, nk, d, scale, row_iv=row_iv, rope=(cos, sin))
+    ops.attn_bwd_dkv(q, k, v, None, Gho, None, st["lse"], D, dk_h, dv_h, B, S, nq, nk, d, scale, 0.0, 0.0, row_iv=row_iv)
+    ops.gqa_reduce_rope(dk_h, Aqkv[:, nq * d: nqk], M, S, nk, nq // nk, d, cos, sin)
+    ops.gqa_reduce(dv_h, Aqkv[:, nqk:], M, nk, nq // nk, d)
+    return ops.gemm_nn_rs_res(Aqkv, W["wqkv"], st["rstd1"], Gs1, new("Gh", H))
+
+
+FUSED_SCRATCH = frozenset(("ssq", "m", "half", "Agu", "Gs1", "Gho", "D", "Aqkv", "dk_h", "dv_h"))      # temporaries: one buffer serves every layer
+
+
 class LlamaLRP:
     """Device-resident weights (each ONCE, forward layout, one flat buffer) + explain()."""
 
@@ -143,7 +259,7 @@ class LlamaLRP:
         # identity rule does not see its weight.  What it buys: the norm is then a pure row scale, which commutes with the Linear --
         # rstd (.) (h W'^T) -- so for M = B S rows the efficient placement runs it inside the GEMM epilogues (K1n, _norm_fused below).
         self.folded = bool(dtype == torch.bfloat16 if fold_norm is None else fold_norm)
-        self._nf_cache = {}                 # row count -> do the K1n entry points take every GEMM around the norms (_norm_fused)
+        self._nf_cache = {}                 # (row count, A/B knobs) -> fused_layer_ok
 
         # ONE flat device buffer holds every weight in its forward layout (embedding, norms, LM head, per layer the fused
         # [q;k;v] and [gate;up] matrices, o, down): the tensors below are views into it, so the multi-GPU start-up is a
@@ -151,30 +267,22 @@ class LlamaLRP:
         H, I, nq, nk, hd, V = cfg["hidden"], cfg["inter"], cfg["n_heads"], cfg["n_kv"], cfg["head_dim"], cfg["vocab"]
         nqkv = (nq + 2 * nk) * hd
         up = lambda n: (n + 63) // 64 * 64                                   # noqa: E731  (every view starts 128-byte aligned)
-        es = torch.empty(0, dtype=dtype).element_size()
-        per_layer = (2 * up(H) + up(nqkv * (H + weight_pitch_pad(H, es, nqkv))) + up(H * nq * hd) + up(2 * I * (H + weight_pitch_pad(H, es, 2 * I)))
-                     + up(H * (I + pitch_pad(I, es))))
+        self.meta = (nq, nk, hd, cfg["rms_eps"], self.act, hd ** -0.5)      # (the layer description of the fused-layer functions above)
+        pt = fused_layout(H, I, nq, nk, hd, dtype)
+        per_layer = 2 * up(H) + up(nqkv * pt["Wqkv"]) + up(H * nq * hd) + up(2 * I * pt["Wgu"]) + up(H * pt["Wd"])
         total = 2 * up(V * H) + up(H) + len(W["layers"]) * per_layer
         self.flat = torch.empty(total, device=dev, dtype=dtype)
         cursor = [0]
 
-        def take(*shape):
+        def take(*shape, pitch=None):
+            # pitch: a [rows, cols] view with that row pitch (fused_layout: off the 4-KiB grid)
+            full = shape[:-1] + (pitch or shape[-1],)
             n = 1
-            for s_ in shape:
+            for s_ in full:
                 n *= s_
-            v = self.flat[cursor[0]: cursor[0] + n].view(*shape)
+            v = self.flat[cursor[0]: cursor[0] + n].view(*full)
             cursor[0] += up(n)
-            return v
-
-        def take_rows(rows, cols):
-            # [rows, cols] view with a row pitch that is not a multiple of 4 KiB (pitch_pad): the K-contiguous operand of a long-K GEMM
-            pad = pitch_pad(cols, es)
-            return take(rows, cols + pad)[:, :cols]
-
-        def take_weight(rows, cols):
-            # stored weight whose NN (dgrad) reads stride over its rows: row pitch off the 4-KiB grid (weight_pitch_pad)
-            pad = weight_pitch_pad(cols, es, rows)
-            return take(rows, cols + pad)[:, :cols]
+            return v[..., : shape[-1]]
 
         def put(dst, *srcs):
             o = 0
@@ -193,21 +301,13 @@ class LlamaLRP:
         self.lm_head_t = None                        # [H, V] copy, made on the first dense-seed explanation
         self.layers = []
 
-        def fold(w, ln):
-            # W' = W diag(ln): product in fp32, ONE rounding to the storage dtype, block by block (no 4-byte copy of a whole weight)
-            lnf = ln.to(device=dev, dtype=torch.float32)
-            for r0 in range(0, w.shape[0], 4096):
-                blk = w[r0: r0 + 4096]
-                blk.copy_((blk.float() * lnf).to(dtype))
-            return w
-
         for L in W["layers"]:
             Lw = dict(ln1=put(take(H), L["ln1"]), ln2=put(take(H), L["ln2"]),
-                      wqkv=put(take_weight(nqkv, H), L["wq"], L["wk"], L["wv"]), wo=put(take(H, nq * hd), L["wo"]),
-                      wgu=put_gu(take_weight(2 * I, H), L["wg"], L["wu"]), wd=put(take_rows(H, I), L["wd"]))
-            if self.folded:
-                fold(Lw["wqkv"], L["ln1"])
-                fold(Lw["wgu"], L["ln2"])
+                      wqkv=put(take(nqkv, H, pitch=pt["Wqkv"]), L["wq"], L["wk"], L["wv"]), wo=put(take(H, nq * hd), L["wo"]),
+                      wgu=put_gu(take(2 * I, H, pitch=pt["Wgu"]), L["wg"], L["wu"]), wd=put(take(H, I, pitch=pt["Wd"]), L["wd"]))
+            if self.folded:          # (in place, on the weights as stored: the product sees the storage dtype's rounding of W)
+                fold_rows(Lw["wqkv"], (Lw["wqkv"],), L["ln1"])
+                fold_rows(Lw["wgu"], (Lw["wgu"],), L["ln2"])
                 Lw["ln1"].fill_(1.0)
                 Lw["ln2"].fill_(1.0)
             self.layers.append(Lw)
@@ -233,52 +333,26 @@ class LlamaLRP:
     def _lin_bwd(self, A, W, out):
         return ops.linear_dgrad(A, W, out=out)
 
-    def _pitches(self):
-        """row pitches (elements) of the backward's two wide GEMM operands, in ONE place: what backward() allocates is what the eligibility
-        checks below are asked about"""
-        c = self.cfg
-        es = torch.empty(0, dtype=self.dtype).element_size()
-        nqkv = (c["n_heads"] + 2 * c["n_kv"]) * c["head_dim"]
-        aqkv_pad = 64 if ((nqkv * es) % 4096 == 0 and PITCH_PAD) else 0
-        return dict(Aqkv=nqkv + aqkv_pad, Aqkv_pad=aqkv_pad, Agu=2 * c["inter"] + pitch_pad(2 * c["inter"], es), m=c["inter"] + pitch_pad(c["inter"], es))
+    def _fused(self, M):
+        """fused_layer_ok of this engine's layers at M rows (every layer has the same shapes and pitches)"""
+        return fused_layer_ok(M, self.layers[0], self.meta, self.dtype, self._nf_cache) if self.layers else FusedOk(False, False, False, False)
 
     def _gated_coef(self, M):
         """the gated-MLP rules run as a coefficient stash inside the two GEMMs around them (ops.gemm_gated_fwd_coef / _bwd_coef) at this row count"""
-        key = ("coef", M, PITCH_PAD, ops.GATED_FUSION)
-        hit = self._nf_cache.get(key)
-        if hit is None:
-            c = self.cfg
-            L0 = self.layers[0] if self.layers else None
-            hit = bool(L0 is not None and ops.gated_coef_ok(M, c["inter"], c["hidden"], c["hidden"], L0["wgu"].stride(0), c["hidden"],
-                                                            L0["wd"].stride(0), self.act, self.dtype))
-            self._nf_cache[key] = hit
-        return hit
+        return self._fused(M).coef
 
     def _norm_fused(self, M, fwd_only=False):
         """K1n applies: folded norm weights, efficient placement (no stabiliser on the residual add / the Linears: eps = 0), and every GEMM on
         both sides of the two norms is a problem the ping-pong kernel's fused epilogues take (bf16, >= 190 tiles, N % 256 == 0).  fwd_only: the
         FORWARD half is the same computation under both placements (the explicit one additionally keeps each Linear's own output: round 6)"""
-        if not (self.folded and ops.NORM_FUSION and (self.mode == "efficient" or fwd_only)):
-            return False
-        key = ("nf", M, PITCH_PAD, repr(ops.NORM_FUSION), ops.GATED_FUSION)
-        hit = self._nf_cache.get(key)
-        if hit is None:
-            c = self.cfg
-            H, I, d, nq, nk = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"]
-            nqkv = (nq + 2 * nk) * d
-            L0 = self.layers[0] if self.layers else None
-            ok = L0 is not None and self._gated_coef(M)
-            if ok:
-                pt = self._pitches()
-                ok = all(ops.norm_fused_ok(*a, self.dtype) for a in (
-                    (M, H, nq * d, nq * d, L0["wo"].stride(0), False),              # h1 = h + o Wo^T
-                    (M, H, I, pt["m"], L0["wd"].stride(0), False),                  # h' = h1 + m Wd^T
-                    (M, nqkv, H, H, L0["wqkv"].stride(0), False),                   # qkv = rstd (h W'qkv^T)
-                    (M, 2 * I, H, H, L0["wgu"].stride(0), False),                   # gate/up = rstd (h1 W'gu^T)
-                    (M, H, nqkv, pt["Aqkv"], L0["wqkv"].stride(0), True),           # G_h = rstd (Aqkv W'qkv) + G_res
-                    (M, H, 2 * I, pt["Agu"], L0["wgu"].stride(0), True)))
-            self._nf_cache[key] = hit = bool(ok)
-        return hit
+        return bool(self.folded and ops.NORM_FUSION and (self.mode == "efficient" or fwd_only) and self._fused(M).norm)
+
+    def _alloc(self, li):
+        """arena allocator of the fused-layer functions for layer li (the gradient a layer hands down alternates between two buffers)"""
+        def alloc(tag, rows, cols, pad, dtype):
+            key = tag if tag in FUSED_SCRATCH else ("Gs", li & 1) if tag == "Gh" else (tag, li)
+            return self._arena.get(key, (rows, cols), dtype, pad=pad)
+        return alloc
 
     def build_transposes(self):
         """kept for callers of the round-2 API (bench.py, dist tests): the bf16 engine holds no W^T copies any more; the fp32 parity
@@ -359,18 +433,11 @@ class LlamaLRP:
         nL = len(self.layers)
         for li, Lw in enumerate(self.layers):
             st = {}
-            rotated = False
             top = self.sparse_top and li == nL - 1
             if ready is not None:
                 st["h"], st["rstd1"] = ready
                 ready = None
-                qkv = new(("qkv", li), M, nqkv)
-                if not explicit and S <= self.max_seq and ops.gemm_nt_rs_rope_ok(st["h"], Lw["wqkv"], qkv, S, nqk, d):
-                    # RoPE in the QKV GEMM's epilogue: q and k leave the kernel rotated (no rope_fwd pass, no second copy of q / k)
-                    ops.gemm_nt_rs_rope(st["h"], Lw["wqkv"], st["rstd1"], self.cos, self.sin, qkv, S, nqk, d)
-                    rotated = True
-                else:
-                    ops.gemm_nt_rs(st["h"], Lw["wqkv"], st["rstd1"], qkv)
+                qkv, qkr = fused_qkv_fwd(st["h"], st["rstd1"], Lw["wqkv"], self.cos, self.sin, S, self.meta, self._alloc(li), explicit)
             else:
                 x, st["rstd1"] = new("x", M, H), f32(("rstd1", li), M)
                 if branch is None:
@@ -380,7 +447,15 @@ class LlamaLRP:
                     st["h"] = new(("h", li), M, H)
                     ops.add_rmsnorm_fwd(h_prev, branch, Lw["ln1"], c["rms_eps"], hsum_out=st["h"], y=x, rstd=st["rstd1"])
                 qkv = self._lin_fwd(x, Lw["wqkv"], new(("qkv", li), M, nqkv))
-            qkr = qkv[:, :nqk] if rotated else ops.rope_fwd(qkv, new(("qkr", li), M, nqk), self.cos, self.sin, S, nq + nk, d)
+                qkr = ops.rope_fwd(qkv, new(("qkr", li), M, nqk), self.cos, self.sin, S, nq + nk, d)
+            if nf and not top:
+                # (not chained in the last layer: the tail below wants h1 and dn of the explained rows separately)
+                st.update(fused_layer_fwd(st["h"], st["rstd1"], qkv, qkr, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv, explicit,
+                                          (self.eps_g, self.eps["lin"]), chain=li + 1 < nL), qkv=qkv, qkr=qkr, coef=True)
+                stash.append(st)
+                ready = (st["h_out"], st["rstd_out"]) if li + 1 < nL else None
+                h_prev, branch = st["h1"], st["dn"]             # (read after the last layer only)
+                continue
             v = qkv[:, nqk:]
             v_t = ops.transpose_heads(v, B, S, nk, d) if self.attn_t else None
             o = new(("o", li), M, nq * d)
@@ -398,28 +473,6 @@ class LlamaLRP:
                 h_prev, branch = h1_l, dn_l
                 break
             ops.attn_fwd(qkr[:, : nq * d], qkr[:, nq * d:], v, v_t, o, lse, B, S, nq, nk, d, scale, True, 0, row_iv=row_iv)
-            if nf:
-                # h1 = h + o Wo^T and its rows' sums of squares in ONE launch; the gate/up GEMM reads the un-normalised h1 and scales its output
-                # rows by rstd2; the down projection leaves the next layer's input sum and ITS statistics the same way (the last layer's keeps
-                # the stand-alone form: the tail below wants h1 and dn of the explained rows separately)
-                h1, ssq = new(("h1", li), M, H), ar.get("ssq", (H // 64, M), torch.float32)
-                a_raw = new(("a", li), M, H) if explicit else None      # explicit placement: the o-projection's own output (its stabiliser divides by it)
-                ops.gemm_res_ssq(o, Lw["wo"], st["h"], h1, ssq, raw=a_raw)
-                st["rstd2"] = ops.rms_rstd(ssq, M, H, c["rms_eps"], f32(("rstd2", li), M))
-                gu, m = ops.gemm_gated_fwd_coef(h1, Lw["wgu"], new(("gu", li), M, 2 * I), wide("m", M, I), self.eps_g, self.eps["lin"], self.act,
-                                                rs=st["rstd2"])
-                st.update(qkv=qkv, qkr=qkr, o=o, lse=lse, a=a_raw, h1=h1, gu=gu, coef=True, dn=None)
-                stash.append(st)
-                if li + 1 < nL:
-                    hn = new(("h", li + 1), M, H)
-                    st["dn"] = new(("dn", li), M, H) if explicit else None
-                    ops.gemm_res_ssq(m, Lw["wd"], h1, hn, ssq, raw=st["dn"])
-                    ready = (hn, ops.rms_rstd(ssq, M, H, c["rms_eps"], f32(("rstd1", li + 1), M)))
-                    h_prev, branch = hn, None
-                else:
-                    st["dn"] = self._lin_fwd(m, Lw["wd"], new(("dn", li), M, H))
-                    h_prev, branch = h1, st["dn"]
-                continue
             a = self._lin_fwd(o, Lw["wo"], new(("a", li), M, H))
             h1 = new(("h1", li), M, H)
             x2, st["rstd2"] = new("x2", M, H), f32(("rstd2", li), M)
@@ -480,16 +533,20 @@ class LlamaLRP:
         layer_R = [rel_last] if layer_relevance else None
         plain_add = E["add"] == 0.0 and E["lin"] == 0.0          # efficient placement: add2 / Linear eps factors are exactly 1
         nfb = plain_add and self._norm_fused(M)                  # K1n in the backward (independent of what the forward ran: both need only rstd)
+        full = nfb and self._fused(M).full                       # dense layers: fused_layer_bwd; below, the partial forms (A/B knobs, explicit)
         # attn_bwd_prep folded away (efficient placement, the bf16 kernels that take every operand token-major, M = B S rows)
-        fuse_prep = (plain_add and E["pv"] == 0.0 and E["mask"] == 0.0 and E["qk"] == 0.0 and not self.attn_t and ops.attn_dq_d_ok(dt, d)
-                     and bool(self.layers) and ops.norm_fused_ok(M, nq * d, H, H, self.layers[0]["wo"].stride(0), True, dt))      # (Aa [M, H] contiguous)
-        half = ar.get("half", (M,), torch.float32).fill_(0.5) if fuse_prep else None
+        fuse_prep = plain_add and E["pv"] == 0.0 and E["mask"] == 0.0 and E["qk"] == 0.0 and not self.attn_t and self._fused(M).prep
+        half = ar.get("half", (M,), torch.float32).fill_(0.5) if fuse_prep else None              # (fused_layer_bwd reads it too)
         fuse_rope = fuse_prep and ops.ROPE_BWD_FUSION and E["rope"] == 0.0 and E["lin"] == 0.0 and d in (64, 128) and S <= self.max_seq
 
         for li in range(len(self.layers) - 1, -1, -1):
             Lw, st = self.layers[li], fw["stash"][li]
             qkv, qkr = st["qkv"], st["qkr"]
             q_begin = 0
+            if full and not st.get("top", False):          # (Adn = Gs: eps = 0)
+                Gs = Adn = fused_layer_bwd(Gs, st, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv)
+                layer_R = layer_R + [ops.readout(st["h"], Gs, out=f32(("rel", li), M))] if layer_relevance else None
+                continue
             if st.get("top", False):
                 # ---- one row per prompt through MLP, norm/add2 and o-proj; scatter into the dense attention inputs
                 gu_l = st["gu_l"]
@@ -544,9 +601,7 @@ class LlamaLRP:
                 q_t = ops.transpose_heads(q, B, S, nq, d)
                 Gho_t = ops.transpose_heads(Gho, B, S, nq, d)
             dk_h, dv_h = new("dk_h", M, nq * d), new("dv_h", M, nq * d)
-            # (row pitch off the 4-KiB grid: the dQ kernel stores one row segment per lane straight into it, and 12 KiB would put them all on the
-            # same channels -- dqk's 10 KiB never did)
-            Aqkv = ar.get("Aqkv", (M, nqkv), dt, pad=self._pitches()["Aqkv_pad"])
+            Aqkv = ar.get("Aqkv", (M, nqkv), dt, pad=fused_layout(H, I, nq, nk, d, dt)["Aqkv"] - nqkv)
             if fuse_prep and q_begin == 0 and fuse_rope:
                 # RoPE's backward rides on the dQ store and on dK's group sum (no rope_bwd pass, no dqk round trip): both write Aqkv directly
                 ops.attn_bwd_dq_d(q, k, v, Gho, st["o"], st["lse"], D, Aqkv[:, : nq * d], B, S, nq, nk, d, scale, row_iv=row_iv,
