@@ -22,6 +22,7 @@ MI355X-first decisions:
 Python only sequences kernel launches on the current stream; it performs no arithmetic.
 """
 import collections
+import math
 
 import torch
 
@@ -239,6 +240,198 @@ def fused_layer_bwd(G, st, W, cos, sin, B, S, meta, alloc, row_iv=None):
 FUSED_SCRATCH = frozenset(("ssq", "m", "half", "Agu", "Gs1", "Gho", "D", "Aqkv", "dk_h", "dv_h"))      # temporaries: one buffer serves every layer
 
 
+# ---- the scaffolding of the fused drivers (LlamaLRP here, Gemma3LRP / Gemma3MMLRP / BertLRP in their modules): one owner per decision
+
+def pack_flat(top, layer, n_layers, dtype, device):
+    """ONE flat buffer holds every weight of a model (a multi-GPU start-up is then a single broadcast of it, lxt_amd.dist.broadcast_weights).
+    top / layer: {name: (shape, row pitch or None)} of the model-wide weights and of one layer's, in storage order; the buffer's size follows
+    from these lists alone.  -> (flat, {name: view}, one {name: view} per layer).  Every view starts 128-byte aligned; with a row pitch it is a
+    [rows, cols] view of [rows, pitch] storage.  device="meta" gives the layout without memory."""
+    up = lambda n: (n + 63) // 64 * 64                                   # noqa: E731
+    stored = lambda shape, pitch: (*shape[:-1], pitch or shape[-1])      # noqa: E731  (the [rows, pitch] block behind a view)
+    specs = [top] + [layer] * n_layers
+    flat = torch.empty(sum(up(math.prod(stored(*e))) for spec in specs for e in spec.values()), device=device, dtype=dtype)
+    views, o = [], 0
+    for spec in specs:
+        views.append({})
+        for name, (shape, pitch) in spec.items():
+            full = stored(shape, pitch)
+            views[-1][name] = flat[o: o + math.prod(full)].view(full)[..., : shape[-1]]
+            o += up(math.prod(full))
+    return flat, views[0], views[1:]
+
+
+def put_rows(dst, *srcs):
+    """dst <- srcs stacked along the rows, in dst's device and dtype"""
+    o = 0
+    for t in srcs:
+        dst[o: o + t.shape[0]].copy_(t.to(device=dst.device, dtype=dst.dtype, non_blocking=True))
+        o += t.shape[0]
+    return dst
+
+
+def put_gate_up(dst, wg, wu):
+    """gate / up rows interleaved in blocks of 32 (ops.interleave_gate_up): the gated-MLP rules then run inside the GEMM epilogues"""
+    return ops.interleave_gate_up(wg.to(device=dst.device, dtype=dst.dtype), wu.to(device=dst.device, dtype=dst.dtype), out=dst)
+
+
+def rope_tables(inv_freq, attention_scaling, max_seq, dtype, device):
+    """-> (cos, sin) [max_seq, d] of the rotary frequencies inv_freq [d / 2].  HF hands cos / sin to the layers in the model dtype; keep that
+    rounding, store as fp32 tables"""
+    fr = torch.arange(max_seq, dtype=torch.float32)[:, None] * inv_freq.float().cpu()[None, :]
+    emb = torch.cat((fr, fr), dim=-1)
+    return ((emb.cos() * attention_scaling).to(dtype).to(torch.float32).to(device).contiguous(),
+            (emb.sin() * attention_scaling).to(dtype).to(torch.float32).to(device).contiguous())
+
+
+class Arena:
+    """Workspace arena: every activation stash and every temporary of one explanation lives in a flat buffer keyed by a tag; the
+    buffers persist across calls (same B*S -> no allocator traffic in the per-layer loops, and stable addresses for hipGraph
+    replay).  A tag is (name, layer or None); temporaries share one tag across layers.  new / f32 / zeros / wide: the forms the drivers
+    allocate, in the model dtype unless named."""
+
+    def __init__(self, device, dtype):
+        self.device, self.dtype, self.buf = device, dtype, {}
+        self.gen = 0          # bumped whenever a buffer is REPLACED by a larger one: captured graphs hold the old address (GraphCache drops them)
+
+    def get(self, tag, shape, dtype, zero=False, pad=0):
+        """pad: extra elements per row of a 2-D buffer (the view returned is [rows, cols] with row pitch cols + pad)"""
+        full = tuple(shape[:-1]) + (shape[-1] + pad,) if pad else tuple(shape)
+        n = math.prod(full)
+        t = self.buf.get((tag, dtype))
+        if t is None or t.numel() < n:
+            if t is not None:
+                self.gen += 1
+            t = torch.empty(max(n, 1), device=self.device, dtype=dtype)
+            self.buf[(tag, dtype)] = t
+        v = t[:n].view(*full)
+        if zero:
+            v.zero_()
+        return v[..., : shape[-1]] if pad else v
+
+    def new(self, tag, *shape):
+        return self.get(tag, shape, self.dtype)
+
+    def f32(self, tag, *shape):
+        return self.get(tag, shape, torch.float32)
+
+    def zeros(self, tag, *shape):
+        return self.get(tag, shape, self.dtype, zero=True)
+
+    def wide(self, tag, rows, cols):
+        """a long-K GEMM operand: row pitch off the 4-KiB grid (pitch_pad)"""
+        return self.get(tag, (rows, cols), self.dtype, pad=pitch_pad(cols, self.dtype.itemsize))
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in self.buf.values())
+
+
+def explain_inputs(input_ids, inputs_embeds, lengths, target, vocab, max_seq, dtype, device, seed=None):
+    """The checks and conversions in front of an explanation; every ValueError is raised before a kernel of the model runs.
+    input_ids [B, S] or inputs_embeds [B, S, H] -> (B, S, emb [B S, H] on the device or None, row_iv, idx):
+      lengths [B]: prompts LEFT-padded to S -> row_iv = (lo, hi) int32 [B, S], the per-row key intervals of the attention kernels (pad rows:
+      empty); else None;  target [B] -> idx int32 vocabulary indices (None: the caller takes the arg-max);  seed [B, V]: instead of target."""
+    B, S = input_ids.shape if inputs_embeds is None else inputs_embeds.shape[:2]
+    if S > max_seq:
+        raise ValueError(f"sequence length {S} exceeds max_seq={max_seq}")
+    row_iv = None
+    if lengths is not None:
+        lens = torch.as_tensor(lengths, device=device).to(torch.int32).reshape(B)
+        if int(lens.min()) < 1 or int(lens.max()) > S:
+            raise ValueError("lengths must lie in [1, S]")
+        i = torch.arange(S, device=device, dtype=torch.int32)
+        first = (S - lens)[:, None]
+        lo = first.expand(B, S).contiguous()
+        hi = torch.where(i[None] >= first, (i + 1)[None].expand(B, S), torch.zeros_like(lo)).contiguous()   # pad rows: empty
+        row_iv = (lo, hi)
+    idx = None
+    if target is not None:
+        tgt = torch.as_tensor(target).reshape(-1).cpu().long()
+        if tgt.numel() != B or int(tgt.min()) < 0 or int(tgt.max()) >= vocab:
+            raise ValueError(f"target must hold {B} vocabulary indices in [0, {vocab})")
+        idx = tgt.to(device=device, dtype=torch.int32).contiguous()
+    if seed is not None:
+        if target is not None:
+            raise ValueError("pass either target or seed, not both")
+        if tuple(seed.shape) != (B, vocab):
+            raise ValueError(f"seed must have shape ({B}, {vocab}), got {tuple(seed.shape)}")
+    emb = None if inputs_embeds is None else inputs_embeds.to(device=device, dtype=dtype).reshape(B * S, -1).contiguous()
+    return B, S, emb, row_iv, idx
+
+
+class GraphCache:
+    """hipGraph capture and replay of whole explanations, one graph per key.  The first call of a key warms up on a side stream (sizes the
+    workspace, loads the kernels), then captures run(*inputs) on static copies of the inputs; every call copies its inputs into those and
+    replays.  The returned tensors are the graph's static outputs (copy them before the next call).  gen(): the workspace generation -- a
+    graph captured before the arena re-allocated one of its buffers (a later, larger call) points into freed memory: it is dropped and
+    captured again against the arena as it is now."""
+
+    def __init__(self, device, gen=lambda: 0):
+        self.device, self.gen, self.graphs = device, gen, {}
+
+    def clear(self):
+        self.graphs = {}
+
+    def __call__(self, key, run, *inputs):
+        g = self.graphs.get(key)
+        if g is not None and g[3] != self.gen():
+            del self.graphs[key]
+            g = None
+        if g is None:
+            static = [None if t is None else t.clone() for t in inputs]
+            side = torch.cuda.Stream(self.device)
+            side.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(side):                        # warm-up outside the capture
+                run(*static)
+            torch.cuda.current_stream(self.device).wait_stream(side)
+            cg = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(cg):
+                out = run(*static)
+            g = self.graphs[key] = (cg, static, out, self.gen())
+        cg, static, out, _ = g
+        for s, t in zip(static, inputs):
+            if s is not None:
+                s.copy_(t)
+        cg.replay()
+        return out
+
+
+def head_fwd(ar, h, branch, top, last, norm, lm_head, eps, w_offset=0.0):
+    """final residual add h + branch, norm and LM head on the explained (last) row of each prompt; top: the sparse top layer has left one row
+    per prompt already.  -> dict(hL_last, dn_last, rstd_f, logits) for the explanation's backward"""
+    B = last.shape[0]
+    if not top:
+        h = h.index_select(0, last)
+        branch = None if branch is None else branch.index_select(0, last)
+    hL_last = ar.new("hL_last", B, h.shape[1])
+    xn, rstd_f = ops.add_rmsnorm_fwd(h, branch, norm, eps, w_offset, hsum_out=hL_last)
+    logits = ops.linear_fwd(xn, lm_head, out=ar.f32("logits", B, lm_head.shape[0]))
+    return dict(hL_last=hL_last, dn_last=branch, rstd_f=rstd_f, logits=logits)
+
+
+def top_attn_operands(ar, Gof_l, o_l, Gs1_l, last, S, nq, d, eps_pv):
+    """the sparse top layer's backward has one live row per prompt: the attention's output-gradient prep on those rows, then the scatter into
+    the dense [M, .] operands of the attention backward (library launches only: zero fill + row scatter; D's live column S - 1 is a strided
+    2-D scatter of the same kind).  -> (Gho, D, Gs1)"""
+    B = last.shape[0]
+    Gho_l, D_l = ar.new("Gho_l", B, nq * d), ar.f32("D_l", B, nq, 1)
+    ops.attn_bwd_prep(Gof_l, o_l, Gho_l, D_l, B, 1, nq, d, eps_pv, 0.5)
+    Gho = ar.zeros("Gho", B * S, nq * d).index_copy_(0, last, Gho_l)
+    D = ar.get("D", (B, nq, S), torch.float32, zero=True)
+    D.view(B * nq, S)[:, S - 1].copy_(D_l.view(B * nq))
+    Gs1 = ar.zeros("Gs1", B * S, Gs1_l.shape[1]).index_copy_(0, last, Gs1_l)
+    return Gho, D, Gs1
+
+
+def explanation(emb, G, idx, logits, B, S, return_G=False):
+    """what explain() returns: dict(idx [B], logit [B], R_tok [B, S] fp32 = sum_h emb (*) G, logits [B, V][, G_emb, emb [B, S, H]])"""
+    logits = logits.clone()                                  # (the arena's buffer is overwritten by the next call)
+    out = dict(idx=idx, logit=logits.gather(1, idx.long()[:, None])[:, 0], R_tok=ops.readout(emb, G).view(B, S), logits=logits)
+    if return_G:
+        out["G_emb"], out["emb"] = G.view(B, S, -1).clone(), emb.view(B, S, -1)
+    return out
+
+
 class LlamaLRP:
     """Device-resident weights (each ONCE, forward layout, one flat buffer) + explain()."""
 
@@ -246,6 +439,8 @@ class LlamaLRP:
         if not torch.cuda.is_available():
             raise RuntimeError("LlamaLRP needs a HIP device: the LRP kernels have no CPU fallback")
         self.cfg, self.dtype, self.device = dict(cfg), dtype, torch.device(device)
+        self._arena = Arena(self.device, dtype)
+        self._graphs = GraphCache(self.device, lambda: self._arena.gen)
         self.set_mode(mode)
         # top-layer sparsity: above the last attention layer only the LAST token of a prompt feeds the
         # explained logit and carries relevance, so the last layer's o-proj / MLP (forward and backward) and
@@ -264,64 +459,26 @@ class LlamaLRP:
         # ONE flat device buffer holds every weight in its forward layout (embedding, norms, LM head, per layer the fused
         # [q;k;v] and [gate;up] matrices, o, down): the tensors below are views into it, so the multi-GPU start-up is a
         # single broadcast of `self.flat` (lxt_amd.dist.broadcast_weights) followed by the LOCAL W^T copies
-        H, I, nq, nk, hd, V = cfg["hidden"], cfg["inter"], cfg["n_heads"], cfg["n_kv"], cfg["head_dim"], cfg["vocab"]
-        nqkv = (nq + 2 * nk) * hd
-        up = lambda n: (n + 63) // 64 * 64                                   # noqa: E731  (every view starts 128-byte aligned)
-        self.meta = (nq, nk, hd, cfg["rms_eps"], self.act, hd ** -0.5)      # (the layer description of the fused-layer functions above)
-        pt = fused_layout(H, I, nq, nk, hd, dtype)
-        per_layer = 2 * up(H) + up(nqkv * pt["Wqkv"]) + up(H * nq * hd) + up(2 * I * pt["Wgu"]) + up(H * pt["Wd"])
-        total = 2 * up(V * H) + up(H) + len(W["layers"]) * per_layer
-        self.flat = torch.empty(total, device=dev, dtype=dtype)
-        cursor = [0]
-
-        def take(*shape, pitch=None):
-            # pitch: a [rows, cols] view with that row pitch (fused_layout: off the 4-KiB grid)
-            full = shape[:-1] + (pitch or shape[-1],)
-            n = 1
-            for s_ in full:
-                n *= s_
-            v = self.flat[cursor[0]: cursor[0] + n].view(*full)
-            cursor[0] += up(n)
-            return v[..., : shape[-1]]
-
-        def put(dst, *srcs):
-            o = 0
-            for t in srcs:
-                rows = t.shape[0]
-                dst[o: o + rows].copy_(t.to(device=dev, dtype=dtype, non_blocking=True))
-                o += rows
-            return dst
-
-        def put_gu(dst, wg, wu):
-            # gate / up rows interleaved in blocks of 32 (ops.interleave_gate_up): the gated-MLP rules then run inside the GEMM epilogues
-            return ops.interleave_gate_up(wg.to(device=dev, dtype=dtype), wu.to(device=dev, dtype=dtype), out=dst)
-
-        self.embed, self.lm_head = put(take(V, H), W["embed"]), put(take(V, H), W["lm_head"])
-        self.norm = put(take(H), W["norm"])
+        nq, hd = cfg["n_heads"], cfg["head_dim"]
+        self.meta = (nq, cfg["n_kv"], hd, cfg["rms_eps"], self.act, hd ** -0.5)      # (the layer description of the fused-layer functions above)
+        self.flat, top, self.layers = pack_flat(*self.flat_layout(cfg, dtype), len(W["layers"]), dtype, dev)
+        self.embed, self.lm_head, self.norm = (put_rows(top[k], W[k]) for k in ("embed", "lm_head", "norm"))
         self.lm_head_t = None                        # [H, V] copy, made on the first dense-seed explanation
-        self.layers = []
-
-        for L in W["layers"]:
-            Lw = dict(ln1=put(take(H), L["ln1"]), ln2=put(take(H), L["ln2"]),
-                      wqkv=put(take(nqkv, H, pitch=pt["Wqkv"]), L["wq"], L["wk"], L["wv"]), wo=put(take(H, nq * hd), L["wo"]),
-                      wgu=put_gu(take(2 * I, H, pitch=pt["Wgu"]), L["wg"], L["wu"]), wd=put(take(H, I, pitch=pt["Wd"]), L["wd"]))
+        for Lw, L in zip(self.layers, W["layers"]):
+            for k in ("ln1", "ln2", "wo", "wd"):
+                put_rows(Lw[k], L[k])
+            put_rows(Lw["wqkv"], L["wq"], L["wk"], L["wv"])
+            put_gate_up(Lw["wgu"], L["wg"], L["wu"])
             if self.folded:          # (in place, on the weights as stored: the product sees the storage dtype's rounding of W)
                 fold_rows(Lw["wqkv"], (Lw["wqkv"],), L["ln1"])
                 fold_rows(Lw["wgu"], (Lw["wgu"],), L["ln2"])
                 Lw["ln1"].fill_(1.0)
                 Lw["ln2"].fill_(1.0)
-            self.layers.append(Lw)
-        self.attn_t = ops.attn_needs_transposed(self.embed, cfg["head_dim"])
-        d = cfg["head_dim"]
+        self.attn_t = ops.attn_needs_transposed(self.embed, hd)
         inv = cfg.get("inv_freq")                    # scaled rope types: HF's own frequencies (config_from_hf)
         if inv is None:
-            inv = 1.0 / (cfg["rope_theta"] ** (torch.arange(0, d, 2, dtype=torch.float32) / d))
-        att = float(cfg.get("attention_scaling", 1.0))
-        fr = torch.arange(max_seq, dtype=torch.float32)[:, None] * inv.float().cpu()[None, :]
-        emb = torch.cat((fr, fr), dim=-1)
-        # HF hands cos/sin to the layers in the model dtype; keep that rounding, store as fp32 tables
-        self.cos = (emb.cos() * att).to(dtype).to(torch.float32).to(dev).contiguous()
-        self.sin = (emb.sin() * att).to(dtype).to(torch.float32).to(dev).contiguous()
+            inv = 1.0 / (cfg["rope_theta"] ** (torch.arange(0, hd, 2, dtype=torch.float32) / hd))
+        self.cos, self.sin = rope_tables(inv, float(cfg.get("attention_scaling", 1.0)), max_seq, dtype, dev)
         self.max_seq = max_seq
         torch.cuda.synchronize(dev)
 
@@ -361,6 +518,15 @@ class LlamaLRP:
             ops.clear_weight_cache(L["wqkv"], L["wo"], L["wgu"], L["wd"])
         self.lm_head_t = None
 
+    @staticmethod
+    def flat_layout(cfg, dtype):
+        """(shape, row pitch) of the weights in `flat` (pack_flat): the model-wide ones, then one layer's; the Linears at fused_layout's pitches"""
+        H, I, nq, nk, d, V = cfg["hidden"], cfg["inter"], cfg["n_heads"], cfg["n_kv"], cfg["head_dim"], cfg["vocab"]
+        pt = fused_layout(H, I, nq, nk, d, dtype)
+        return (dict(embed=((V, H), None), lm_head=((V, H), None), norm=((H,), None)),
+                dict(ln1=((H,), None), ln2=((H,), None), wqkv=(((nq + 2 * nk) * d, H), pt["Wqkv"]), wo=((H, nq * d), None),
+                     wgu=((2 * I, H), pt["Wgu"]), wd=((H, I), pt["Wd"])))
+
     @classmethod
     def from_hf(cls, model, **kw):
         cfg, W = weights_from_hf(model)
@@ -371,58 +537,25 @@ class LlamaLRP:
         if mode not in ("explicit", "efficient"):
             raise ValueError(f"mode must be 'explicit' or 'efficient', got {mode!r}")
         self.mode = mode
-        self._graphs = {}
+        self._graphs.clear()
         self.eps = dict(EXPLICIT if mode == "explicit" else EFFICIENT)
         # identity rule (*) gate Linear eps: act/(g+eps_lin) in explicit form, act/(g+1e-10) efficient
         self.eps_g = self.eps["lin"] if mode == "explicit" else self.eps["act"]
 
     # ---------------------------------------------------------------------------------------------
-    class _Arena:
-        """Workspace arena: every activation stash and every temporary of one explanation lives in a flat buffer keyed by a tag; the
-        buffers persist across calls (same B*S -> no allocator traffic in the per-layer loops, and stable addresses for hipGraph
-        replay).  A tag is (name, layer or None); temporaries share one tag across layers."""
-
-        def __init__(self, device):
-            self.device, self.buf = device, {}
-            self.gen = 0          # bumped whenever a buffer is REPLACED by a larger one: captured graphs hold the old address (engine drops them)
-
-        def get(self, tag, shape, dtype, zero=False, pad=0):
-            """pad: extra elements per row of a 2-D buffer (the view returned is [rows, cols] with row pitch cols + pad)"""
-            full = tuple(shape[:-1]) + (shape[-1] + pad,) if pad else tuple(shape)
-            n = 1
-            for s_ in full:
-                n *= s_
-            t = self.buf.get((tag, dtype))
-            if t is None or t.numel() < n:
-                if t is not None:
-                    self.gen += 1
-                t = torch.empty(max(n, 1), device=self.device, dtype=dtype)
-                self.buf[(tag, dtype)] = t
-            v = t[:n].view(*full)
-            if zero:
-                v.zero_()
-            return v[..., : shape[-1]] if pad else v
-
-        def nbytes(self):
-            return sum(t.numel() * t.element_size() for t in self.buf.values())
-
     def release(self):
         """drop the arena (and the captured graphs that point into it)"""
-        self._arena, self._graphs = None, {}
+        self._arena = Arena(self.device, self.dtype)
+        self._graphs.clear()
 
     def forward(self, emb, B, S, row_iv=None):
         c = self.cfg
         H, I, d, nq, nk = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"]
         M = B * S
-        dev, dt = self.device, self.dtype
+        dev = self.device
         nqk, nqkv = (nq + nk) * d, (nq + 2 * nk) * d
         scale = d ** -0.5
-        if getattr(self, "_arena", None) is None:
-            self._arena = LlamaLRP._Arena(dev)
         ar = self._arena
-        new = lambda tag, *s: ar.get(tag, s, dt)  # noqa: E731
-        wide = lambda tag, r, c_: ar.get(tag, (r, c_), dt, pad=pitch_pad(c_, emb.element_size()))  # noqa: E731  (long-K GEMM operands)
-        f32 = lambda tag, *s: ar.get(tag, s, torch.float32)  # noqa: E731
         stash = []
         h_prev, branch = emb, None
         last = torch.arange(B, device=dev) * S + (S - 1)
@@ -439,15 +572,15 @@ class LlamaLRP:
                 ready = None
                 qkv, qkr = fused_qkv_fwd(st["h"], st["rstd1"], Lw["wqkv"], self.cos, self.sin, S, self.meta, self._alloc(li), explicit)
             else:
-                x, st["rstd1"] = new("x", M, H), f32(("rstd1", li), M)
+                x, st["rstd1"] = ar.new("x", M, H), ar.f32(("rstd1", li), M)
                 if branch is None:
                     st["h"] = h_prev
                     ops.add_rmsnorm_fwd(h_prev, None, Lw["ln1"], c["rms_eps"], y=x, rstd=st["rstd1"])
                 else:
-                    st["h"] = new(("h", li), M, H)
+                    st["h"] = ar.new(("h", li), M, H)
                     ops.add_rmsnorm_fwd(h_prev, branch, Lw["ln1"], c["rms_eps"], hsum_out=st["h"], y=x, rstd=st["rstd1"])
-                qkv = self._lin_fwd(x, Lw["wqkv"], new(("qkv", li), M, nqkv))
-                qkr = ops.rope_fwd(qkv, new(("qkr", li), M, nqk), self.cos, self.sin, S, nq + nk, d)
+                qkv = self._lin_fwd(x, Lw["wqkv"], ar.new(("qkv", li), M, nqkv))
+                qkr = ops.rope_fwd(qkv, ar.new(("qkr", li), M, nqk), self.cos, self.sin, S, nq + nk, d)
             if nf and not top:
                 # (not chained in the last layer: the tail below wants h1 and dn of the explained rows separately)
                 st.update(fused_layer_fwd(st["h"], st["rstd1"], qkv, qkr, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv, explicit,
@@ -458,42 +591,36 @@ class LlamaLRP:
                 continue
             v = qkv[:, nqk:]
             v_t = ops.transpose_heads(v, B, S, nk, d) if self.attn_t else None
-            o = new(("o", li), M, nq * d)
-            lse = f32(("lse", li), B, nq, S)
+            o = ar.new(("o", li), M, nq * d)
+            lse = ar.f32(("lse", li), B, nq, S)
             if top:
                 ops.attn_fwd(qkr[:, : nq * d], qkr[:, nq * d:], v, v_t, o, lse, B, S, nq, nk, d, scale, True, 0, q_begin=S - 1, row_iv=row_iv)
                 o_l, h_l = o.index_select(0, last), st["h"].index_select(0, last)
-                a_l = self._lin_fwd(o_l, Lw["wo"], new("a_l", B, H))
-                h1_l = new("h1_l", B, H)
+                a_l = self._lin_fwd(o_l, Lw["wo"], ar.new("a_l", B, H))
+                h1_l = ar.new("h1_l", B, H)
                 x2_l, rstd2_l = ops.add_rmsnorm_fwd(h_l, a_l, Lw["ln2"], c["rms_eps"], hsum_out=h1_l)
-                gu_l, m_l = ops.gemm_gated_fwd(x2_l, Lw["wgu"], new("gu_l", B, 2 * I), new("m_l", B, I), self.act)
-                dn_l = self._lin_fwd(m_l, Lw["wd"], new("dn_l", B, H))
+                gu_l, m_l = ops.gemm_gated_fwd(x2_l, Lw["wgu"], ar.new("gu_l", B, 2 * I), ar.new("m_l", B, I), self.act)
+                dn_l = self._lin_fwd(m_l, Lw["wd"], ar.new("dn_l", B, H))
                 st.update(top=True, qkv=qkv, qkr=qkr, lse=lse, o_l=o_l, a_l=a_l, h1_l=h1_l, rstd2_l=rstd2_l, gu_l=gu_l, dn_l=dn_l)
                 stash.append(st)
                 h_prev, branch = h1_l, dn_l
                 break
             ops.attn_fwd(qkr[:, : nq * d], qkr[:, nq * d:], v, v_t, o, lse, B, S, nq, nk, d, scale, True, 0, row_iv=row_iv)
-            a = self._lin_fwd(o, Lw["wo"], new(("a", li), M, H))
-            h1 = new(("h1", li), M, H)
-            x2, st["rstd2"] = new("x2", M, H), f32(("rstd2", li), M)
+            a = self._lin_fwd(o, Lw["wo"], ar.new(("a", li), M, H))
+            h1 = ar.new(("h1", li), M, H)
+            x2, st["rstd2"] = ar.new("x2", M, H), ar.f32(("rstd2", li), M)
             ops.add_rmsnorm_fwd(st["h"], a, Lw["ln2"], c["rms_eps"], hsum_out=h1, y=x2, rstd=st["rstd2"])
             if coef:      # the gated rules inside the two GEMMs around them: the backward's coefficients are stashed in gu's place (g, u never stored)
-                gu, m = ops.gemm_gated_fwd_coef(x2, Lw["wgu"], new(("gu", li), M, 2 * I), wide("m", M, I), self.eps_g, self.eps["lin"], self.act)
+                gu, m = ops.gemm_gated_fwd_coef(x2, Lw["wgu"], ar.new(("gu", li), M, 2 * I), ar.wide("m", M, I), self.eps_g, self.eps["lin"], self.act)
             else:
-                gu, m = ops.gemm_gated_fwd(x2, Lw["wgu"], new(("gu", li), M, 2 * I), wide("m", M, I), self.act)
-            dn = self._lin_fwd(m, Lw["wd"], new(("dn", li), M, H))
+                gu, m = ops.gemm_gated_fwd(x2, Lw["wgu"], ar.new(("gu", li), M, 2 * I), ar.wide("m", M, I), self.act)
+            dn = self._lin_fwd(m, Lw["wd"], ar.new(("dn", li), M, H))
             st.update(qkv=qkv, qkr=qkr, o=o, lse=lse, a=a, h1=h1, gu=gu, coef=coef, dn=dn)
             stash.append(st)
             h_prev, branch = h1, dn
         # last token only: final residual add + norm + LM head
-        if h_prev.shape[0] == B and self.sparse_top and len(self.layers) > 0:
-            h1_last, dn_last = h_prev, branch
-        else:
-            h1_last, dn_last = h_prev.index_select(0, last), branch.index_select(0, last)
-        hL_last = new("hL_last", B, H)
-        xn, rstd_f = ops.add_rmsnorm_fwd(h1_last, dn_last, self.norm, c["rms_eps"], hsum_out=hL_last)
-        logits = self._lin_fwd(xn, self.lm_head, f32("logits", B, c["vocab"]))
-        return dict(stash=stash, last=last, hL_last=hL_last, dn_last=dn_last, rstd_f=rstd_f, logits=logits, row_iv=row_iv)
+        top = bool(stash) and stash[-1].get("top", False)
+        return dict(stash=stash, last=last, row_iv=row_iv, **head_fwd(ar, h_prev, branch, top, last, self.norm, self.lm_head, c["rms_eps"]))
 
     # ---------------------------------------------------------------------------------------------
     def backward(self, fw, emb, idx, B, S, layer_relevance=False, seed=None):
@@ -504,13 +631,9 @@ class LlamaLRP:
         nqk, nqkv = (nq + nk) * d, (nq + 2 * nk) * d
         scale = d ** -0.5
         ar = self._arena
-        new = lambda tag, *s: ar.get(tag, s, dt)  # noqa: E731
-        wide = lambda tag, r, c_: ar.get(tag, (r, c_), dt, pad=pitch_pad(c_, emb.element_size()))  # noqa: E731
-        f32 = lambda tag, *s: ar.get(tag, s, torch.float32)  # noqa: E731
-        zeros = lambda tag, *s: ar.get(tag, s, dt, zero=True)  # noqa: E731
         # LM head eps rule + final-norm identity rule on the single explained row of each prompt
         if seed is None:
-            Gh_last = ops.head_seed(self.lm_head, fw["logits"], idx, self.norm, fw["rstd_f"], new("Gh_last", B, H), 0.0, E["lin"])
+            Gh_last = ops.head_seed(self.lm_head, fw["logits"], idx, self.norm, fw["rstd_f"], ar.new("Gh_last", B, H), 0.0, E["lin"])
         else:
             # dense seed over the last-position logits (contrastive explanations): gradient in efficient mode, relevance
             # in explicit mode (coef = R / (z + eps)); G_xn = coef @ W_lm (ops.linear_dgrad: W streamed once from its stored layout),
@@ -519,24 +642,24 @@ class LlamaLRP:
             if E["lin"] != 0.0:
                 coef = ops.eps_scale(coef, fw["logits"], 1.0, E["lin"], relevance=True)
             g_xn = ops.linear_dgrad(coef.to(dt), self.lm_head, out_dtype=torch.float32)
-            Gh_last = ops.head_norm_bwd(g_xn, self.norm, fw["rstd_f"], new("Gh_last", B, H))
+            Gh_last = ops.head_norm_bwd(g_xn, self.norm, fw["rstd_f"], ar.new("Gh_last", B, H))
         # add2 at h_L = h1 + dn and the eps scale of the last down_proj, still one row per prompt
-        Gs_last, A_last = new("Gs_last", B, H), new("A_last", B, H)
-        rel_last = f32("rel_last", B) if layer_relevance else None
+        Gs_last, A_last = ar.new("Gs_last", B, H), ar.new("A_last", B, H)
+        rel_last = ar.f32("rel_last", B) if layer_relevance else None
         ops.rmsnorm_bwd_add2(Gh_last, None, None, None, fw["hL_last"], fw["dn_last"], Gs_last, A_last, rel_last,
                              0.0, E["add"], E["lin"])
         last, row_iv = fw["last"], fw["row_iv"]
         top_sparse = bool(fw["stash"]) and fw["stash"][-1].get("top", False)
         if not top_sparse:
-            Gs = zeros(("Gs", len(self.layers) & 1), M, H).index_copy_(0, last, Gs_last)
-            Adn = zeros(("Adn", len(self.layers) & 1), M, H).index_copy_(0, last, A_last)
+            Gs = ar.zeros(("Gs", len(self.layers) & 1), M, H).index_copy_(0, last, Gs_last)
+            Adn = ar.zeros(("Adn", len(self.layers) & 1), M, H).index_copy_(0, last, A_last)
         layer_R = [rel_last] if layer_relevance else None
         plain_add = E["add"] == 0.0 and E["lin"] == 0.0          # efficient placement: add2 / Linear eps factors are exactly 1
         nfb = plain_add and self._norm_fused(M)                  # K1n in the backward (independent of what the forward ran: both need only rstd)
         full = nfb and self._fused(M).full                       # dense layers: fused_layer_bwd; below, the partial forms (A/B knobs, explicit)
         # attn_bwd_prep folded away (efficient placement, the bf16 kernels that take every operand token-major, M = B S rows)
         fuse_prep = plain_add and E["pv"] == 0.0 and E["mask"] == 0.0 and E["qk"] == 0.0 and not self.attn_t and self._fused(M).prep
-        half = ar.get("half", (M,), torch.float32).fill_(0.5) if fuse_prep else None              # (fused_layer_bwd reads it too)
+        half = ar.f32("half", M).fill_(0.5) if fuse_prep else None              # (fused_layer_bwd reads it too)
         fuse_rope = fuse_prep and ops.ROPE_BWD_FUSION and E["rope"] == 0.0 and E["lin"] == 0.0 and d in (64, 128) and S <= self.max_seq
 
         for li in range(len(self.layers) - 1, -1, -1):
@@ -545,54 +668,46 @@ class LlamaLRP:
             q_begin = 0
             if full and not st.get("top", False):          # (Adn = Gs: eps = 0)
                 Gs = Adn = fused_layer_bwd(Gs, st, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv)
-                layer_R = layer_R + [ops.readout(st["h"], Gs, out=f32(("rel", li), M))] if layer_relevance else None
+                layer_R = layer_R + [ops.readout(st["h"], Gs, out=ar.f32(("rel", li), M))] if layer_relevance else None
                 continue
             if st.get("top", False):
                 # ---- one row per prompt through MLP, norm/add2 and o-proj; scatter into the dense attention inputs
                 gu_l = st["gu_l"]
-                Agu = ops.gemm_gated_bwd(A_last, Lw["wd"], gu_l, new("Agu_l", B, 2 * I), self.eps_g, E["lin"], self.act)
-                Gx2 = self._lin_bwd(Agu, Lw["wgu"], new("Gx2_l", B, H))
-                Gs1_l, Aa_l = new("Gs1_l", B, H), new("Aa_l", B, H)
+                Agu = ops.gemm_gated_bwd(A_last, Lw["wd"], gu_l, ar.new("Agu_l", B, 2 * I), self.eps_g, E["lin"], self.act)
+                Gx2 = self._lin_bwd(Agu, Lw["wgu"], ar.new("Gx2_l", B, H))
+                Gs1_l, Aa_l = ar.new("Gs1_l", B, H), ar.new("Aa_l", B, H)
                 ops.rmsnorm_bwd_add2(Gs_last, Gx2, Lw["ln2"], st["rstd2_l"], st["h1_l"], st["a_l"], Gs1_l, Aa_l, None, 0.0,
                                      E["add"], E["lin"])
-                Gof_l = self._lin_bwd(Aa_l, Lw["wo"], new("Gof_l", B, nq * d))
-                Gho_l = new("Gho_l", B, nq * d)
-                D_l = f32("D_l", B, nq, 1)
-                ops.attn_bwd_prep(Gof_l, st["o_l"], Gho_l, D_l, B, 1, nq, d, E["pv"], 0.5)
-                # scatter the one live row per prompt into the dense [M, .] operands of the attention backward (library launches only:
-                # zero fill + row scatter; D's live column S-1 is a strided 2-D scatter of the same kind)
-                Gho = zeros("Gho", M, nq * d).index_copy_(0, last, Gho_l)
-                D = ar.get("D", (B, nq, S), torch.float32, zero=True)
-                D.view(B * nq, S)[:, S - 1].copy_(D_l.view(B * nq))
-                Gs1 = zeros("Gs1", M, H).index_copy_(0, last, Gs1_l)
+                Gof_l = self._lin_bwd(Aa_l, Lw["wo"], ar.new("Gof_l", B, nq * d))
+                Gho, D, Gs1 = top_attn_operands(ar, Gof_l, st["o_l"], Gs1_l, last, S, nq, d, E["pv"])
                 q_begin = S - 1
             else:
                 gu = st["gu"]
                 # ---- MLP
                 if st.get("coef", False):
-                    Agu = ops.gemm_gated_bwd_coef(Adn, Lw["wd"], gu, wide("Agu", M, 2 * I))
+                    Agu = ops.gemm_gated_bwd_coef(Adn, Lw["wd"], gu, ar.wide("Agu", M, 2 * I))
                 else:
-                    Agu = ops.gemm_gated_bwd(Adn, Lw["wd"], gu, wide("Agu", M, 2 * I), self.eps_g, E["lin"], self.act)
-                Gs1 = new("Gs1", M, H)
+                    Agu = ops.gemm_gated_bwd(Adn, Lw["wd"], gu, ar.wide("Agu", M, 2 * I), self.eps_g, E["lin"], self.act)
+                Gs1 = ar.new("Gs1", M, H)
                 if nfb and ops.norm_fusion_part("bwd_gu"):               # K1n: Gs1 = rstd2 (.) (Agu W'gu) + Gs in the dgrad GEMM's epilogue
                     Aa = ops.gemm_nn_rs_res(Agu, Lw["wgu"], st["rstd2"], Gs, Gs1)
                 else:
-                    Gx2 = self._lin_bwd(Agu, Lw["wgu"], new("Gx2", M, H))
+                    Gx2 = self._lin_bwd(Agu, Lw["wgu"], ar.new("Gx2", M, H))
                     if plain_add:     # no stabiliser on the add / the branch's Linear: the branch gradient IS the residual gradient
                         ops.rmsnorm_bwd_add2(Gs, Gx2, Lw["ln2"], st["rstd2"], None, None, Gs1, None, None, 0.0, 0.0, 0.0)
                         Aa = Gs1
                     else:
-                        Aa = new("Aa", M, H)
+                        Aa = ar.new("Aa", M, H)
                         ops.rmsnorm_bwd_add2(Gs, Gx2, Lw["ln2"], st["rstd2"], st["h1"], st["a"], Gs1, Aa, None, 0.0, E["add"], E["lin"])
                 # ---- attention
-                Gho = new("Gho", M, nq * d)
-                D = f32("D", B, nq, S)
+                Gho = ar.new("Gho", M, nq * d)
+                D = ar.f32("D", B, nq, S)
                 if fuse_prep:
                     # no attn_bwd_prep pass: Gho = 1/2 (Aa Wo) straight out of the o-projection's dgrad (row scale 1/2: exact), and the dQ
                     # kernel forms D = rowsum(Gho (*) o) from the rows it loads anyway and leaves it for the dK / dV kernel
                     ops.gemm_nn_rs(Aa, Lw["wo"], half, Gho)
                 else:
-                    Gof = self._lin_bwd(Aa, Lw["wo"], new("Gof", M, nq * d))
+                    Gof = self._lin_bwd(Aa, Lw["wo"], ar.new("Gof", M, nq * d))
                     ops.attn_bwd_prep(Gof, st["o"], Gho, D, B, S, nq, d, E["pv"], 0.5)
             q, k, v = qkr[:, : nq * d], qkr[:, nq * d:], qkv[:, nqk:]
             k_t = q_t = Gho_t = None
@@ -600,7 +715,7 @@ class LlamaLRP:
                 k_t = ops.transpose_heads(k, B, S, nk, d)
                 q_t = ops.transpose_heads(q, B, S, nq, d)
                 Gho_t = ops.transpose_heads(Gho, B, S, nq, d)
-            dk_h, dv_h = new("dk_h", M, nq * d), new("dv_h", M, nq * d)
+            dk_h, dv_h = ar.new("dk_h", M, nq * d), ar.new("dv_h", M, nq * d)
             Aqkv = ar.get("Aqkv", (M, nqkv), dt, pad=fused_layout(H, I, nq, nk, d, dt)["Aqkv"] - nqkv)
             if fuse_prep and q_begin == 0 and fuse_rope:
                 # RoPE's backward rides on the dQ store and on dK's group sum (no rope_bwd pass, no dqk round trip): both write Aqkv directly
@@ -610,7 +725,7 @@ class LlamaLRP:
                 ops.gqa_reduce_rope(dk_h, Aqkv[:, nq * d: nqk], M, S, nk, rep, d, self.cos, self.sin)
                 ops.gqa_reduce(dv_h, Aqkv[:, nqk:], M, nk, rep, d)
             else:
-                dqk = new("dqk", M, nqk) if q_begin == 0 else zeros("dqk", M, nqk)
+                dqk = ar.new("dqk", M, nqk) if q_begin == 0 else ar.zeros("dqk", M, nqk)
                 if fuse_prep and q_begin == 0:
                     ops.attn_bwd_dq_d(q, k, v, Gho, st["o"], st["lse"], D, dqk[:, : nq * d], B, S, nq, nk, d, scale, row_iv=row_iv)
                 else:
@@ -623,32 +738,32 @@ class LlamaLRP:
                     ops.gqa_reduce(dv_h, Aqkv[:, nqk:], M, nk, rep, d)
                     ops.rope_bwd(dqk, None, None, Aqkv[:, :nqk], self.cos, self.sin, S, nq + nk, d, 0.0, 0.0)
                 else:
-                    dv = ops.gqa_reduce(dv_h, new("dv", M, nk * d), M, nk, rep, d)
+                    dv = ops.gqa_reduce(dv_h, ar.new("dv", M, nk * d), M, nk, rep, d)
                     ops.eps_scale2d(dv, v, Aqkv[:, nqk:], 1.0, E["lin"])
                     ops.rope_bwd(dqk, qkr, qkv[:, :nqk], Aqkv[:, :nqk], self.cos, self.sin, S, nq + nk, d, E["rope"], E["lin"])
-            rel = f32(("rel", li), M) if layer_relevance else None
+            rel = ar.f32(("rel", li), M) if layer_relevance else None
             if nfb and ops.norm_fusion_part("bwd_qkv"):
                 # K1n: Gs = rstd1 (.) (Aqkv W'qkv) + Gs1 -- the input norm's identity rule and the residual add in the qkv dgrad's epilogue.  The
                 # layer relevance sum_j h_j G_j (a diagnostic) is then one read-out pass over the stored gradient: the SAME kernels serve the call
                 # with and without it (a prompt's relevance must not depend on the options of the call)
-                Gs = ops.gemm_nn_rs_res(Aqkv, Lw["wqkv"], st["rstd1"], Gs1, new(("Gs", li & 1), M, H))
+                Gs = ops.gemm_nn_rs_res(Aqkv, Lw["wqkv"], st["rstd1"], Gs1, ar.new(("Gs", li & 1), M, H))
                 Adn = Gs
                 if layer_relevance:
                     layer_R.append(ops.readout(st["h"], Gs, out=rel))
                 continue
-            Gx = self._lin_bwd(Aqkv, Lw["wqkv"], new("Gx", M, H))
+            Gx = self._lin_bwd(Aqkv, Lw["wqkv"], ar.new("Gx", M, H))
             # ---- input norm + the residual add below (or the embedding)
             if li > 0:
                 prev = fw["stash"][li - 1]
-                Gs = new(("Gs", li & 1), M, H)
+                Gs = ar.new(("Gs", li & 1), M, H)
                 if plain_add:
                     ops.rmsnorm_bwd_add2(Gs1, Gx, Lw["ln1"], st["rstd1"], st["h"] if layer_relevance else None, None, Gs, None, rel, 0.0, 0.0, 0.0)
                     Adn = Gs
                 else:
-                    Adn = new(("Adn", li & 1), M, H)
+                    Adn = ar.new(("Adn", li & 1), M, H)
                     ops.rmsnorm_bwd_add2(Gs1, Gx, Lw["ln1"], st["rstd1"], st["h"], prev["dn"], Gs, Adn, rel, 0.0, E["add"], E["lin"])
             else:
-                Gs = new(("Gs", 0), M, H)
+                Gs = ar.new(("Gs", 0), M, H)
                 ops.rmsnorm_bwd_add2(Gs1, Gx, Lw["ln1"], st["rstd1"], st["h"] if layer_relevance else None, None, Gs, None,
                                      rel, 0.0, 0.0, 0.0)
             if layer_relevance:
@@ -665,15 +780,10 @@ class LlamaLRP:
             # (a dense seed explains no single logit; idx / logit then report the arg-max for convenience)
             idx, _ = ops.argmax_rows(fw["logits"])
         G, layer_R = self.backward(fw, emb, idx, B, S, layer_relevance, seed=seed)
-        R_tok = ops.readout(emb, G).view(B, S)
-        logits = fw["logits"].clone()                            # (the arena's buffer is overwritten by the next call)
-        out = dict(idx=idx, logit=logits.gather(1, idx.long()[:, None])[:, 0], R_tok=R_tok, logits=logits)
+        out = explanation(emb, G, idx, fw["logits"], B, S, return_G)
         if layer_relevance:
             rows = [layer_R[0]] + [r.view(B, S).sum(1) for r in layer_R[1:]]
             out["layer_R"] = torch.stack(rows[::-1], 0)          # [L+1, B], index 0 = embedding
-        if return_G:
-            out["G_emb"] = G.view(B, S, -1).clone()
-            out["emb"] = emb.view(B, S, -1)
         return out
 
     @torch.no_grad()
@@ -691,65 +801,13 @@ class LlamaLRP:
         in explicit mode.
         graph=True (input_ids only, no lengths / seed / return_G): the ~1500 launches of one explanation of this (B, S) are captured
         once into a hipGraph and replayed; the returned tensors are the graph's static outputs (copy them before the next call)."""
+        B, S, emb, row_iv, idx = explain_inputs(input_ids, inputs_embeds, lengths, target, self.cfg["vocab"], self.max_seq, self.dtype,
+                                                self.device, seed)
         if inputs_embeds is None:
             input_ids = input_ids.to(self.device)
-            B, S = input_ids.shape
-            emb = None
-        else:
-            B, S = inputs_embeds.shape[:2]
-            emb = inputs_embeds.to(device=self.device, dtype=self.dtype).reshape(B * S, -1).contiguous()
-        if S > self.max_seq:
-            raise ValueError(f"sequence length {S} exceeds max_seq={self.max_seq}")
-        row_iv = None
-        if lengths is not None:
-            lens = torch.as_tensor(lengths, device=self.device).to(torch.int32).reshape(B)
-            if int(lens.min()) < 1 or int(lens.max()) > S:
-                raise ValueError("lengths must lie in [1, S]")
-            i = torch.arange(S, device=self.device, dtype=torch.int32)
-            first = (S - lens)[:, None]
-            lo = first.expand(B, S).contiguous()
-            hi = torch.where(i[None] >= first, (i + 1)[None].expand(B, S), torch.zeros_like(lo)).contiguous()   # pad rows: empty
-            row_iv = (lo, hi)
-        V = self.cfg["vocab"]
-        idx = None
-        if target is not None:
-            tgt = torch.as_tensor(target).reshape(-1).cpu().long()
-            if tgt.numel() != B or int(tgt.min()) < 0 or int(tgt.max()) >= V:
-                raise ValueError(f"target must hold {B} vocabulary indices in [0, {V})")
-            idx = tgt.to(device=self.device, dtype=torch.int32).contiguous()
-        if seed is not None:
-            if target is not None:
-                raise ValueError("pass either target or seed, not both")
-            if tuple(seed.shape) != (B, V):
-                raise ValueError(f"seed must have shape ({B}, {V}), got {tuple(seed.shape)}")
         if not graph:
             return self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed)
         if emb is not None or lengths is not None or seed is not None or return_G:
             raise ValueError("graph=True takes input_ids only (no inputs_embeds / lengths / seed / return_G)")
-        if not hasattr(self, "_graphs") or self._graphs is None:
-            self._graphs = {}
-        key = (B, S, idx is not None, bool(layer_relevance), self.mode)
-        g = self._graphs.get(key)
-        # a graph captured before the arena re-allocated one of its buffers (a later, larger call) points into freed memory: drop it
-        # and capture again against the arena as it is now (ADVICE r3)
-        if g is not None and g[4] != self._arena.gen:
-            del self._graphs[key]
-            g = None
-        if g is None:
-            s_ids = input_ids.clone()
-            s_idx = idx.clone() if idx is not None else None
-            side = torch.cuda.Stream(self.device)
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):                        # warm-up outside the capture: sizes the arena, loads the kernels
-                self._run(s_ids, None, B, S, None, s_idx, layer_relevance, False, None)
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            cg = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(cg):
-                out = self._run(s_ids, None, B, S, None, s_idx, layer_relevance, False, None)
-            g = self._graphs[key] = (cg, s_ids, s_idx, out, self._arena.gen)
-        cg, s_ids, s_idx, out, _ = g
-        s_ids.copy_(input_ids)
-        if s_idx is not None:
-            s_idx.copy_(idx)
-        cg.replay()
-        return out
+        return self._graphs((B, S, idx is not None, bool(layer_relevance), self.mode),
+                            lambda ids, idx_: self._run(ids, None, B, S, None, idx_, layer_relevance, False, None), input_ids, idx)

@@ -20,6 +20,7 @@ import math
 import torch
 
 from . import ops
+from .engine import GraphCache
 
 EXPLICIT = dict(lin=1e-8, add=1e-8, qk=1e-8, mask=1e-8, pv=1e-8, ln=1e-6, act=0.0)
 EFFICIENT = dict(lin=0.0, add=0.0, qk=0.0, mask=0.0, pv=0.0, ln=0.0, act=1e-10)
@@ -61,6 +62,7 @@ class BertLRP:
         if not torch.cuda.is_available():
             raise RuntimeError("BertLRP needs a HIP device: the LRP kernels have no CPU fallback")
         self.cfg, self.dtype, self.device = dict(cfg), dtype, torch.device(device)
+        self._graphs = GraphCache(self.device)                               # (no arena: buffers are allocated per call, never replaced)
         self.set_mode(mode)
         t = lambda x: x.to(device=self.device, dtype=dtype).contiguous()     # noqa: E731
         self.word, self.eln_w, self.eln_b = t(W["word"]), t(W["eln_w"]), t(W["eln_b"])
@@ -74,7 +76,6 @@ class BertLRP:
                      wi=t(L["wi"]), bi=t(L["bi"]), wd=t(L["wd"]), bd=t(L["bd"]), ln1_w=t(L["ln1_w"]), ln1_b=t(L["ln1_b"]),
                      ln2_w=t(L["ln2_w"]), ln2_b=t(L["ln2_b"]))
             self.layers.append(P)
-        self._graphs = {}
 
     @classmethod
     def from_hf(cls, model, dtype=None, device="cuda", mode="efficient"):
@@ -85,7 +86,7 @@ class BertLRP:
         if mode not in ("efficient", "explicit"):
             raise ValueError(f"mode must be 'efficient' or 'explicit', got {mode!r}")
         self.mode, self.eps = mode, dict(EXPLICIT if mode == "explicit" else EFFICIENT)
-        self._graphs = {}
+        self._graphs.clear()
 
     # ------------------------------------------------------------------------------------------------ helpers
     def _scale(self, G, z, eps, out=None):
@@ -212,23 +213,5 @@ class BertLRP:
                 raise ValueError("target must hold one class index in [0, num_labels) per prompt")
         if not graph:
             return self._run(ids, target, layer_relevance)
-        key = (tuple(ids.shape), target is not None, bool(layer_relevance))
-        g = self._graphs.get(key)
-        if g is None:
-            s_ids = ids.clone()
-            s_tgt = target.clone() if target is not None else None
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):                                    # warm-up outside the capture (lazy module loads)
-                self._run(s_ids, s_tgt, layer_relevance)
-            torch.cuda.current_stream().wait_stream(side)
-            cg = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(cg):
-                out = self._run(s_ids, s_tgt, layer_relevance)
-            g = self._graphs[key] = (cg, s_ids, s_tgt, out)
-        cg, s_ids, s_tgt, out = g
-        s_ids.copy_(ids)
-        if s_tgt is not None:
-            s_tgt.copy_(target)
-        cg.replay()
-        return out
+        return self._graphs((tuple(ids.shape), target is not None, bool(layer_relevance)), lambda ids_, tgt: self._run(ids_, tgt, layer_relevance),
+                            ids, target)

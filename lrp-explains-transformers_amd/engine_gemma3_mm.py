@@ -21,6 +21,7 @@ constant [tokens, patches] matrix (power-of-two pooling windows: 1 / k^2 exact i
 import torch
 
 from . import ops
+from .engine import explain_inputs, explanation
 from .engine_gemma3 import Gemma3LRP
 
 
@@ -263,6 +264,7 @@ class Gemma3MMLRP:
             raise NotImplementedError("Gemma3MMLRP.explain: padded image + text batches are not supported (every prompt must fill the batch's sequence length)")
         if attention_mask is not None and not bool(torch.as_tensor(attention_mask).bool().all()):
             raise NotImplementedError("Gemma3MMLRP.explain: padded image + text batches are not supported (attention_mask has masked positions)")
+        _, _, _, _, idx = explain_inputs(ids, None, None, target, tx.cfg["vocab"], tx.max_seq, tx.dtype, dev)
         # the prompt's bookkeeping (image positions, per-row key intervals) is HOST work on the host copy of the ids: with ids handed over on the CPU
         # (the usual tokenizer output) explain() contains no device -> host round trip ahead of the launches -- three of them (nonzero, any, the
         # interval builder's .cpu()) used to drain the queue at the top of every call, and the tower's many short kernels then ran behind the host
@@ -281,16 +283,12 @@ class Gemma3MMLRP:
         emb.index_copy_(0, rows, fv["feat"].to(emb.dtype))                       # HF: inputs_embeds.masked_scatter(image mask, image features)
         iv = None if iv_h is None else {k: (lo.to(dev), hi.to(dev)) for k, (lo, hi) in iv_h.items()}
         fw = tx.forward(emb, B, S, iv)
-        if target is None:
+        if idx is None:
             idx, _ = ops.argmax_rows(fw["logits"])
-        else:
-            idx = torch.as_tensor(target).reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
         G = tx.backward(fw, idx, B, S)
-        R_tok = ops.readout(emb, G)
-        R_tok.index_fill_(0, rows, 0.0)                                           # the word embeddings at image positions were replaced: no relevance
+        out = explanation(emb, G, idx, fw["logits"], B, S)
+        out["R_tok"].view(-1).index_fill_(0, rows, 0.0)                         # the word embeddings at image positions were replaced: no relevance
         Gpix, Gpatch = vi.backward(fv, G.index_select(0, rows))
-        R_pix = ops.mul(fv["pv"].contiguous(), Gpix.contiguous()).float()
-        R_patch = ops.readout(fv["patches"], Gpatch).view(n_img, vi.grid, vi.grid)     # sum over a patch of pixel (*) gradient, one row per patch
-        logits = fw["logits"].clone()
-        return dict(idx=idx, logit=logits.gather(1, idx.long()[:, None])[:, 0], R_tok=R_tok.view(B, S), R_pix=R_pix, R_patch=R_patch,
-                    logits=logits)
+        out["R_pix"] = ops.mul(fv["pv"].contiguous(), Gpix.contiguous()).float()
+        out["R_patch"] = ops.readout(fv["patches"], Gpatch).view(n_img, vi.grid, vi.grid)     # sum over a patch of pixel (*) gradient, one row per patch
+        return out

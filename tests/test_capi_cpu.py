@@ -276,9 +276,9 @@ def test_explicit_bert_registers_a_mask_function():
         xb.register_interfaces()           # restore the real attention function under the name
 
 
-def test_host_dispatch_rules_round3():
+def test_host_dispatch_rules():
     """host-side logic added in round 3, none of which launches a kernel: the row-pitch padding rule, the split-K dispatch predicate,
-    padded arena buffers, the gate/up interleave map, and the Gemma-3 config reader's refusals"""
+    padded buffers of the drivers' workspace arena (engine.Arena), the gate/up interleave map, and the Gemma-3 config reader's refusals"""
     import lxt_amd.engine as E
     import lxt_amd.ops as O
     # pitch: 128 bytes of padding exactly for the long-K operands whose pitch is a multiple of 4 KiB
@@ -291,7 +291,7 @@ def test_host_dispatch_rules_round3():
     # 1 ... 1.5 rounds of the chip with a long K loop (Gemma-3-4B down projection): two K splits; not with a short one, not at 2 rounds
     assert O.splitk_ok(8192, 2560, 10240) and not O.splitk_ok(8192, 2560, 4096) and not O.splitk_ok(8192, 4096, 14336)
     # arena: a padded 2-D buffer is a [rows, cols] view with the padded pitch; the same tag is reused, a larger request grows it
-    ar = E.LlamaLRP._Arena(torch.device("cpu"))
+    ar = E.Arena(torch.device("cpu"), torch.bfloat16)
     a = ar.get("m", (8, 14336), torch.bfloat16, pad=64)
     assert a.shape == (8, 14336) and a.stride(0) == 14400 and ar.get("m", (8, 14336), torch.bfloat16, pad=64).data_ptr() == a.data_ptr()
     z = ar.get("m", (4, 14336), torch.bfloat16, zero=True, pad=64)

@@ -9,7 +9,7 @@ BASELINE config 4 "image+text"):
 import pytest
 import torch
 
-from tests.golden.hf_models import build_gemma3_mm, wsum
+from tests.golden.hf_models import build_gemma3_mm, gemma3_mm_inputs, wsum
 from tests.util import nmax, load, t
 
 pytestmark = pytest.mark.gpu
@@ -88,3 +88,21 @@ def test_gemma3_mm_engine_full_dims_vs_reference_fixture(mm, impl):
         print(f"[gemma3 4B image+text dims, bf16 vs fp32 fused] token nmax {nmax(rb['R_tok'][0], r32['R_tok'][0]):.2e} cos {cos_t:.5f} | patch nmax "
               f"{nmax(rb['R_patch'][0], r32['R_patch'][0]):.2e} cos {cos_p:.5f}")
         assert torch.isfinite(rb["R_pix"]).all() and cos_t > 0.99 and cos_p > 0.98
+
+
+def test_gemma3_mm_engine_refuses_bad_input_before_any_launch(mm, monkeypatch):
+    """an out-of-range target (it would index the logits inside the kernels) and a prompt longer than max_seq are refused with ValueError
+    before the tower or the decoder runs, as LlamaLRP and Gemma3LRP refuse them"""
+    eng = mm.Gemma3MMLRP.from_hf(build_gemma3_mm(attn="eager"), dtype=torch.float32, max_seq=256)
+    ids, tt, pv = gemma3_mm_inputs()
+
+    def no_launch(*a, **kw):
+        raise AssertionError("explain() ran the model before checking its input")
+
+    monkeypatch.setattr(eng.vision, "forward", no_launch)
+    monkeypatch.setattr(eng.text, "forward", no_launch)
+    with pytest.raises(ValueError, match="target"):
+        eng.explain(ids, pv, token_type_ids=tt, target=[eng.text.cfg["vocab"]])
+    monkeypatch.setattr(eng.text, "max_seq", ids.shape[1] - 1)
+    with pytest.raises(ValueError, match="max_seq"):
+        eng.explain(ids, pv, token_type_ids=tt)
