@@ -447,6 +447,7 @@ int lrp_add2_rule_bwd(const void* a, const void* b, const void* R, void* Ra, voi
 /* ---------------------------------------------------------------------------------------
  * K9 / harness.  ref: docs/source/quickstart.rst:120-141, examples/paper/llama.py:45-46
  *   lrp_readout      : R_tok[row] = sum_h emb[row,h]*G[row,h]   (fp32 out)
+ *   lrp_colsum_dot   : out[b,j] = sum_t x[b S + t,j]*g[b S + t,j]   (fp32 out; the column counterpart, below)
  *   lrp_head_seed    : last-token head, one launch per prompt batch:
  *        Gxn[b,:] = zfac * W_lm[idx[b],:]  with zfac = z/(z+eps_lin), z = logits[b,idx[b]]
  *        then the final-norm identity rule: Gh_last[b,:] = Gxn (*) w' * rstd[b]
@@ -455,6 +456,18 @@ int lrp_add2_rule_bwd(const void* a, const void* b, const void* R, void* Ra, voi
  *   lrp_cast         : dtype conversion fp32 <-> bf16
  * --------------------------------------------------------------------------------------- */
 int lrp_readout(const void* emb, const void* G, float* R_tok, int M, int H, int dtype, void* stream);
+/* lrp_colsum_dot (csrc/latent.hip): out[b, j] = sum_{t < S} x[b S + t, j] g[b S + t, j] for b < B, j < N, fp32 [B, N] contiguous -- the
+ * token-summed relevance of every hidden unit of a latent feature attribution (x = h, g = G_h: a residual-stream dimension; x = m, g = G_m:
+ * an MLP neuron).  ref: docs/source/latent-feature-attribution-efficient.rst (`(h * h.grad)` summed over the tokens).
+ *   x, g: [M = B S, N] row-major with row pitches ldx / ldg (elements), both LRP_F32 or both LRP_BF16; 16-byte aligned bases and pitches
+ *   that are multiples of 16 bytes (LRP_EALIGN), any N (the row's tail past the last 16-byte vector is read element-wise).
+ *   B S != M, a size < 1, B > 65535, ld < N -> LRP_ESHAPE; a NULL operand / output, or a NULL ws where one is needed -> LRP_EINVAL.
+ *   Bitwise deterministic and batch invariant: fp32 partials of fixed 64-row chunks of ONE prompt (rows in order inside a wave, four waves
+ *   added in wave order) go to the caller-allocated workspace ws (lrp_colsum_dot_ws(B, S, N) BYTES; 0 when S <= 64: the partials are the
+ *   result), a second launch adds a prompt's chunks in chunk order.  lrp_colsum_dot_ws returns LRP_ESHAPE for a size < 1. */
+int64_t lrp_colsum_dot_ws(int B, int S, int N);
+int lrp_colsum_dot(const void* x, const void* g, float* out, void* ws, int M, int N, int B, int S, int64_t ldx, int64_t ldg, int dtype,
+                   void* stream);
 int lrp_head_seed(const void* W_lm, const float* logits, const int* idx, const void* w_norm,
                   const float* rstd_last, void* Gh_last, int B, int V, int H, int64_t ld_logits,
                   float w_offset, float eps_lin, int dtype, void* stream);

@@ -194,7 +194,8 @@ def fused_layer_fwd(h, rstd1, qkv, qkr, W, cos, sin, B, S, meta, alloc, row_iv=N
                     chain=True):
     """attention, h1 = h + o Wo^T with its sums of squares in the epilogue, the gate/up GEMM on rstd2 (.) h1 with the coefficient stash of the
     gated rule (eps = (eps_g, eps_lin)); chain: the down projection leaves h_out and ITS rstd the same way, else dn = m Wd^T.  explicit: the
-    Linears' own outputs a / dn are kept for their stabilisers.  -> dict(o, lse, h1, a, rstd2, gu, dn[, h_out, rstd_out])"""
+    Linears' own outputs a / dn are kept for their stabilisers.  -> dict(o, lse, h1, a, rstd2, gu, m, dn[, h_out, rstd_out]) (m: wherever the
+    allocator put it -- a scratch buffer unless the caller keeps it per layer)"""
     nq, nk, d, rms_eps, act, scale = meta
     M, H, I, dt = B * S, h.shape[1], W["wd"].shape[1], h.dtype
     new = lambda tag, cols, pitch=None: alloc(tag, M, cols, (pitch or cols) - cols, dt)      # noqa: E731
@@ -208,6 +209,7 @@ def fused_layer_fwd(h, rstd1, qkv, qkr, W, cos, sin, B, S, meta, alloc, row_iv=N
     ops.gemm_res_ssq(st["o"], W["wo"], h, st["h1"], ssq, raw=st["a"])
     st["rstd2"] = ops.rms_rstd(ssq, M, H, rms_eps, vec("rstd2"))
     st["gu"], m = ops.gemm_gated_fwd_coef(st["h1"], W["wgu"], new("gu", 2 * I), new("m", I, pt["m"]), *eps, act, rs=st["rstd2"])
+    st["m"] = m
     if chain:
         st["h_out"], st["dn"] = new("h_out", H), new("dn", H) if explicit else None
         ops.gemm_res_ssq(m, W["wd"], st["h1"], st["h_out"], ssq, raw=st["dn"])
@@ -359,6 +361,30 @@ def explain_inputs(input_ids, inputs_embeds, lengths, target, vocab, max_seq, dt
     return B, S, emb, row_iv, idx
 
 
+LATENT = ("trace", "resid", "mlp")
+
+
+def latent_request(latent, H, I, dtype):
+    """explain(latent=...) -> frozenset of the requested read-outs of a latent feature attribution ("trace": per-token relevance at every
+    residual boundary, "resid": token-summed per residual dimension, "mlp": token-summed per MLP neuron); None -> the empty set.  Raises
+    ValueError before a kernel of the model runs: an unknown name, or a request the column read-out cannot serve (lrp_colsum_dot reads rows
+    of a multiple of 16 bytes: H for "resid", I for "mlp")"""
+    if latent is None:
+        return frozenset()
+    try:
+        names = (latent,) if isinstance(latent, str) else tuple(latent)
+    except TypeError:
+        raise ValueError(f"latent must be an iterable of names from {LATENT}, got {latent!r}") from None
+    bad = [n for n in names if n not in LATENT]
+    if bad:
+        raise ValueError(f"latent: unknown read-out(s) {bad}; choose from {LATENT}")
+    req = frozenset(names)
+    for name, n in (("resid", H), ("mlp", I)):
+        if name in req and (n * dtype.itemsize) % 16:
+            raise ValueError(f"latent={name!r} needs rows of a multiple of 16 bytes ({n} elements of {dtype} are not)")
+    return req
+
+
 class GraphCache:
     """hipGraph capture and replay of whole explanations, one graph per key.  The first call of a key warms up on a side stream (sizes the
     workspace, loads the kernels), then captures run(*inputs) on static copies of the inputs; every call copies its inputs into those and
@@ -504,10 +530,11 @@ class LlamaLRP:
         FORWARD half is the same computation under both placements (the explicit one additionally keeps each Linear's own output: round 6)"""
         return bool(self.folded and ops.NORM_FUSION and (self.mode == "efficient" or fwd_only) and self._fused(M).norm)
 
-    def _alloc(self, li):
-        """arena allocator of the fused-layer functions for layer li (the gradient a layer hands down alternates between two buffers)"""
+    def _alloc(self, li, keep=()):
+        """arena allocator of the fused-layer functions for layer li (the gradient a layer hands down alternates between two buffers); keep:
+        scratch tags that get a buffer of their own per layer instead (latent "mlp": m)"""
         def alloc(tag, rows, cols, pad, dtype):
-            key = tag if tag in FUSED_SCRATCH else ("Gs", li & 1) if tag == "Gh" else (tag, li)
+            key = tag if tag in FUSED_SCRATCH and tag not in keep else ("Gs", li & 1) if tag == "Gh" else (tag, li)
             return self._arena.get(key, (rows, cols), dtype, pad=pad)
         return alloc
 
@@ -548,7 +575,9 @@ class LlamaLRP:
         self._arena = Arena(self.device, self.dtype)
         self._graphs.clear()
 
-    def forward(self, emb, B, S, row_iv=None):
+    def forward(self, emb, B, S, row_iv=None, keep_m=False):
+        """keep_m: every dense layer's m (the down projection's input) in a buffer of its own, ("m", li), for the latent "mlp" read-out;
+        the arithmetic is the same, only where m lands changes"""
         c = self.cfg
         H, I, d, nq, nk = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"]
         M = B * S
@@ -583,7 +612,8 @@ class LlamaLRP:
                 qkr = ops.rope_fwd(qkv, ar.new(("qkr", li), M, nqk), self.cos, self.sin, S, nq + nk, d)
             if nf and not top:
                 # (not chained in the last layer: the tail below wants h1 and dn of the explained rows separately)
-                st.update(fused_layer_fwd(st["h"], st["rstd1"], qkv, qkr, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv, explicit,
+                st.update(fused_layer_fwd(st["h"], st["rstd1"], qkv, qkr, Lw, self.cos, self.sin, B, S, self.meta,
+                                          self._alloc(li, ("m",) if keep_m else ()), row_iv, explicit,
                                           (self.eps_g, self.eps["lin"]), chain=li + 1 < nL), qkv=qkv, qkr=qkr, coef=True)
                 stash.append(st)
                 ready = (st["h_out"], st["rstd_out"]) if li + 1 < nL else None
@@ -601,7 +631,7 @@ class LlamaLRP:
                 x2_l, rstd2_l = ops.add_rmsnorm_fwd(h_l, a_l, Lw["ln2"], c["rms_eps"], hsum_out=h1_l)
                 gu_l, m_l = ops.gemm_gated_fwd(x2_l, Lw["wgu"], ar.new("gu_l", B, 2 * I), ar.new("m_l", B, I), self.act)
                 dn_l = self._lin_fwd(m_l, Lw["wd"], ar.new("dn_l", B, H))
-                st.update(top=True, qkv=qkv, qkr=qkr, lse=lse, o_l=o_l, a_l=a_l, h1_l=h1_l, rstd2_l=rstd2_l, gu_l=gu_l, dn_l=dn_l)
+                st.update(top=True, qkv=qkv, qkr=qkr, lse=lse, o_l=o_l, a_l=a_l, h1_l=h1_l, rstd2_l=rstd2_l, gu_l=gu_l, m_l=m_l, dn_l=dn_l)
                 stash.append(st)
                 h_prev, branch = h1_l, dn_l
                 break
@@ -610,12 +640,13 @@ class LlamaLRP:
             h1 = ar.new(("h1", li), M, H)
             x2, st["rstd2"] = ar.new("x2", M, H), ar.f32(("rstd2", li), M)
             ops.add_rmsnorm_fwd(st["h"], a, Lw["ln2"], c["rms_eps"], hsum_out=h1, y=x2, rstd=st["rstd2"])
+            gu, m = ar.new(("gu", li), M, 2 * I), ar.wide(("m", li) if keep_m else "m", M, I)
             if coef:      # the gated rules inside the two GEMMs around them: the backward's coefficients are stashed in gu's place (g, u never stored)
-                gu, m = ops.gemm_gated_fwd_coef(x2, Lw["wgu"], ar.new(("gu", li), M, 2 * I), ar.wide("m", M, I), self.eps_g, self.eps["lin"], self.act)
+                gu, m = ops.gemm_gated_fwd_coef(x2, Lw["wgu"], gu, m, self.eps_g, self.eps["lin"], self.act)
             else:
-                gu, m = ops.gemm_gated_fwd(x2, Lw["wgu"], ar.new(("gu", li), M, 2 * I), ar.wide("m", M, I), self.act)
+                gu, m = ops.gemm_gated_fwd(x2, Lw["wgu"], gu, m, self.act)
             dn = self._lin_fwd(m, Lw["wd"], ar.new(("dn", li), M, H))
-            st.update(qkv=qkv, qkr=qkr, o=o, lse=lse, a=a, h1=h1, gu=gu, coef=coef, dn=dn)
+            st.update(qkv=qkv, qkr=qkr, o=o, lse=lse, a=a, h1=h1, gu=gu, coef=coef, m=m, dn=dn)
             stash.append(st)
             h_prev, branch = h1, dn
         # last token only: final residual add + norm + LM head
@@ -623,7 +654,8 @@ class LlamaLRP:
         return dict(stash=stash, last=last, row_iv=row_iv, **head_fwd(ar, h_prev, branch, top, last, self.norm, self.lm_head, c["rms_eps"]))
 
     # ---------------------------------------------------------------------------------------------
-    def backward(self, fw, emb, idx, B, S, layer_relevance=False, seed=None):
+    def backward(self, fw, emb, idx, B, S, layer_relevance=False, seed=None, latent=frozenset()):
+        """-> (G at the embedding, layer_R rows or None, dict of the token-summed latent read-outs: R_resid [L+1, B, H] / R_mlp [L, B, I])"""
         c, E = self.cfg, self.eps
         H, I, d, nq, nk = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"]
         M, rep = B * S, nq // nk
@@ -648,6 +680,12 @@ class LlamaLRP:
         rel_last = ar.f32("rel_last", B) if layer_relevance else None
         ops.rmsnorm_bwd_add2(Gh_last, None, None, None, fw["hL_last"], fw["dn_last"], Gs_last, A_last, rel_last,
                              0.0, E["add"], E["lin"])
+        nL, lat = len(self.layers), {}
+        if "resid" in latent:          # index L: the head's explained rows, the gradient rel_last is formed from (S = 1)
+            lat["R_resid"] = torch.empty(nL + 1, B, H, device=dev, dtype=torch.float32)
+            ops.colsum_dot(fw["hL_last"], Gh_last, B, 1, out=lat["R_resid"][nL])
+        if "mlp" in latent:
+            lat["R_mlp"] = torch.empty(nL, B, I, device=dev, dtype=torch.float32)
         last, row_iv = fw["last"], fw["row_iv"]
         top_sparse = bool(fw["stash"]) and fw["stash"][-1].get("top", False)
         if not top_sparse:
@@ -666,9 +704,20 @@ class LlamaLRP:
             Lw, st = self.layers[li], fw["stash"][li]
             qkv, qkr = st["qkv"], st["qkr"]
             q_begin = 0
+            if "mlp" in latent:
+                # G_m = Adn Wd: the gradient at the down projection's input (Adn: the eps-scaled branch gradient; = Gs in the efficient placement),
+                # one dgrad the backward otherwise folds into Agu.  The sparse top layer has one row per prompt: the other rows' neurons are 0
+                if st.get("top", False):
+                    Gm = self._lin_bwd(A_last, Lw["wd"], ar.new("Gm_l", B, I))
+                    ops.colsum_dot(st["m_l"], Gm, B, 1, out=lat["R_mlp"][li])
+                else:
+                    Gm = self._lin_bwd(Adn, Lw["wd"], ar.new("Gm", M, I))
+                    ops.colsum_dot(st["m"], Gm, B, S, out=lat["R_mlp"][li])
             if full and not st.get("top", False):          # (Adn = Gs: eps = 0)
                 Gs = Adn = fused_layer_bwd(Gs, st, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv)
                 layer_R = layer_R + [ops.readout(st["h"], Gs, out=ar.f32(("rel", li), M))] if layer_relevance else None
+                if "resid" in latent:
+                    ops.colsum_dot(st["h"], Gs, B, S, out=lat["R_resid"][li])
                 continue
             if st.get("top", False):
                 # ---- one row per prompt through MLP, norm/add2 and o-proj; scatter into the dense attention inputs
@@ -750,6 +799,8 @@ class LlamaLRP:
                 Adn = Gs
                 if layer_relevance:
                     layer_R.append(ops.readout(st["h"], Gs, out=rel))
+                if "resid" in latent:
+                    ops.colsum_dot(st["h"], Gs, B, S, out=lat["R_resid"][li])
                 continue
             Gx = self._lin_bwd(Aqkv, Lw["wqkv"], ar.new("Gx", M, H))
             # ---- input norm + the residual add below (or the embedding)
@@ -768,27 +819,39 @@ class LlamaLRP:
                                      rel, 0.0, 0.0, 0.0)
             if layer_relevance:
                 layer_R.append(rel)
-        return Gs, layer_R
+            if "resid" in latent:
+                ops.colsum_dot(st["h"], Gs, B, S, out=lat["R_resid"][li])
+        return Gs, layer_R, lat
 
     # ---------------------------------------------------------------------------------------------
-    def _run(self, input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed):
+    def _run(self, input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, latent=frozenset()):
         """forward + backward + read-out on the current stream: library launches only, no host synchronisation (capturable)"""
         if emb is None:
             emb = self.embed.index_select(0, input_ids.reshape(-1))
-        fw = self.forward(emb, B, S, row_iv)
+        fw = self.forward(emb, B, S, row_iv, keep_m="mlp" in latent)
         if idx is None:
             # (a dense seed explains no single logit; idx / logit then report the arg-max for convenience)
             idx, _ = ops.argmax_rows(fw["logits"])
-        G, layer_R = self.backward(fw, emb, idx, B, S, layer_relevance, seed=seed)
+        G, layer_R, lat = self.backward(fw, emb, idx, B, S, layer_relevance or "trace" in latent, seed=seed, latent=latent)
         out = explanation(emb, G, idx, fw["logits"], B, S, return_G)
         if layer_relevance:
             rows = [layer_R[0]] + [r.view(B, S).sum(1) for r in layer_R[1:]]
             out["layer_R"] = torch.stack(rows[::-1], 0)          # [L+1, B], index 0 = embedding
+        if "trace" in latent:
+            # the per-token rows layer_R sums: index l = the input of layer l (l = 0: R_tok itself), index L = the head's explained rows
+            nL = len(layer_R) - 1
+            trace = torch.zeros(nL + 1, B, S, device=self.device, dtype=torch.float32)
+            trace[0] = out["R_tok"]
+            for li in range(1, nL):
+                trace[li] = layer_R[nL - li].view(B, S)
+            trace[nL, :, S - 1] = layer_R[0]
+            out["R_trace"] = trace
+        out.update(lat)
         return out
 
     @torch.no_grad()
     def explain(self, input_ids=None, inputs_embeds=None, target=None, layer_relevance=False, return_G=False, lengths=None,
-                seed=None, graph=False):
+                seed=None, graph=False, latent=None):
         """input_ids [B,S] (or inputs_embeds [B,S,H]); target: None (arg-max of the last position) or
         int tensor [B].  Returns dict(idx [B], logit [B], R_tok [B,S] fp32, and optionally
         layer_R [L+1, B] (sum_h h (*) G_h at every residual-stream boundary) and G_emb [B,S,H]).
@@ -800,14 +863,20 @@ class LlamaLRP:
         a gradient over the last-position logits in efficient mode (contrastive explanations), a relevance over them
         in explicit mode.
         graph=True (input_ids only, no lengths / seed / return_G): the ~1500 launches of one explanation of this (B, S) are captured
-        once into a hipGraph and replayed; the returned tensors are the graph's static outputs (copy them before the next call)."""
+        once into a hipGraph and replayed; the returned tensors are the graph's static outputs (copy them before the next call).
+        latent (optional): names from {"trace", "resid", "mlp"}, the latent feature attribution read-outs, each one
+        more output, fp32: R_trace [L+1, B, S] = sum_h h (*) G_h per token at every residual boundary (index 0 = R_tok, index l = the output
+        of layer l - 1, index L = the head's row: only each prompt's last column is non-zero; R_trace[l].sum(-1) is layer_R[l]);
+        R_resid [L+1, B, H] = sum_t h (*) G_h per residual dimension at the same boundaries; R_mlp [L, B, I] = sum_t m (*) G_m per MLP neuron
+        (m: the down projection's input, HF column order).  R_tok, logit and layer_R do not change with it."""
+        lat = latent_request(latent, self.cfg["hidden"], self.cfg["inter"], self.dtype)
         B, S, emb, row_iv, idx = explain_inputs(input_ids, inputs_embeds, lengths, target, self.cfg["vocab"], self.max_seq, self.dtype,
                                                 self.device, seed)
         if inputs_embeds is None:
             input_ids = input_ids.to(self.device)
         if not graph:
-            return self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed)
+            return self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, lat)
         if emb is not None or lengths is not None or seed is not None or return_G:
             raise ValueError("graph=True takes input_ids only (no inputs_embeds / lengths / seed / return_G)")
-        return self._graphs((B, S, idx is not None, bool(layer_relevance), self.mode),
-                            lambda ids, idx_: self._run(ids, None, B, S, None, idx_, layer_relevance, False, None), input_ids, idx)
+        return self._graphs((B, S, idx is not None, bool(layer_relevance), self.mode, tuple(sorted(lat))),
+                            lambda ids, idx_: self._run(ids, None, B, S, None, idx_, layer_relevance, False, None, lat), input_ids, idx)

@@ -806,6 +806,31 @@ def readout(emb, G, out=None):
     return out
 
 
+def colsum_dot(x, g, B, S, out=None, ws=None):
+    """out[b, j] = sum_t x[b S + t, j] g[b S + t, j]  ([B, N] fp32) for x, g [B S, N] with unit column stride (any row pitch): the token-summed
+    relevance of every hidden unit (x = h, g = G_h; x = m, g = G_m).  Fixed-order fp32 sums, a prompt's result depends on its rows only.
+    ws: the caller's workspace (uint8, at least lrp_colsum_dot_ws bytes); None: the per-stream scratch buffer"""
+    M, N = x.shape
+    if tuple(g.shape) != (M, N) or x.stride(1) != 1 or g.stride(1) != 1:
+        raise ValueError(f"colsum_dot: x {tuple(x.shape)} and g {tuple(g.shape)} must be the same [B S, N] shape with contiguous rows")
+    px, pg = p(x), p(g)                 # (device tensors only: raises before anything is allocated)
+    out = torch.empty(B, N, device=x.device, dtype=torch.float32) if out is None else out
+    same(x, g)
+    f32(out)
+    if tuple(out.shape) != (B, N) or not out.is_contiguous():
+        raise ValueError(f"colsum_dot: out must be a contiguous [{B}, {N}] tensor")
+    need = lib.lrp_colsum_dot_ws(B, S, N)
+    if need < 0:
+        raise ValueError(f"colsum_dot: bad sizes B={B}, S={S}, N={N}")
+    if need and ws is None:
+        ws = workspace(need, x)
+    elif need and ws.numel() * ws.element_size() < need:
+        raise ValueError(f"colsum_dot: workspace of {ws.numel() * ws.element_size()} bytes, {need} needed")
+    check(lib.lrp_colsum_dot(px, pg, p(out), p(ws) if need else None, M, N, B, S, x.stride(0), g.stride(0), dt(x), stream()),
+          "lrp_colsum_dot")
+    return out
+
+
 def argmax_rows(logits):
     B, V = logits.shape
     idx = torch.empty(B, device=logits.device, dtype=torch.int32)

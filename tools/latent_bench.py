@@ -1,0 +1,101 @@
+#!/usr/bin/env python3
+"""Latent feature attribution read-outs on the MI355X:
+  (1) lrp_colsum_dot at the Llama-3-8B shapes, B S = 8192 rows (B = 4, S = 2048), N = 4096 (residual dims) and N = 14336 (MLP neurons), bf16:
+      time per call from device events (median over --reps timed calls after warm-up) and the bytes the algorithm must read, 2 B S N 2,
+      over it -- and that rate over the 8 TB/s HBM peak;
+  (2) the per-step overhead of each LlamaLRP.explain(latent=...) option against a plain explain(), bf16, at the Llama-3-8B layer shape
+      (H 4096, I 14336, 32 / 8 heads of 128) with --layers layers, B = 4, S = 2048; the requests alternate inside each round.
+usage: python tools/latent_bench.py [--out FILE] [--layers 2] [--reps 20] [--rounds 5]"""
+import argparse
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
+
+
+def timed(fn, reps):
+    """median milliseconds of fn() over reps calls, each between two device events"""
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return statistics.median(ts), min(ts)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--layers", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("latent_bench needs a HIP device")
+    from lxt_amd import ops
+    import lxt_amd.engine as E
+    lines = [f"device: {torch.cuda.get_device_name(0)}"]
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    # ---- (1) the kernel
+    B, S = 4, 2048
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for N, pad in ((4096, 0), (14336, 64)):
+        x = torch.randn(B * S, N + pad, generator=g, device="cuda").bfloat16()[:, :N]
+        y = torch.randn(B * S, N + pad, generator=g, device="cuda").bfloat16()[:, :N]
+        out = torch.empty(B, N, device="cuda")
+        for _ in range(5):
+            ops.colsum_dot(x, y, B, S, out=out)
+        med, best = timed(lambda: ops.colsum_dot(x, y, B, S, out=out), 50)
+        nbytes = 2 * B * S * N * 2
+        say(f"colsum_dot bf16 B={B} S={S} N={N} (row pitch {N + pad}): {med * 1e3:7.1f} us median, {best * 1e3:7.1f} us best over 50 calls; "
+            f"{nbytes / 1e6:.0f} MB read -> {nbytes / med / 1e9:.2f} TB/s median = {nbytes / med / 1e9 / 8.0:.2f} of 8 TB/s "
+            f"(best {nbytes / best / 1e9:.2f} TB/s); workspace {ops.lib.lrp_colsum_dot_ws(B, S, N) / 1e6:.1f} MB of fp32 partials")
+        del x, y
+
+    # ---- (2) the engine
+    H, I, d, L = 4096, 14336, 128, a.layers
+    cfg = dict(hidden=H, inter=I, n_layers=L, n_heads=32, n_kv=8, head_dim=d, vocab=4096, rope_theta=5e5, rms_eps=1e-5)
+    rn = lambda *s: (torch.randn(*s, generator=g, device="cuda") * 0.02).bfloat16()      # noqa: E731
+    ones = lambda: torch.ones(H, device="cuda").bfloat16()                                # noqa: E731
+    W = dict(embed=rn(4096, H), norm=ones(), lm_head=rn(4096, H),
+             layers=[dict(ln1=ones(), ln2=ones(), wq=rn(32 * d, H), wk=rn(8 * d, H), wv=rn(8 * d, H), wo=rn(H, 32 * d), wg=rn(I, H), wu=rn(I, H),
+                          wd=rn(H, I)) for _ in range(L)])
+    eng = E.LlamaLRP(cfg, W, dtype=torch.bfloat16, mode="efficient", max_seq=S)
+    del W
+    ids = torch.randint(0, 4096, (B, S), generator=torch.Generator().manual_seed(1)).cuda()
+    reqs = dict(plain=None, trace=("trace",), resid=("resid",), mlp=("mlp",), all=("trace", "resid", "mlp"))
+    for lat in reqs.values():                                   # warm-up: every shape, every arena buffer
+        for _ in range(2):
+            eng.explain(ids, latent=lat)
+    torch.cuda.synchronize()
+    arena0 = eng._arena.nbytes()
+    ts = {k: [] for k in reqs}
+    for _ in range(a.rounds):
+        for k, lat in reqs.items():
+            ts[k].append(timed(lambda: eng.explain(ids, latent=lat), max(1, a.reps // a.rounds))[0])
+    base = statistics.median(ts["plain"])
+    say(f"engine bf16, Llama-3-8B layer shape, {L} layers, B={B} S={S} (M = {B * S} rows), median of {a.rounds} rounds x "
+        f"{max(1, a.reps // a.rounds)} steps, requests alternating:")
+    for k in reqs:
+        m = statistics.median(ts[k])
+        say(f"  latent={k:6s}: {m:8.2f} ms per step   +{m - base:6.2f} ms  ({100 * (m - base) / base:+5.1f} %)  "
+            f"= {(m - base) / L * 1e3:7.1f} us per layer   [spread {min(ts[k]):.2f} .. {max(ts[k]):.2f}]")
+    say(f"  arena after every request: {arena0 / 2**30:.2f} GiB (kept m: {L} x {B * S} x {I} bf16 = {L * B * S * I * 2 / 2**30:.2f} GiB of it)")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
