@@ -16,7 +16,13 @@ torch.distributed.run with one rank per GPU.  A "step" = every rank explains `--
                rocprofv3 summary) and are listed under roofline.with_fused_epilogue_launches.
   cpu_baseline the oracle (CPU port of the same op sequence, oracle/llama.py) timed on this box's
                host cores on a bounded sample (one decoder layer + head, fp32, extrapolated x32);
-               rank 0, N=1 only.
+               rank 0, N=1, --full only.
+
+A plain run does what `value` needs and no more: set-up, warm-up, the timed steps, --dump-outputs, the line (value, ms_per_step and the
+roofline of the GEMM launches inside the timed region).  `--full` adds, after and outside the timed region, everything that takes runs of
+its own: cpu_baseline, the small-M Linear tables (roofline_linear_eps_smallm), seq = 4096 (config5_seq4096), the explicit placement and
+4 / 1 prompts per step (mode_explicit, batch4, batch1), the Gemma-3-4B probes (config4_*) and the HF model under monkey_patch
+(dropin_monkey_patch); the timed region and the headline keys are the same in both.
 """
 import argparse
 import json
@@ -525,9 +531,19 @@ def self_launch(n):
         sys.exit(rc)
 
 
-def main():
+EXTRAS = ("cpu_baseline", "config5", "config4", "config4_image", "dropin", "extra_modes", "smallm")      # each has a --no-<name> option
+
+
+def parse_args(argv=None):
+    """the command line -> args.  Without --full every part of EXTRAS is switched off (args.no_<name> = True): a plain run sets up, warms
+    up, times the steps and prints the line.  With --full each runs unless its own --no-<name> option drops it."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else the benchmark knows, each in runs of its own and under a key of its "
+                         "own in the result line: the small-M Linear tables, seq=4096, the explicit placement and 4 / 1 prompts per step, the "
+                         "Gemma-3-4B probes, the HF model under monkey_patch, the CPU baseline (the --no-... options below drop one of them "
+                         "each).  Off by default: a plain run does only what the headline value needs")
     ap.add_argument("--single-rank-collectives", action="store_true",
                     help="dev, 1 GPU: run the N > 1 code path (RCCL broadcast / self-checks / all-gather / barriers) with a one-rank process group")
     ap.add_argument("--per-step", action="store_true", help="dev: print per-step wall times to stderr (adds a full sync per step)")
@@ -560,9 +576,17 @@ def main():
                          "one JSON line from rank 0 -- value is null; used by tests/test_dist_cpu.py for the N>1 launch contract")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step's explain() returned "
                     "(R_tok, idx, logit, logits; all ranks' prompts) as DIR/<name>.npy in float32 / float64, at most 64 MB in all")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        for name in EXTRAS:
+            setattr(args, "no_" + name, True)
+    return args
+
+
+def main():
+    args = parse_args()
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ and not args.single_rank_collectives:
         return self_launch(args.gpus)
     if args.dry_run:
