@@ -318,6 +318,18 @@ int lrp_gemm_nt_rs(const void* x, const void* W, const float* rs, void* out, int
 int lrp_gemm_nt_rs_rope_ok(int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols, int head_dim, int dtype);
 int lrp_gemm_nt_rs_rope(const void* x, const void* W, const float* rs, const float* cos, const float* sin, void* out, int M, int N, int K,
                         int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols, int head_dim, int dtype, void* stream);
+/* Qwen2's q / k / v bias in the fused QKV forward (same arguments as the two entry points above plus bias: bf16 [N], 16-byte aligned):
+ *   lrp_gemm_nt_rs_bias      : out[m,n] = bf16(rs[m] * (x W^T)[m,n] + bias[n])
+ *   lrp_gemm_nt_rs_bias_rope : the same, then RoPE on the columns [0, rope_cols): the bias is added in fp32 to the un-rounded scaled accumulator,
+ *                              the rotation acts on the sum (HF rotates q_proj(x) = x W^T + b), one rounding at the store.  rope_cols must be a
+ *                              multiple of 256 here (the kernel rotates whole 256-column tiles: an odd nq + nk at head_dim 128 would rotate the
+ *                              first v head): lrp_gemm_nt_rs_bias_rope_ok() -> 0 and the entry point LRP_ESHAPE for such shapes (the caller keeps
+ *                              lrp_gemm_nt_rs_bias + lrp_rope_fwd).  The norm-weight fold W' = W diag(w) does not touch the bias. */
+int lrp_gemm_nt_rs_bias(const void* x, const void* W, const float* rs, const void* bias, void* out, int M, int N, int K, int64_t ldx, int64_t ldw,
+                        int64_t ldout, int dtype, void* stream);
+int lrp_gemm_nt_rs_bias_rope_ok(int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols, int head_dim, int dtype);
+int lrp_gemm_nt_rs_bias_rope(const void* x, const void* W, const float* rs, const void* bias, const float* cos, const float* sin, void* out, int M,
+                             int N, int K, int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols, int head_dim, int dtype, void* stream);
 int lrp_gemm_nn_rs(const void* s, const void* W, const float* rs, void* out, int M, int N, int K, int64_t lds, int64_t ldw, int64_t ldout,
                    int dtype, void* stream);      /* out[M,N] = bf16(rs[m] * (s W)), W [K,N] as stored (rs = 1/2 everywhere: the o-projection's dgrad
                                                      with the uniform rule's factor of the P.V product, lxt/efficient/patches.py:193-203) */

@@ -31,6 +31,10 @@ int lrp_launch_gemm_pp_nt_rs_rope(const void* x, const void* W, const float* rs,
                                   int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols, hipStream_t st);
 int lrp_launch_gemm_pp_nn_rs_res(const void* s, const void* W, const float* rs, const void* res, void* out, int M, int N, int K, int64_t lds_,
                                  int64_t ldw, int64_t ldres, int64_t ldout, hipStream_t st);
+int lrp_launch_gemm_pp_nt_rs_bias(const void* x, const void* W, const float* rs, const void* bias, void* out, int M, int N, int K, int64_t ldx,
+                                  int64_t ldw, int64_t ldout, hipStream_t st);
+int lrp_launch_gemm_pp_nt_rs_bias_rope(const void* x, const void* W, const float* rs, const void* bias, const float* cos, const float* sin, void* out,
+                                       int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols, hipStream_t st);
 
 namespace {
 
@@ -671,6 +675,48 @@ extern "C" int lrp_gemm_nt_rs_rope(const void* x, const void* W, const float* rs
         const int rc = lrp_launch_gemm_pp_nt_rs_rope((const char*)x + (int64_t)m0 * ldx * 2, W, rs + m0, cos + (int64_t)p0 * 128, sin + (int64_t)p0 * 128,
                                                      (char*)out + (int64_t)m0 * ldout * 2, M - m0 < chunk ? M - m0 : chunk, N, K, ldx, ldw, ldout,
                                                      seq, rope_cols, (hipStream_t)stream);
+        if (rc != LRP_OK) return rc;
+    }
+    return LRP_OK;
+}
+
+// Qwen2's q / k / v bias in the fused QKV forward: bias bf16 [N], added in fp32 after the row scale (and ahead of the rotation)
+extern "C" int lrp_gemm_nt_rs_bias(const void* x, const void* W, const float* rs, const void* bias, void* out, int M, int N, int K, int64_t ldx,
+                                   int64_t ldw, int64_t ldout, int dtype, void* stream) {
+    if (!x || !W || !rs || !bias || !out || M < 0 || N < 0 || K < 0) return LRP_EINVAL;
+    if (M == 0 || N == 0) return LRP_OK;
+    if (!lrp_gemm_norm_fused_ok(M, N, K, ldx, ldw, 0, dtype)) return LRP_ESHAPE;
+    if (!a16(x) || !a16(W) || !a16(bias) || (ldout % 8)) return LRP_EALIGN;
+    const int chunk = pp_row_chunk(ldx);
+    for (int m0 = 0; m0 < M; m0 += chunk) {
+        const int rc = lrp_launch_gemm_pp_nt_rs_bias((const char*)x + (int64_t)m0 * ldx * 2, W, rs + m0, bias, (char*)out + (int64_t)m0 * ldout * 2,
+                                                     M - m0 < chunk ? M - m0 : chunk, N, K, ldx, ldw, ldout, (hipStream_t)stream);
+        if (rc != LRP_OK) return rc;
+    }
+    return LRP_OK;
+}
+
+// (rope_cols a multiple of 256: the kernel decides "rotate" per 256-column tile, and a tile that held the last k head and the first v head --
+// an odd nq + nk at head_dim 128 -- would rotate v; such shapes keep lrp_gemm_nt_rs_bias + lrp_rope_fwd)
+extern "C" int lrp_gemm_nt_rs_bias_rope_ok(int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols, int head_dim,
+                                           int dtype) {
+    if (rope_cols % 256) return 0;
+    return lrp_gemm_nt_rs_rope_ok(M, N, K, ldx, ldw, ldout, seq, rope_cols, head_dim, dtype);
+}
+
+extern "C" int lrp_gemm_nt_rs_bias_rope(const void* x, const void* W, const float* rs, const void* bias, const float* cos, const float* sin,
+                                        void* out, int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols,
+                                        int head_dim, int dtype, void* stream) {
+    if (!x || !W || !rs || !bias || !cos || !sin || !out || M < 0 || N < 0 || K < 0) return LRP_EINVAL;
+    if (M == 0 || N == 0) return LRP_OK;
+    if (!lrp_gemm_nt_rs_bias_rope_ok(M, N, K, ldx, ldw, ldout, seq, rope_cols, head_dim, dtype)) return LRP_ESHAPE;
+    if (!a16(x) || !a16(W) || !a16(out) || !a16(bias) || !a16(cos) || !a16(sin)) return LRP_EALIGN;
+    const int chunk = pp_row_chunk(ldx);
+    for (int m0 = 0; m0 < M; m0 += chunk) {
+        const int p0 = m0 % seq;          // (a chunk that starts inside a prompt gets tables that start at that position, as lrp_gemm_nt_rs_rope)
+        const int rc = lrp_launch_gemm_pp_nt_rs_bias_rope((const char*)x + (int64_t)m0 * ldx * 2, W, rs + m0, bias, cos + (int64_t)p0 * 128,
+                                                          sin + (int64_t)p0 * 128, (char*)out + (int64_t)m0 * ldout * 2,
+                                                          M - m0 < chunk ? M - m0 : chunk, N, K, ldx, ldw, ldout, seq, rope_cols, (hipStream_t)stream);
         if (rc != LRP_OK) return rc;
     }
     return LRP_OK;

@@ -117,11 +117,14 @@ struct PPEpi {
 // {32 w .. 32 w + 31} and {64 + 32 w .. 64 + 32 w + 31} of its head (w = wave & 1) -- two immediates of the fragment read change, nothing else --
 // so that column tiles j and j + 2 of ONE lane are a rotation pair, and stores its two 32-column segments where they belong.  Weights,
 // activations and every other kernel keep the standard head-dim order.
+// EPI 6 (Qwen2's q / k / v bias): EPI 5 with bias[n] added to rs acc in fp32 BEFORE the rotation, one rounding at the store; the bias is read
+// through the same column map as the B fragments (a second instantiation: EPI 5's code does not change).
 template <typename TO, bool NN, int EPI, int ACT, bool SK = false, bool LEAN = false, bool RS = false>
 __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(
     const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, TO* __restrict__ C, const bf16_t* __restrict__ bias,
     int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int tiles_m, int tiles_n, int kt_per_split, int64_t slab_stride, PPEpi ep) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr bool ROPE = EPI == 5 || EPI == 6;                        // EPI 6 = EPI 5 with a bias [N] added ahead of the rotation
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = wave >> 2, wc = wave & 3;
@@ -206,7 +209,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(
         for (int j = 0; j < 4; ++j)
             cB[j] = (unsigned)(2 * PP_OPND + (8 * hi + (i16 >> 2)) * 512 + (((8 * wc + 2 * j + ((i16 & 3) >> 1)) ^ f) << 4) + 8 * (i16 & 1));
     } else {
-        const unsigned rowB = (unsigned)(2 * PP_OPND + ((EPI == 5 ? (wc >> 1) * 128 + (wc & 1) * 32 : wc * 64) + (lane & 15)) * 128);
+        const unsigned rowB = (unsigned)(2 * PP_OPND + ((ROPE ? (wc >> 1) * 128 + (wc & 1) * 32 : wc * 64) + (lane & 15)) * 128);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) cB[ks] = rowB + (unsigned)(((4 * ks + hi) ^ (lane & 7)) << 4);
         cB[2] = cB[3] = 0;
@@ -263,7 +266,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(
     }
     // EPI 5: cos / sin of row block k in tpre[k & 1] = {cos tile 0, cos tile 1, sin tile 0, sin tile 1} of the lane's 2 x 4 table columns
     const int w5 = wc & 1, hb5 = (wc >> 1) * 128;
-    const bool rot5 = (EPI == 5) && en0 < ep.rope_cols;              // q / k tile (tile-uniform); v tiles only take the row scale
+    const bool rot5 = ROPE && en0 < ep.rope_cols;              // q / k tile (tile-uniform); v tiles only take the row scale
     f32x4 tpre[2][4];
     // (seq is a multiple of 16 -- lrp_gemm_nt_rs_rope_ok -- so the 16 rows of a row block share one prompt and their positions are
     // consecutive: the block's first position is WAVE-UNIFORM, scalar arithmetic incl. the modulo, and the lane part of the address one register)
@@ -305,8 +308,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(
         _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                        \
             PP_DSRD(fb[0][ks].v, cB[ks], (BUF) * PP_OPND);                                        \
             PP_DSRD(fb[1][ks].v, cB[ks], (BUF) * PP_OPND + 2048);                                 \
-            PP_DSRD(fb[2][ks].v, cB[ks], (BUF) * PP_OPND + (EPI == 5 ? 8192 : 4096));             \
-            PP_DSRD(fb[3][ks].v, cB[ks], (BUF) * PP_OPND + (EPI == 5 ? 10240 : 6144));            \
+            PP_DSRD(fb[2][ks].v, cB[ks], (BUF) * PP_OPND + (ROPE ? 8192 : 4096));             \
+            PP_DSRD(fb[3][ks].v, cB[ks], (BUF) * PP_OPND + (ROPE ? 10240 : 6144));            \
         }                                                                                         \
     }
 #define PP_WAIT_A() asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[1][0]), "+v"(fa[1][1]),   \
@@ -364,8 +367,16 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(
     if constexpr (EPI == 3) {
         asm volatile("" : "+v"(rpre[0][0]), "+v"(rpre[0][1]), "+v"(rpre[1][0]), "+v"(rpre[1][1]));
     }
-    if constexpr (EPI == 5) {        // (the tables of the first two row blocks: requested here, ahead of the next tile's staging pieces, like EPI 4's operands)
+    if constexpr (ROPE) {        // (the tables of the first two row blocks: requested here, ahead of the next tile's staging pieces, like EPI 4's operands)
         issue_tab(0, tpre[0]); issue_tab(1, tpre[1]);              // (v tiles load them too and ignore them: flat control flow, no spills)
+    }
+    // EPI 6: the bias of this lane's 4 x 4 columns, packed bf16 (8 registers), same column map as the B-fragment rows above: column tiles j and
+    // j + 2 are a rotate-half pair, so the partner's bias sits in the lane that holds the partner's accumulator
+    u32x2 bpre[4];
+    if constexpr (EPI == 6) {
+        const bf16_t* bp = bias + en0 + hb5 + 32 * w5 + 4 * hi;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bpre[j] = *reinterpret_cast<const u32x2*>(bp + 16 * (j & 1) + 64 * (j >> 1));
     }
     // EPI 2: the coefficient loads of the first row block, likewise ahead of the staging pieces.  Lane (row l & 15, hi) reads, for column tile j,
     // the 16 bytes {cg x 4 | cu x 4} of ITS four intermediate indices ncol + 16 j + 4 hi .. + 3: the stash is in accumulator order (no cross-lane
@@ -515,7 +526,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(
             done = true;
         }
     }
-    if constexpr (EPI == 5) {
+    if constexpr (ROPE) {
         // ---- row scale + RoPE + bf16 pack, full tiles (the host admits only M, N multiples of 256).  Tables software-pipelined two row blocks
         // deep: blocks 0 and 1 were requested right after the K loop, block b + 2 goes out behind block b's stores (8 x 16 B per lane in flight;
         // the tables are L2-resident: 1 MB).
@@ -525,7 +536,11 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(
             for (int b = 0; b < 8; ++b) {
                 f32x4 v[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = acc[b >> 2][b & 3][j] * rsv[b];
+                for (int j = 0; j < 4; ++j) {
+                    v[j] = acc[b >> 2][b & 3][j] * rsv[b];
+                    if constexpr (EPI == 6)          // fp32, on the un-rounded scaled accumulator, ahead of the rotation (HF: RoPE acts on x W^T + b)
+                        v[j] += f32x4{bf16_lo(bpre[j][0]), bf16_hi(bpre[j][0]), bf16_lo(bpre[j][1]), bf16_hi(bpre[j][1])};
+                }
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj) {
                     f32x4 cs = tpre[b & 1][jj], sn = tpre[b & 1][2 + jj];
@@ -705,9 +720,13 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(
 #pragma unroll
         for (int b = 0; b < 8; ++b) asm volatile("" :: "v"(rsv[b]));
     }
-    if constexpr (EPI == 5) {
+    if constexpr (ROPE) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) asm volatile("" :: "v"(tpre[0][k]), "v"(tpre[1][k]));
+    }
+    if constexpr (EPI == 6) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) asm volatile("" :: "v"(bpre[j]));
     }
     if (g == 0) __builtin_amdgcn_s_barrier();                          // balances group 1's extra barrier
     if (!has_next) break;
@@ -716,7 +735,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(
     // the fused gated backward's own gu loads were issued after the pieces and waited for by the compiler, only its last stores remain;
     // ragged tiles and fp32 output (scalar / conditional stores): drain.
     if (full && sizeof(TO) == 2) {
-        if constexpr (EPI == 0 || EPI == 5) PP_VMWAIT(24);
+        if constexpr (EPI == 0 || ROPE) PP_VMWAIT(24);
         else if constexpr (EPI == 1) PP_VMWAIT(32);
         else PP_VMWAIT(8);
     } else PP_VMWAIT(0);
@@ -830,6 +849,21 @@ int lrp_launch_gemm_pp_nt_rs_rope(const void* x, const void* W, const float* rs,
     PPEpi ep{};
     ep.rs = rs; ep.cos = cos; ep.sin = sin; ep.seq = seq; ep.rope_cols = rope_cols;
     return launch_pp_t<bf16_t, false, 5, 0, false, false, true>(x, W, out, nullptr, M, N, K, ldx, ldw, ldout, 1, K / PP_KT, 0, ep, st);
+}
+// out = rs (.) (x W^T) + bias (NT; EPI 0's bias add follows the row scale), bias bf16 [N]
+int lrp_launch_gemm_pp_nt_rs_bias(const void* x, const void* W, const float* rs, const void* bias, void* out, int M, int N, int K, int64_t ldx,
+                                  int64_t ldw, int64_t ldout, hipStream_t st) {
+    PPEpi ep{};
+    ep.rs = rs;
+    return launch_pp_t<bf16_t, false, 0, 0, false, false, true>(x, W, out, bias, M, N, K, ldx, ldw, ldout, 1, K / PP_KT, 0, ep, st);
+}
+// out = RoPE(rs (.) (x W^T) + bias) on the q / k head columns [0, rope_cols), rs (.) (x W^T) + bias on the rest (rope_cols a multiple of 256:
+// a tile never holds a k head and a v head)
+int lrp_launch_gemm_pp_nt_rs_bias_rope(const void* x, const void* W, const float* rs, const void* bias, const float* cos, const float* sin, void* out,
+                                       int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols, hipStream_t st) {
+    PPEpi ep{};
+    ep.rs = rs; ep.cos = cos; ep.sin = sin; ep.seq = seq; ep.rope_cols = rope_cols;
+    return launch_pp_t<bf16_t, false, 6, 0, false, false, true>(x, W, out, bias, M, N, K, ldx, ldw, ldout, 1, K / PP_KT, 0, ep, st);
 }
 // out = rs (.) (s W) (NN: W [K, N] as stored)
 int lrp_launch_gemm_pp_nn_rs(const void* s, const void* W, const float* rs, void* out, int M, int N, int K, int64_t lds_, int64_t ldw,

@@ -123,7 +123,7 @@ def _empty(device):
 
 
 class DecoderLayerFn(Function):
-    """ONE Llama-type decoder layer of an adopted bf16 HF model at M = B S rows on the fused layer of lxt_amd.engine (fused_qkv_fwd,
+    """ONE Llama-type decoder layer (Llama; Qwen2 with its q / k / v bias; Qwen3 with its q / k head norms) of an adopted bf16 HF model at M = B S rows on the fused layer of lxt_amd.engine (fused_qkv_fwd,
     fused_layer_fwd, fused_layer_bwd: LlamaLRP's dense layers), rules as lxt.efficient places them (ref lxt/efficient/patches.py:111-123,
     :145-157, :193-203).  h [B, S, H]; rstd1 fp32 [B S]: 1 / rms of h's rows; fw: patches._fused_layer_weights (norm weights folded in);
     cos / sin fp32 [S, d] (plain causal, un-padded batches).  Returns (h_out, rstd of h_out's rows)."""
@@ -133,9 +133,9 @@ class DecoderLayerFn(Function):
         from ..engine import fused_qkv_fwd, fused_layer_fwd
         B, S, H = h.shape
         h2, alloc = h.reshape(B * S, H).contiguous(), _empty(h.device)
-        qkv, qkr = fused_qkv_fwd(h2, rstd1, fw["wqkv"], cos, sin, S, fw["meta"], alloc)
+        qkv, qkr, *hn = fused_qkv_fwd(h2, rstd1, fw["wqkv"], cos, sin, S, fw["meta"], alloc, bias=fw.get("bqkv"), qk_norm=fw.get("qk_norm"))
         st = fused_layer_fwd(h2, rstd1, qkv, qkr, fw, cos, sin, B, S, fw["meta"], alloc)
-        ctx.save_for_backward(rstd1, st["rstd2"], qkv, qkr, st["o"], st["lse"], st["gu"], cos, sin)
+        ctx.save_for_backward(rstd1, st["rstd2"], qkv, qkr, st["o"], st["lse"], st["gu"], *hn, cos, sin)      # (hn: Qwen3's rstd_q, rstd_k)
         ctx.fw = fw
         ctx.mark_non_differentiable(st["rstd_out"])
         return st["h_out"].view(B, S, H), st["rstd_out"]
@@ -145,8 +145,9 @@ class DecoderLayerFn(Function):
         from ..engine import fused_layer_bwd
         *saved, cos, sin = ctx.saved_tensors
         B, S, H = gy.shape
-        st = dict(zip(("rstd1", "rstd2", "qkv", "qkr", "o", "lse", "gu"), saved))
-        Gh = fused_layer_bwd(gy.reshape(B * S, H).contiguous(), st, ctx.fw, cos, sin, B, S, ctx.fw["meta"], _empty(gy.device))
+        st = dict(zip(("rstd1", "rstd2", "qkv", "qkr", "o", "lse", "gu", "rstd_q", "rstd_k"), saved))
+        Gh = fused_layer_bwd(gy.reshape(B * S, H).contiguous(), st, ctx.fw, cos, sin, B, S, ctx.fw["meta"], _empty(gy.device),
+                             qk_norm=ctx.fw.get("qk_norm"))
         return Gh.view(B, S, H), None, None, None, None
 
 

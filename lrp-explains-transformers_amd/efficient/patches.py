@@ -248,7 +248,8 @@ FUSE_LAYER = True         # module attribute (no environment knob): False = per-
 
 
 def _fused_layer_weights(layer):
-    """-> dict(wqkv, wo, wgu, wd, meta, ok, ok_rows) of an ADOPTED bf16 Llama-type decoder layer for DecoderLayerFn, built once and kept on the module: the
+    """-> dict(wqkv, wo, wgu, wd, meta, bqkv, qk_norm, ok, ok_rows) of an ADOPTED bf16 Llama-type decoder layer (Llama, Qwen2: bqkv = [bq; bk; bv],
+    Qwen3: qk_norm = (q_norm.weight, k_norm.weight); None otherwise) for DecoderLayerFn, built once and kept on the module: the
     fused [q; k; v] weight and the interleaved gate/up weight with the layer's two RMSNorm weights FOLDED into their columns (W' = W diag(w):
     the same network and the same relevance under every rule -- lxt_amd.engine.LlamaLRP does the same; the norm is then a row scale that runs in
     the GEMM epilogues), stored-weight row pitches of engine.fused_layout.  Memory: a second copy of q/k/v and gate/up (Llama-3-8B: 10.7 GB; the
@@ -260,11 +261,17 @@ def _fused_layer_weights(layer):
     att, mlp = getattr(layer, "self_attn", None), getattr(layer, "mlp", None)
     lins = [getattr(att, n, None) for n in ("q_proj", "k_proj", "v_proj", "o_proj")] + [getattr(mlp, n, None) for n in ("gate_proj", "up_proj", "down_proj")]
     n1, n2 = getattr(layer, "input_layernorm", None), getattr(layer, "post_attention_layernorm", None)
-    if not (FUSE_LAYER and all(isinstance(t, torch.nn.Linear) and _owned(t) and t.bias is None and not t.weight.requires_grad for t in lins)
+    # the two dense Qwen variants: a bias on q / k / v (Qwen2; all three or none) and the per-head q_norm / k_norm of the layer's RMSNorm type
+    # (Qwen3); a bias on o or the MLP, one head norm without the other, or a head norm of another kind stay on the per-module patches
+    qkvb = [getattr(t, "bias", None) for t in lins[:3]]
+    hn = [getattr(att, a, None) for a in ("q_norm", "k_norm")]
+    if not (FUSE_LAYER and all(isinstance(t, torch.nn.Linear) and _owned(t) and not t.weight.requires_grad for t in lins)
+            and all(t.bias is None for t in lins[3:]) and len({b is None for b in qkvb}) == 1 and not any(b is not None and b.requires_grad for b in qkvb)
             and n1 is not None and n2 is not None and type(n1) is type(n2) and type(n1).__name__.endswith("RMSNorm")
-            and not any(hasattr(att, a) for a in ("q_norm", "k_norm"))):
+            and len({t is None for t in hn}) == 1 and all(t is None or (type(t) is type(n1) and not t.weight.requires_grad) for t in hn)):
         return None
-    ws = [t.weight for t in lins] + [n1.weight, n2.weight]
+    extra = [b for b in qkvb if b is not None] + [t.weight for t in hn if t is not None]
+    ws = [t.weight for t in lins] + [n1.weight, n2.weight] + extra
     key = tuple((t.data_ptr(), t._version) for t in ws)
     if hit is not None and hit["key"] == key:
         return hit
@@ -281,7 +288,8 @@ def _fused_layer_weights(layer):
     ok = (wq.is_cuda and all(t.dtype == torch.bfloat16 for t in ws) and act in ("silu", "gelu_tanh") and I % ops.GATED_IL == 0 and H % 256 == 0
           and wq.shape == (nq * d, H) and wk.shape == wv.shape == (nk * d, H) and wo.shape == (H, nq * d) and wu.shape == wg.shape
           and wd.shape == (H, I) and d in (64, 128) and nq % nk == 0 and eps1 is not None and eps1 == eps2
-          and float(getattr(att, "scaling", d ** -0.5)) > 0 and not getattr(att, "sliding_window", None) and not ops.attn_needs_transposed(wq, d))
+          and float(getattr(att, "scaling", d ** -0.5)) > 0 and not getattr(att, "sliding_window", None) and not ops.attn_needs_transposed(wq, d)
+          and all(t is None or (t.weight.shape == (d,) and getattr(t, "variance_epsilon", getattr(t, "eps", None)) == eps1) for t in hn))
     if not ok:
         layer.__dict__["_lrp_fused_layer_refused"] = True
         return None
@@ -303,9 +311,11 @@ def _fused_layer_weights(layer):
             Wd.copy_(wd)
             lins[6].weight.data = Wd                      # ONE down weight: the padded one (see _fused_mlp_weights)
         mlp.__dict__.pop("_lrp_fused_mlp", None)          # the MLP-level copy (if an earlier call made one) is superseded
-    key = tuple((t.data_ptr(), t._version) for t in [t_.weight for t_ in lins] + [n1.weight, n2.weight])
+        bqkv = torch.cat([b.detach() for b in qkvb]).contiguous() if qkvb[0] is not None else None        # [bq; bk; bv], as stored: the fold scales W only
+        qk_norm = (hn[0].weight.detach().contiguous(), hn[1].weight.detach().contiguous()) if hn[0] is not None else None
+    key = tuple((t.data_ptr(), t._version) for t in [t_.weight for t_ in lins] + [n1.weight, n2.weight] + extra)
     hit = dict(key=key, wqkv=Wqkv, wo=wo.detach(), wgu=Wgu, wd=Wd, meta=(nq, nk, d, float(eps1), act, float(getattr(att, "scaling", d ** -0.5))),
-               ok={}, ok_rows={})
+               bqkv=bqkv, qk_norm=qk_norm, ok={}, ok_rows={})
     layer.__dict__["_lrp_fused_layer"] = hit
     return hit
 

@@ -178,12 +178,31 @@ def fused_layer_ok(M, W, meta, dtype, cache):
     return hit
 
 
-def fused_qkv_fwd(h, rstd1, Wqkv, cos, sin, S, meta, alloc, explicit=False):
+def fused_qkv_fwd(h, rstd1, Wqkv, cos, sin, S, meta, alloc, explicit=False, bias=None, qk_norm=None):
     """-> (qkv, qkr): rstd1 (.) (h Wqkv^T) with RoPE in the GEMM's epilogue where the kernel takes it, else a rope_fwd pass (always in the
-    explicit placement: RoPE's stabiliser needs the un-rotated q / k).  meta = (nq, nk, d, eps, act, scale); alloc(tag, rows, cols, pad, dtype)"""
+    explicit placement: RoPE's stabiliser needs the un-rotated q / k).  meta = (nq, nk, d, eps, act, scale); alloc(tag, rows, cols, pad, dtype).
+    The two dense Qwen variants (efficient placement; the defaults are the Llama sequence):
+      bias [(nq + 2 nk) d] (Qwen2): added in the same epilogue, in fp32 and ahead of the rotation (HF rotates x W^T + b); the norm-weight fold
+        scales columns of W only, the bias is used as stored;
+      qk_norm = (wq [d], wk [d]) (Qwen3): the per-head RMSNorm of q and k sits between the projection and RoPE, so the GEMM leaves qkv un-rotated
+        and one site kernel norms and rotates; -> (qkv, qkr, rstd_q, rstd_k), the head norms' 1 / rms for fused_layer_bwd."""
     nq, nk, d = meta[:3]
     M, nqk = h.shape[0], (nq + nk) * d
     qkv = alloc("qkv", M, (nq + 2 * nk) * d, 0, h.dtype)
+    if qk_norm is not None:
+        if bias is None:
+            ops.gemm_nt_rs(h, Wqkv, rstd1, qkv)
+        else:
+            ops.gemm_nt_rs_bias(h, Wqkv, rstd1, bias, qkv)
+        qkr = alloc("qkr", M, nqk, 0, h.dtype)
+        rstd_q, rstd_k = alloc("rstd_q", 1, M * nq, 0, torch.float32)[0], alloc("rstd_k", 1, M * nk, 0, torch.float32)[0]
+        ops.qk_norm_rope_fwd(qkv, qk_norm[0], qk_norm[1], qkr[:, : nq * d], qkr[:, nq * d:], rstd_q, rstd_k, cos, sin, S, nq, nk, d, meta[3])
+        return qkv, qkr, rstd_q, rstd_k
+    if bias is not None:
+        if not explicit and ops.gemm_nt_rs_bias_rope_ok(h, Wqkv, qkv, S, nqk, d):
+            return qkv, ops.gemm_nt_rs_bias_rope(h, Wqkv, rstd1, bias, cos, sin, qkv, S, nqk, d)[:, :nqk]
+        ops.gemm_nt_rs_bias(h, Wqkv, rstd1, bias, qkv)
+        return qkv, ops.rope_fwd(qkv, alloc("qkr", M, nqk, 0, h.dtype), cos, sin, S, nq + nk, d)
     if not explicit and ops.gemm_nt_rs_rope_ok(h, Wqkv, qkv, S, nqk, d):
         return qkv, ops.gemm_nt_rs_rope(h, Wqkv, rstd1, cos, sin, qkv, S, nqk, d)[:, :nqk]
     ops.gemm_nt_rs(h, Wqkv, rstd1, qkv)
@@ -219,9 +238,12 @@ def fused_layer_fwd(h, rstd1, qkv, qkr, W, cos, sin, B, S, meta, alloc, row_iv=N
     return st
 
 
-def fused_layer_bwd(G, st, W, cos, sin, B, S, meta, alloc, row_iv=None):
+def fused_layer_bwd(G, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm=None):
     """efficient placement: G at the layer's output -> G at its input in 7 GEMMs, rules / norms in their epilogues, D and RoPE's backward in the
-    attention backward.  st: what the forward left, plus rstd1; alloc("half", 1, M, ...) returns fp32 rows already set to 1/2 (no fill per layer)"""
+    attention backward.  st: what the forward left, plus rstd1; alloc("half", 1, M, ...) returns fp32 rows already set to 1/2 (no fill per layer).
+    A q / k / v bias (Qwen2) changes nothing here: it receives relevance and passes none on, G_h is the same GEMM.  qk_norm = (wq, wk) (Qwen3;
+    st then holds rstd_q, rstd_k): the dQ kernel leaves the gradient of the ROTATED q, and one site kernel builds the whole Aqkv operand -- RoPE
+    transposed, the head norms' row-constant scale, the GQA group sums -- in place of gqa_reduce_rope + gqa_reduce."""
     nq, nk, d, _, _, scale = meta
     M, H, I, dt, nqk, nqkv = B * S, G.shape[1], W["wd"].shape[1], G.dtype, (nq + nk) * d, (nq + 2 * nk) * d
     pt = fused_layout(H, I, nq, nk, d, dt)
@@ -232,6 +254,11 @@ def fused_layer_bwd(G, st, W, cos, sin, B, S, meta, alloc, row_iv=None):
     q, k, v = st["qkr"][:, : nq * d], st["qkr"][:, nq * d:], st["qkv"][:, nqk:]
     D = alloc("D", B * nq, S, 0, torch.float32).view(B, nq, S)
     Aqkv, dk_h, dv_h = new("Aqkv", nqkv, pt["Aqkv"]), new("dk_h", nq * d), new("dv_h", nq * d)
+    if qk_norm is not None:
+        dq = ops.attn_bwd_dq_d(q, k, v, Gho, st["o"], st["lse"], D, new("dq", nq * d), B, S, nq, nk, d, scale, row_iv=row_iv)
+        ops.attn_bwd_dkv(q, k, v, None, Gho, None, st["lse"], D, dk_h, dv_h, B, S, nq, nk, d, scale, 0.0, 0.0, row_iv=row_iv)
+        ops.qkv_bwd_pack(dq, dk_h, dv_h, qk_norm[0], qk_norm[1], st["rstd_q"], st["rstd_k"], cos, sin, Aqkv, S, nq, nk, d)
+        return ops.gemm_nn_rs_res(Aqkv, W["wqkv"], st["rstd1"], Gs1, new("Gh", H))
     ops.attn_bwd_dq_d(q, k, v, Gho, st["o"], st["lse"], D, Aqkv[:, : nq * d], B, S, nq, nk, d, scale, row_iv=row_iv, rope=(cos, sin))
     ops.attn_bwd_dkv(q, k, v, None, Gho, None, st["lse"], D, dk_h, dv_h, B, S, nq, nk, d, scale, 0.0, 0.0, row_iv=row_iv)
     ops.gqa_reduce_rope(dk_h, Aqkv[:, nq * d: nqk], M, S, nk, nq // nk, d, cos, sin)
@@ -239,7 +266,7 @@ def fused_layer_bwd(G, st, W, cos, sin, B, S, meta, alloc, row_iv=None):
     return ops.gemm_nn_rs_res(Aqkv, W["wqkv"], st["rstd1"], Gs1, new("Gh", H))
 
 
-FUSED_SCRATCH = frozenset(("ssq", "m", "half", "Agu", "Gs1", "Gho", "D", "Aqkv", "dk_h", "dv_h"))      # temporaries: one buffer serves every layer
+FUSED_SCRATCH = frozenset(("ssq", "m", "half", "Agu", "Gs1", "Gho", "D", "Aqkv", "dk_h", "dv_h", "dq"))      # temporaries: one buffer serves every layer
 
 
 # ---- the scaffolding of the fused drivers (LlamaLRP here, Gemma3LRP / Gemma3MMLRP / BertLRP in their modules): one owner per decision
@@ -488,11 +515,14 @@ class LlamaLRP:
         nq, hd = cfg["n_heads"], cfg["head_dim"]
         self.meta = (nq, cfg["n_kv"], hd, cfg["rms_eps"], self.act, hd ** -0.5)      # (the layer description of the fused-layer functions above)
         self.flat, top, self.layers = pack_flat(*self.flat_layout(cfg, dtype), len(W["layers"]), dtype, dev)
-        self.embed, self.lm_head, self.norm = (put_rows(top[k], W[k]) for k in ("embed", "lm_head", "norm"))
+        self.embed, self.norm = put_rows(top["embed"], W["embed"]), put_rows(top["norm"], W["norm"])
+        self.lm_head = put_rows(top["lm_head"], W["lm_head"]) if "lm_head" in top else self.embed      # (cfg["tied"]: one stored copy serves both)
         self.lm_head_t = None                        # [H, V] copy, made on the first dense-seed explanation
         for Lw, L in zip(self.layers, W["layers"]):
-            for k in ("ln1", "ln2", "wo", "wd"):
+            for k in ("ln1", "ln2", "wo", "wd") + (("qn", "kn") if "qn" in Lw else ()):
                 put_rows(Lw[k], L[k])
+            if "bqkv" in Lw:
+                put_rows(Lw["bqkv"], L["bq"], L["bk"], L["bv"])
             put_rows(Lw["wqkv"], L["wq"], L["wk"], L["wv"])
             put_gate_up(Lw["wgu"], L["wg"], L["wu"])
             if self.folded:          # (in place, on the weights as stored: the product sees the storage dtype's rounding of W)
@@ -519,6 +549,11 @@ class LlamaLRP:
     def _fused(self, M):
         """fused_layer_ok of this engine's layers at M rows (every layer has the same shapes and pitches)"""
         return fused_layer_ok(M, self.layers[0], self.meta, self.dtype, self._nf_cache) if self.layers else FusedOk(False, False, False, False)
+
+    @staticmethod
+    def _qk_norm(Lw):
+        """(q_norm, k_norm) weights [d] of a layer that has them (QwenLRP's Qwen3 layers), else None"""
+        return (Lw["qn"], Lw["kn"]) if "qn" in Lw else None
 
     def _gated_coef(self, M):
         """the gated-MLP rules run as a coefficient stash inside the two GEMMs around them (ops.gemm_gated_fwd_coef / _bwd_coef) at this row count"""
@@ -547,12 +582,21 @@ class LlamaLRP:
 
     @staticmethod
     def flat_layout(cfg, dtype):
-        """(shape, row pitch) of the weights in `flat` (pack_flat): the model-wide ones, then one layer's; the Linears at fused_layout's pitches"""
+        """(shape, row pitch) of the weights in `flat` (pack_flat): the model-wide ones, then one layer's; the Linears at fused_layout's pitches.
+        Optional cfg keys of the dense Qwen driver (engine_qwen.QwenLRP; absent = the Llama layout): tied -- no lm_head copy; qkv_bias -- the
+        concatenated [bq; bk; bv]; qk_norm -- the per-head q / k norm weights [d]"""
         H, I, nq, nk, d, V = cfg["hidden"], cfg["inter"], cfg["n_heads"], cfg["n_kv"], cfg["head_dim"], cfg["vocab"]
         pt = fused_layout(H, I, nq, nk, d, dtype)
-        return (dict(embed=((V, H), None), lm_head=((V, H), None), norm=((H,), None)),
-                dict(ln1=((H,), None), ln2=((H,), None), wqkv=(((nq + 2 * nk) * d, H), pt["Wqkv"]), wo=((H, nq * d), None),
-                     wgu=((2 * I, H), pt["Wgu"]), wd=((H, I), pt["Wd"])))
+        top = dict(embed=((V, H), None), lm_head=((V, H), None), norm=((H,), None))
+        layer = dict(ln1=((H,), None), ln2=((H,), None), wqkv=(((nq + 2 * nk) * d, H), pt["Wqkv"]), wo=((H, nq * d), None),
+                     wgu=((2 * I, H), pt["Wgu"]), wd=((H, I), pt["Wd"]))
+        if cfg.get("tied"):
+            del top["lm_head"]
+        if cfg.get("qkv_bias"):
+            layer["bqkv"] = (((nq + 2 * nk) * d,), None)
+        if cfg.get("qk_norm"):
+            layer.update(qn=((d,), None), kn=((d,), None))
+        return top, layer
 
     @classmethod
     def from_hf(cls, model, **kw):
@@ -599,7 +643,9 @@ class LlamaLRP:
             if ready is not None:
                 st["h"], st["rstd1"] = ready
                 ready = None
-                qkv, qkr = fused_qkv_fwd(st["h"], st["rstd1"], Lw["wqkv"], self.cos, self.sin, S, self.meta, self._alloc(li), explicit)
+                qkv, qkr, *hn = fused_qkv_fwd(st["h"], st["rstd1"], Lw["wqkv"], self.cos, self.sin, S, self.meta, self._alloc(li), explicit,
+                                              Lw.get("bqkv"), self._qk_norm(Lw))
+                st.update(zip(("rstd_q", "rstd_k"), hn))
             else:
                 x, st["rstd1"] = ar.new("x", M, H), ar.f32(("rstd1", li), M)
                 if branch is None:
@@ -608,8 +654,13 @@ class LlamaLRP:
                 else:
                     st["h"] = ar.new(("h", li), M, H)
                     ops.add_rmsnorm_fwd(h_prev, branch, Lw["ln1"], c["rms_eps"], hsum_out=st["h"], y=x, rstd=st["rstd1"])
-                qkv = self._lin_fwd(x, Lw["wqkv"], ar.new(("qkv", li), M, nqkv))
-                qkr = ops.rope_fwd(qkv, ar.new(("qkr", li), M, nqk), self.cos, self.sin, S, nq + nk, d)
+                qkv, qkn = ops.linear_fwd(x, Lw["wqkv"], Lw.get("bqkv"), out=ar.new(("qkv", li), M, nqkv)), self._qk_norm(Lw)
+                if qkn is not None:      # (QwenLRP: the per-head q / k norm between the projection and RoPE)
+                    qn = ar.new("qkn", M, nqk)
+                    st["rstd_q"], st["rstd_k"] = ar.f32(("rstd_q", li), M * nq), ar.f32(("rstd_k", li), M * nk)
+                    ops.head_rmsnorm_fwd(qkv[:, : nq * d], qkn[0], qn[:, : nq * d], st["rstd_q"], nq, d, c["rms_eps"])
+                    ops.head_rmsnorm_fwd(qkv[:, nq * d: nqk], qkn[1], qn[:, nq * d:], st["rstd_k"], nk, d, c["rms_eps"])
+                qkr = ops.rope_fwd(qkv if qkn is None else qn, ar.new(("qkr", li), M, nqk), self.cos, self.sin, S, nq + nk, d)
             if nf and not top:
                 # (not chained in the last layer: the tail below wants h1 and dn of the explained rows separately)
                 st.update(fused_layer_fwd(st["h"], st["rstd1"], qkv, qkr, Lw, self.cos, self.sin, B, S, self.meta,
@@ -714,7 +765,7 @@ class LlamaLRP:
                     Gm = self._lin_bwd(Adn, Lw["wd"], ar.new("Gm", M, I))
                     ops.colsum_dot(st["m"], Gm, B, S, out=lat["R_mlp"][li])
             if full and not st.get("top", False):          # (Adn = Gs: eps = 0)
-                Gs = Adn = fused_layer_bwd(Gs, st, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv)
+                Gs = Adn = fused_layer_bwd(Gs, st, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv, self._qk_norm(Lw))
                 layer_R = layer_R + [ops.readout(st["h"], Gs, out=ar.f32(("rel", li), M))] if layer_relevance else None
                 if "resid" in latent:
                     ops.colsum_dot(st["h"], Gs, B, S, out=lat["R_resid"][li])
@@ -766,7 +817,8 @@ class LlamaLRP:
                 Gho_t = ops.transpose_heads(Gho, B, S, nq, d)
             dk_h, dv_h = ar.new("dk_h", M, nq * d), ar.new("dv_h", M, nq * d)
             Aqkv = ar.get("Aqkv", (M, nqkv), dt, pad=fused_layout(H, I, nq, nk, d, dt)["Aqkv"] - nqkv)
-            if fuse_prep and q_begin == 0 and fuse_rope:
+            qkn = self._qk_norm(Lw)
+            if fuse_prep and q_begin == 0 and fuse_rope and qkn is None:
                 # RoPE's backward rides on the dQ store and on dK's group sum (no rope_bwd pass, no dqk round trip): both write Aqkv directly
                 ops.attn_bwd_dq_d(q, k, v, Gho, st["o"], st["lse"], D, Aqkv[:, : nq * d], B, S, nq, nk, d, scale, row_iv=row_iv,
                                   rope=(self.cos, self.sin))
@@ -785,7 +837,11 @@ class LlamaLRP:
                 ops.gqa_reduce(dk_h, dqk[:, nq * d:], M, nk, rep, d)
                 if E["lin"] == 0.0:
                     ops.gqa_reduce(dv_h, Aqkv[:, nqk:], M, nk, rep, d)
-                    ops.rope_bwd(dqk, None, None, Aqkv[:, :nqk], self.cos, self.sin, S, nq + nk, d, 0.0, 0.0)
+                    Gqk = ops.rope_bwd(dqk, None, None, Aqkv[:, :nqk] if qkn is None else ar.new("Gqkn", M, nqk), self.cos, self.sin, S, nq + nk, d,
+                                       0.0, 0.0)
+                    if qkn is not None:      # the head norms' backward with rstd detached: a row-constant scale per head
+                        ops.head_rmsnorm_bwd(Gqk[:, : nq * d], qkn[0], st["rstd_q"], Aqkv[:, : nq * d], nq, d)
+                        ops.head_rmsnorm_bwd(Gqk[:, nq * d:], qkn[1], st["rstd_k"], Aqkv[:, nq * d: nqk], nk, d)
                 else:
                     dv = ops.gqa_reduce(dv_h, ar.new("dv", M, nk * d), M, nk, rep, d)
                     ops.eps_scale2d(dv, v, Aqkv[:, nqk:], 1.0, E["lin"])

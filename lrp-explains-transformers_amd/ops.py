@@ -614,6 +614,39 @@ def gemm_nt_rs_rope(x, W, rs, cos, sin, out, seq, rope_cols, head_dim):
     return out
 
 
+def gemm_nt_rs_bias(x, W, rs, bias, out):
+    """out = rs[:, None] * (x @ W^T) + bias: gemm_nt_rs for a biased projection (Qwen2's q / k / v; the folded norm weight is in W, not in bias)"""
+    M, K = x.shape
+    N = W.shape[0]
+    same(x, W, out, bias)
+    f32(rs)
+    assert bias.shape == (N,) and bias.is_contiguous()
+    _timed(2.0 * M * N * K, "plain_norm", lambda: lib.lrp_gemm_nt_rs_bias(p(x), p(W), p(rs), p(bias), p(out), M, N, K, x.stride(0), W.stride(0),
+                                                                          out.stride(0), dt(x), stream()), "lrp_gemm_nt_rs_bias")
+    return out
+
+
+def gemm_nt_rs_bias_rope_ok(x, W, out, seq, rope_cols, head_dim):
+    M, K = x.shape
+    return bool(ROPE_FWD_FUSION and NORM_FUSION and x.dtype == torch.bfloat16 and
+                lib.lrp_gemm_nt_rs_bias_rope_ok(M, W.shape[0], K, x.stride(0), W.stride(0), out.stride(0), seq, rope_cols, head_dim, _DT[x.dtype]))
+
+
+def gemm_nt_rs_bias_rope(x, W, rs, bias, cos, sin, out, seq, rope_cols, head_dim):
+    """gemm_nt_rs_rope with bias [N] added ahead of the rotation: RoPE(rs (x W^T) + bias) on the columns [0, rope_cols), rs (x W^T) + bias on
+    the rest, one rounding (the fused QKV forward of a Qwen2 layer); rope_cols a multiple of 256"""
+    M, K = x.shape
+    N = W.shape[0]
+    same(x, W, out, bias)
+    f32(rs, cos, sin)
+    assert bias.shape == (N,) and bias.is_contiguous()
+    assert cos.shape[0] >= seq and cos.stride(0) == head_dim and sin.stride(0) == head_dim
+    _timed(2.0 * M * N * K, "plain_norm", lambda: lib.lrp_gemm_nt_rs_bias_rope(p(x), p(W), p(rs), p(bias), p(cos), p(sin), p(out), M, N, K, x.stride(0),
+                                                                               W.stride(0), out.stride(0), seq, rope_cols, head_dim, dt(x),
+                                                                               stream()), "lrp_gemm_nt_rs_bias_rope")
+    return out
+
+
 def gemm_nn_rs(s, W, rs, out):
     """out = rs[:, None] * (s @ W) from the STORED weight W [K, N] (rs = 1/2: the o-projection's dgrad with the uniform rule's factor)"""
     M, K = s.shape
