@@ -460,6 +460,8 @@ int lrp_add2_rule_bwd(const void* a, const void* b, const void* R, void* Ra, voi
  * K9 / harness.  ref: docs/source/quickstart.rst:120-141, examples/paper/llama.py:45-46
  *   lrp_readout      : R_tok[row] = sum_h emb[row,h]*G[row,h]   (fp32 out)
  *   lrp_colsum_dot   : out[b,j] = sum_t x[b S + t,j]*g[b S + t,j]   (fp32 out; the column counterpart, below)
+ *   lrp_headdot      : out[b,h,t] = scale sum_j x[b S + t,(h/rep) d + j]*g'[b S + t,h d + j]   (fp32 out; per attention head: declared in
+ *                      lrp_hip_latent.h, which this header includes at its end)
  *   lrp_head_seed    : last-token head, one launch per prompt batch:
  *        Gxn[b,:] = zfac * W_lm[idx[b],:]  with zfac = z/(z+eps_lin), z = logits[b,idx[b]]
  *        then the final-norm identity rule: Gh_last[b,:] = Gxn (*) w' * rstd[b]
@@ -529,4 +531,6 @@ int lrp_moe_gate_up_dgrad(const void* Agu, const void* Wgu, const int* plan, voi
 #ifdef __cplusplus
 }
 #endif
+/* the per-head read-out of the latent feature attribution (same ABI version, same conventions; a header of its own) */
+#include "lrp_hip_latent.h"
 #endif /* LRP_HIP_H */

@@ -22,9 +22,12 @@ _CTYPE = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_floa
 
 
 def parse_header(path=HEADER_PATH):
-    """-> {name: (restype_str, [argtype_str...])} for every function the header declares."""
+    """-> {name: (restype_str, [argtype_str...])} for every function the header, and the headers it includes from its own directory, declare."""
     with open(path) as f:
         src = f.read()
+    for inc in re.findall(r'^#include "(\w+\.h)"', src, flags=re.M):          # (lrp_hip.h includes lrp_hip_latent.h: one ABI, two files)
+        with open(os.path.join(os.path.dirname(path), inc)) as f:
+            src += f.read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     out = {}
     for m in re.finditer(r"\b(int64_t|int|const char\*)\s+(lrp_\w+)\s*\(([^)]*)\)\s*;", src):

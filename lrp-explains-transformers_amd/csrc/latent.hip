@@ -1,5 +1,6 @@
-// latent.hip -- latent feature attribution read-outs (include/lrp_hip.h: lrp_colsum_dot).
+// latent.hip -- latent feature attribution read-outs (include/lrp_hip.h: lrp_colsum_dot; include/lrp_hip_latent.h: lrp_headdot).
 //
+// ---- lrp_colsum_dot
 // out[b, j] = sum_{t < S} x[b S + t, j] g[b S + t, j]: the token-summed relevance of every hidden unit (a residual-stream dimension with
 // x = h, g = G_h; an MLP neuron with x = m, g = G_m).  HBM-bound: 2 B S N sizeof(T) bytes are read once.
 //
@@ -74,6 +75,98 @@ __global__ __launch_bounds__(256) void colsum_dot_reduce_kernel(const float* __r
     out[(int64_t)b * N + j] = s;
 }
 
+// ---- lrp_headdot
+// out[b, h, t] = scale sum_{j < d} x[b S + t, (h / rep) d + j] g'[b S + t, h d + j]: the relevance of every attention head at every position
+// (x = o, q, k or v; g = its gradient, per QUERY head; g' = g, or the forward rotate-half RoPE of g at position t -- the fused dQ kernel
+// leaves RoPE^T(dq) and only the rotated q is kept: sum_d q dq = sum_d q_rot RoPE(dq_unrot)).  HBM-bound: x and g are read once, 16 bytes
+// per lane; the rotation's partner vector and the fp32 tables are re-reads of lines the workgroup has in cache.
+//
+// Order of the sums (bitwise deterministic, batch invariant, no atomics): a workgroup owns HD_ROWS consecutive rows of ONE prompt, counted
+// from the prompt's first row, and a block of up to HD_HEADS heads (all of them for nh <= 64).  A (row, head) dot belongs to a group of LG
+// lanes (the power of two >= d / V, V = 16 / sizeof(T)): a lane multiplies its V elements in order, the group adds its lanes by an
+// xor butterfly.  Consecutive groups take consecutive heads of a row, so a wave reads 1 KiB runs of g.  The sums go through an LDS tile
+// [head][row] and leave as runs of HD_ROWS floats along t for each head (plain vector stores).
+// Every load is in bounds by construction: a group past the last (row, head) of the block re-reads the last one and stores nothing, a lane
+// past d reads element 0 and adds 0.
+constexpr int HD_ROWS = 16;     // rows of one workgroup: B ceil(S / 16) workgroups (512 at B S = 8192: two per CU)
+constexpr int HD_HEADS = 64;    // heads of one workgroup (LDS tile 64 x 17 floats)
+constexpr int HD_UNROLL = 4;    // (row, head) items a group has in flight
+
+inline int64_t hd_chunks(int S) { return ((int64_t)S + HD_ROWS - 1) / HD_ROWS; }
+
+template <typename T, bool ROPE>
+__global__ __launch_bounds__(256) void headdot_kernel(const T* __restrict__ x, const T* __restrict__ g, const float* __restrict__ cs,
+                                                      const float* __restrict__ sn, float* __restrict__ out, int S, int nh, int rep, int d,
+                                                      int64_t ldx, int64_t ldg, float scale, int lg_shift) {
+    constexpr int V = 16 / sizeof(T);
+    __shared__ float tile[HD_HEADS][HD_ROWS + 1];
+    const int LG = 1 << lg_shift, NG = 256 >> lg_shift;
+    const int gi = threadIdx.x >> lg_shift, li = threadIdx.x & (LG - 1);
+    const int h0 = blockIdx.x * HD_HEADS, nhb = min(HD_HEADS, nh - h0);
+    const int r0 = blockIdx.y * HD_ROWS, nr = min(HD_ROWS, S - r0), b = blockIdx.z;
+    const int64_t row0 = (int64_t)b * S + r0;
+    const int items = nr * nhb, half = d >> 1;
+    const bool act = li * V < d;
+    const int j = act ? li * V : 0;
+    // the rotation's partner of elements j .. j + V - 1: one 16-byte vector when d / 2 is a multiple of V, else element by element
+    const bool lo = j < half, pvec = (half % V) == 0;
+    const int jp = lo ? j + half : j - half;
+    for (int it0 = 0; it0 < items; it0 += NG * HD_UNROLL) {
+        Vec16<T> xa[HD_UNROLL], ga[HD_UNROLL], gp[HD_UNROLL];
+        int rr[HD_UNROLL], hh[HD_UNROLL];
+#pragma unroll
+        for (int u = 0; u < HD_UNROLL; ++u) {
+            const int item = min(it0 + u * NG + gi, items - 1);
+            rr[u] = item / nhb;
+            hh[u] = item - rr[u] * nhb;
+            const int h = h0 + hh[u];
+            const T* gr = g + (row0 + rr[u]) * ldg + (int64_t)h * d;
+            xa[u] = ld16(x + (row0 + rr[u]) * ldx + (int64_t)(h / rep) * d + j);
+            ga[u] = ld16(gr + j);
+            if constexpr (ROPE) {
+                if (pvec) {
+                    gp[u] = ld16(gr + jp);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < V; ++k) {
+                        const int e = j + k;                       // (j + k < d: d is a multiple of V)
+                        gp[u].set(k, to_f32(gr[e < half ? e + half : e - half]));
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < HD_UNROLL; ++u) {
+            float acc = 0.f;
+            if constexpr (ROPE) {
+                const float* c = cs + (int64_t)(r0 + rr[u]) * d + j;
+                const float* s = sn + (int64_t)(r0 + rr[u]) * d + j;
+#pragma unroll
+                for (int k4 = 0; k4 < V; k4 += 4) {
+                    const f32x4 cv = *reinterpret_cast<const f32x4*>(c + k4), sv = *reinterpret_cast<const f32x4*>(s + k4);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const float p = gp[u].get(k4 + k) * sv[k];
+                        const bool low = pvec ? lo : (j + k4 + k < half);
+                        acc += xa[u].get(k4 + k) * (ga[u].get(k4 + k) * cv[k] + (low ? -p : p));
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < V; ++k) acc += xa[u].get(k) * ga[u].get(k);
+            }
+            acc = act ? acc : 0.f;
+            for (int m = LG >> 1; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);
+            if (li == 0 && it0 + u * NG + gi < items) tile[hh[u]][rr[u]] = acc * scale;
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nhb * HD_ROWS; i += 256) {
+        const int h = i / HD_ROWS, r = i - h * HD_ROWS;
+        if (r < nr) out[((int64_t)b * nh + h0 + h) * S + r0 + r] = tile[h][r];
+    }
+}
+
 }  // namespace
 
 #define DISPATCH_T(dtype, ...)                                              \
@@ -106,5 +199,28 @@ extern "C" int lrp_colsum_dot(const void* x, const void* g, float* out, void* ws
         if (rc != LRP_OK) return rc;
         hipLaunchKernelGGL(colsum_dot_reduce_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)B), dim3(256), 0, st, (const float*)ws, out, N, nch);
     }
+    return lrp_check_launch();
+}
+
+extern "C" int lrp_headdot(const void* x, const void* g, const float* cos, const float* sin, float* out, int M, int B, int S, int nh, int rep,
+                           int d, int64_t ldx, int64_t ldg, float scale, int dtype, void* stream) {
+    if (!x || !g || !out || (dtype != LRP_F32 && dtype != LRP_BF16) || (cos == nullptr) != (sin == nullptr)) return LRP_EINVAL;
+    if (B < 1 || S < 1 || (int64_t)B * S != (int64_t)M || nh < 1 || rep < 1 || d < 1 || nh % rep != 0 || d > 256 || (cos && (d & 1)) ||
+        B > 65535 || hd_chunks(S) > 65535 || ldx < (int64_t)(nh / rep) * d || ldg < (int64_t)nh * d)
+        return LRP_ESHAPE;
+    const int V = dtype == LRP_BF16 ? 8 : 4;
+    if (((uintptr_t)x | (uintptr_t)g | (uintptr_t)cos | (uintptr_t)sin) % 16 || ldx % V || ldg % V || d % V || (uintptr_t)out % 4) return LRP_EALIGN;
+    int lg_shift = 0;
+    while ((V << lg_shift) < d) ++lg_shift;             // lanes of a (row, head) group: 1 .. 64
+    const dim3 grid((unsigned)((nh + HD_HEADS - 1) / HD_HEADS), (unsigned)hd_chunks(S), (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+    DISPATCH_T(dtype, {
+        if (cos)
+            hipLaunchKernelGGL((headdot_kernel<T, true>), grid, dim3(256), 0, st, (const T*)x, (const T*)g, cos, sin, out, S, nh, rep, d, ldx, ldg,
+                               scale, lg_shift);
+        else
+            hipLaunchKernelGGL((headdot_kernel<T, false>), grid, dim3(256), 0, st, (const T*)x, (const T*)g, cos, sin, out, S, nh, rep, d, ldx, ldg,
+                               scale, lg_shift);
+    })
     return lrp_check_launch();
 }

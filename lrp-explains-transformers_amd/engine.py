@@ -238,12 +238,13 @@ def fused_layer_fwd(h, rstd1, qkv, qkr, W, cos, sin, B, S, meta, alloc, row_iv=N
     return st
 
 
-def fused_layer_bwd(G, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm=None):
+def fused_layer_bwd(G, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm=None, heads=None):
     """efficient placement: G at the layer's output -> G at its input in 7 GEMMs, rules / norms in their epilogues, D and RoPE's backward in the
     attention backward.  st: what the forward left, plus rstd1; alloc("half", 1, M, ...) returns fp32 rows already set to 1/2 (no fill per layer).
     A q / k / v bias (Qwen2) changes nothing here: it receives relevance and passes none on, G_h is the same GEMM.  qk_norm = (wq, wk) (Qwen3;
     st then holds rstd_q, rstd_k): the dQ kernel leaves the gradient of the ROTATED q, and one site kernel builds the whole Aqkv operand -- RoPE
-    transposed, the head norms' row-constant scale, the GQA group sums -- in place of gqa_reduce_rope + gqa_reduce."""
+    transposed, the head norms' row-constant scale, the GQA group sums -- in place of gqa_reduce_rope + gqa_reduce.
+    heads: a HeadSink (explain(heads=...)) that reads the per-head relevance off the buffers while they are live; None: nothing is launched."""
     nq, nk, d, _, _, scale = meta
     M, H, I, dt, nqk, nqkv = B * S, G.shape[1], W["wd"].shape[1], G.dtype, (nq + nk) * d, (nq + 2 * nk) * d
     pt = fused_layout(H, I, nq, nk, d, dt)
@@ -254,13 +255,23 @@ def fused_layer_bwd(G, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm=
     q, k, v = st["qkr"][:, : nq * d], st["qkr"][:, nq * d:], st["qkv"][:, nqk:]
     D = alloc("D", B * nq, S, 0, torch.float32).view(B, nq, S)
     Aqkv, dk_h, dv_h = new("Aqkv", nqkv, pt["Aqkv"]), new("dk_h", nq * d), new("dv_h", nq * d)
+    if heads is not None:
+        heads("out", st["o"], Gho, scale=2.0)          # (Gho = 1/2 G_o out of the dgrad's epilogue)
     if qk_norm is not None:
         dq = ops.attn_bwd_dq_d(q, k, v, Gho, st["o"], st["lse"], D, new("dq", nq * d), B, S, nq, nk, d, scale, row_iv=row_iv)
         ops.attn_bwd_dkv(q, k, v, None, Gho, None, st["lse"], D, dk_h, dv_h, B, S, nq, nk, d, scale, 0.0, 0.0, row_iv=row_iv)
+        if heads is not None:
+            heads("q", q, dq)
+            heads("k", k, dk_h, nq // nk)
+            heads("v", v, dv_h, nq // nk)
         ops.qkv_bwd_pack(dq, dk_h, dv_h, qk_norm[0], qk_norm[1], st["rstd_q"], st["rstd_k"], cos, sin, Aqkv, S, nq, nk, d)
         return ops.gemm_nn_rs_res(Aqkv, W["wqkv"], st["rstd1"], Gs1, new("Gh", H))
     ops.attn_bwd_dq_d(q, k, v, Gho, st["o"], st["lse"], D, Aqkv[:, : nq * d], B, S, nq, nk, d, scale, row_iv=row_iv, rope=(cos, sin))
     ops.attn_bwd_dkv(q, k, v, None, Gho, None, st["lse"], D, dk_h, dv_h, B, S, nq, nk, d, scale, 0.0, 0.0, row_iv=row_iv)
+    if heads is not None:
+        heads("q", q, Aqkv[:, : nq * d], rope=(cos, sin))          # RoPE^T(dq) against the rotated q: lrp_headdot rotates it back
+        heads("k", k, dk_h, nq // nk)
+        heads("v", v, dv_h, nq // nk)
     ops.gqa_reduce_rope(dk_h, Aqkv[:, nq * d: nqk], M, S, nk, nq // nk, d, cos, sin)
     ops.gqa_reduce(dv_h, Aqkv[:, nqk:], M, nk, nq // nk, d)
     return ops.gemm_nn_rs_res(Aqkv, W["wqkv"], st["rstd1"], Gs1, new("Gh", H))
@@ -410,6 +421,54 @@ def latent_request(latent, H, I, dtype):
         if name in req and (n * dtype.itemsize) % 16:
             raise ValueError(f"latent={name!r} needs rows of a multiple of 16 bytes ({n} elements of {dtype} are not)")
     return req
+
+
+HEADS = ("out", "q", "k", "v")
+
+
+def head_request(heads, d, dtype):
+    """explain(heads=...) -> frozenset of the requested per-head read-outs ("out": the relevance each head writes, at the o projection's input;
+    "q" / "k" / "v": at the attention's query / key / value input, k and v per QUERY head); None -> the empty set.  Raises ValueError before a
+    kernel of the model runs: an unknown name, a non-iterable, or a head dim lrp_headdot cannot read (rows of a head are 16-byte vectors,
+    d <= 256)"""
+    if heads is None:
+        return frozenset()
+    try:
+        names = (heads,) if isinstance(heads, str) else tuple(heads)
+    except TypeError:
+        raise ValueError(f"heads must be an iterable of names from {HEADS}, got {heads!r}") from None
+    bad = [n for n in names if n not in HEADS]
+    if bad:
+        raise ValueError(f"heads: unknown read-out(s) {bad}; choose from {HEADS}")
+    req = frozenset(names)
+    if req and (not isinstance(d, int) or d < 1 or d > 256 or (d * dtype.itemsize) % 16):
+        raise ValueError(f"heads: the per-head read-out needs a head dim <= 256 whose rows are a multiple of 16 bytes ({d} elements of {dtype} are not)")
+    return req
+
+
+class HeadSink:
+    """the per-head read-outs of one explanation: out[name] [L, B, nq, S] fp32, one ops.headdot per requested name and layer on the buffers the
+    attention backward has just left (the fused-layer functions and LlamaLRP.backward call it; a name that was not requested launches nothing).
+    rope_scale: 1 / s^2 for rotary tables that carry an attention_scaling s (the rotated read-out applies the tables a second time)"""
+
+    def __init__(self, req, nL, B, S, nq, d, device, rope_scale=1.0):
+        self.B, self.S, self.nq, self.d, self.rope_scale, self.li = B, S, nq, d, rope_scale, None
+        self.out = {n: torch.empty(nL, B, nq, S, device=device, dtype=torch.float32) for n in HEADS if n in req}
+
+    def layer(self, li):
+        self.li = li
+        return self
+
+    def __call__(self, name, x, g, rep=1, scale=1.0, rope=None):
+        if name in self.out:
+            ops.headdot(x, g, self.B, self.S, self.nq, rep, self.d, scale * (self.rope_scale if rope is not None else 1.0), rope,
+                        out=self.out[name][self.li])
+
+    def last(self, name, x_l, g_l):
+        """the sparse top layer: one live query row per prompt -- the last column from those rows, exactly 0 elsewhere"""
+        if name in self.out:
+            dst = self.out[name][self.li].zero_()
+            dst[:, :, self.S - 1].copy_(ops.headdot(x_l, g_l, self.B, 1, self.nq, 1, self.d)[:, :, 0])
 
 
 class GraphCache:
@@ -705,8 +764,9 @@ class LlamaLRP:
         return dict(stash=stash, last=last, row_iv=row_iv, **head_fwd(ar, h_prev, branch, top, last, self.norm, self.lm_head, c["rms_eps"]))
 
     # ---------------------------------------------------------------------------------------------
-    def backward(self, fw, emb, idx, B, S, layer_relevance=False, seed=None, latent=frozenset()):
-        """-> (G at the embedding, layer_R rows or None, dict of the token-summed latent read-outs: R_resid [L+1, B, H] / R_mlp [L, B, I])"""
+    def backward(self, fw, emb, idx, B, S, layer_relevance=False, seed=None, latent=frozenset(), heads=None):
+        """-> (G at the embedding, layer_R rows or None, dict of the token-summed latent read-outs: R_resid [L+1, B, H] / R_mlp [L, B, I]);
+        heads: a HeadSink that collects the per-head read-outs layer by layer, or None"""
         c, E = self.cfg, self.eps
         H, I, d, nq, nk = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"]
         M, rep = B * S, nq // nk
@@ -764,8 +824,9 @@ class LlamaLRP:
                 else:
                     Gm = self._lin_bwd(Adn, Lw["wd"], ar.new("Gm", M, I))
                     ops.colsum_dot(st["m"], Gm, B, S, out=lat["R_mlp"][li])
+            hs = None if heads is None else heads.layer(li)
             if full and not st.get("top", False):          # (Adn = Gs: eps = 0)
-                Gs = Adn = fused_layer_bwd(Gs, st, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv, self._qk_norm(Lw))
+                Gs = Adn = fused_layer_bwd(Gs, st, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv, self._qk_norm(Lw), hs)
                 layer_R = layer_R + [ops.readout(st["h"], Gs, out=ar.f32(("rel", li), M))] if layer_relevance else None
                 if "resid" in latent:
                     ops.colsum_dot(st["h"], Gs, B, S, out=lat["R_resid"][li])
@@ -780,6 +841,8 @@ class LlamaLRP:
                                      E["add"], E["lin"])
                 Gof_l = self._lin_bwd(Aa_l, Lw["wo"], ar.new("Gof_l", B, nq * d))
                 Gho, D, Gs1 = top_attn_operands(ar, Gof_l, st["o_l"], Gs1_l, last, S, nq, d, E["pv"])
+                if hs is not None:
+                    hs.last("out", st["o_l"], Gof_l)
                 q_begin = S - 1
             else:
                 gu = st["gu"]
@@ -806,9 +869,13 @@ class LlamaLRP:
                     # no attn_bwd_prep pass: Gho = 1/2 (Aa Wo) straight out of the o-projection's dgrad (row scale 1/2: exact), and the dQ
                     # kernel forms D = rowsum(Gho (*) o) from the rows it loads anyway and leaves it for the dK / dV kernel
                     ops.gemm_nn_rs(Aa, Lw["wo"], half, Gho)
+                    if hs is not None:
+                        hs("out", st["o"], Gho, scale=2.0)
                 else:
                     Gof = self._lin_bwd(Aa, Lw["wo"], ar.new("Gof", M, nq * d))
                     ops.attn_bwd_prep(Gof, st["o"], Gho, D, B, S, nq, d, E["pv"], 0.5)
+                    if hs is not None:
+                        hs("out", st["o"], Gof)
             q, k, v = qkr[:, : nq * d], qkr[:, nq * d:], qkv[:, nqk:]
             k_t = q_t = Gho_t = None
             if self.attn_t:        # kernels that read head-transposed copies (fp32, head dims other than 128)
@@ -823,6 +890,8 @@ class LlamaLRP:
                 ops.attn_bwd_dq_d(q, k, v, Gho, st["o"], st["lse"], D, Aqkv[:, : nq * d], B, S, nq, nk, d, scale, row_iv=row_iv,
                                   rope=(self.cos, self.sin))
                 ops.attn_bwd_dkv(q, k, v, None, Gho, None, st["lse"], D, dk_h, dv_h, B, S, nq, nk, d, scale, 0.0, 0.0, row_iv=row_iv)
+                if hs is not None:
+                    hs("q", q, Aqkv[:, : nq * d], rope=(self.cos, self.sin))
                 ops.gqa_reduce_rope(dk_h, Aqkv[:, nq * d: nqk], M, S, nk, rep, d, self.cos, self.sin)
                 ops.gqa_reduce(dv_h, Aqkv[:, nqk:], M, nk, rep, d)
             else:
@@ -834,6 +903,10 @@ class LlamaLRP:
                                     q_begin=q_begin, row_iv=row_iv)
                 ops.attn_bwd_dkv(q, k, v, q_t, Gho, Gho_t, st["lse"], D, dk_h, dv_h, B, S, nq, nk, d, scale, E["mask"], E["qk"],
                                  q_begin=q_begin, row_iv=row_iv)
+                if hs is not None and q_begin == 0:
+                    hs("q", q, dqk[:, : nq * d])
+                elif hs is not None:          # (the sparse top layer: dq's only live rows)
+                    hs.last("q", q.index_select(0, last), dqk.index_select(0, last)[:, : nq * d])
                 ops.gqa_reduce(dk_h, dqk[:, nq * d:], M, nk, rep, d)
                 if E["lin"] == 0.0:
                     ops.gqa_reduce(dv_h, Aqkv[:, nqk:], M, nk, rep, d)
@@ -846,6 +919,9 @@ class LlamaLRP:
                     dv = ops.gqa_reduce(dv_h, ar.new("dv", M, nk * d), M, nk, rep, d)
                     ops.eps_scale2d(dv, v, Aqkv[:, nqk:], 1.0, E["lin"])
                     ops.rope_bwd(dqk, qkr, qkv[:, :nqk], Aqkv[:, :nqk], self.cos, self.sin, S, nq + nk, d, E["rope"], E["lin"])
+            if hs is not None:
+                hs("k", k, dk_h, rep)
+                hs("v", v, dv_h, rep)
             rel = ar.f32(("rel", li), M) if layer_relevance else None
             if nfb and ops.norm_fusion_part("bwd_qkv"):
                 # K1n: Gs = rstd1 (.) (Aqkv W'qkv) + Gs1 -- the input norm's identity rule and the residual add in the qkv dgrad's epilogue.  The
@@ -880,7 +956,7 @@ class LlamaLRP:
         return Gs, layer_R, lat
 
     # ---------------------------------------------------------------------------------------------
-    def _run(self, input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, latent=frozenset()):
+    def _run(self, input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, latent=frozenset(), heads=frozenset()):
         """forward + backward + read-out on the current stream: library launches only, no host synchronisation (capturable)"""
         if emb is None:
             emb = self.embed.index_select(0, input_ids.reshape(-1))
@@ -888,7 +964,11 @@ class LlamaLRP:
         if idx is None:
             # (a dense seed explains no single logit; idx / logit then report the arg-max for convenience)
             idx, _ = ops.argmax_rows(fw["logits"])
-        G, layer_R, lat = self.backward(fw, emb, idx, B, S, layer_relevance or "trace" in latent, seed=seed, latent=latent)
+        hs = None
+        if heads:
+            c = self.cfg
+            hs = HeadSink(heads, len(self.layers), B, S, c["n_heads"], c["head_dim"], self.device, float(c.get("attention_scaling", 1.0)) ** -2)
+        G, layer_R, lat = self.backward(fw, emb, idx, B, S, layer_relevance or "trace" in latent, seed=seed, latent=latent, heads=hs)
         out = explanation(emb, G, idx, fw["logits"], B, S, return_G)
         if layer_relevance:
             rows = [layer_R[0]] + [r.view(B, S).sum(1) for r in layer_R[1:]]
@@ -903,11 +983,15 @@ class LlamaLRP:
             trace[nL, :, S - 1] = layer_R[0]
             out["R_trace"] = trace
         out.update(lat)
+        if hs is not None:
+            out.update({"R_head_" + n: t for n, t in hs.out.items()})
+            if "out" in hs.out:
+                out["R_head"] = hs.out["out"].sum(-1)
         return out
 
     @torch.no_grad()
     def explain(self, input_ids=None, inputs_embeds=None, target=None, layer_relevance=False, return_G=False, lengths=None,
-                seed=None, graph=False, latent=None):
+                seed=None, graph=False, latent=None, heads=None):
         """input_ids [B,S] (or inputs_embeds [B,S,H]); target: None (arg-max of the last position) or
         int tensor [B].  Returns dict(idx [B], logit [B], R_tok [B,S] fp32, and optionally
         layer_R [L+1, B] (sum_h h (*) G_h at every residual-stream boundary) and G_emb [B,S,H]).
@@ -924,15 +1008,21 @@ class LlamaLRP:
         more output, fp32: R_trace [L+1, B, S] = sum_h h (*) G_h per token at every residual boundary (index 0 = R_tok, index l = the output
         of layer l - 1, index L = the head's row: only each prompt's last column is non-zero; R_trace[l].sum(-1) is layer_R[l]);
         R_resid [L+1, B, H] = sum_t h (*) G_h per residual dimension at the same boundaries; R_mlp [L, B, I] = sum_t m (*) G_m per MLP neuron
-        (m: the down projection's input, HF column order).  R_tok, logit and layer_R do not change with it."""
+        (m: the down projection's input, HF column order).  R_tok, logit and layer_R do not change with it.
+        heads (optional): names from {"out", "q", "k", "v"}, the per-head attention relevance, each one more fp32
+        output [L, B, n_heads, S]: R_head_out = sum_d o (*) G_o at the o projection's input, per query head and query position (and R_head
+        [L, B, n_heads] = R_head_out.sum(-1): which heads of which layer carry the prediction); R_head_q / R_head_k / R_head_v = sum_d x (*) G_x
+        at the attention's query / key / value input (after RoPE and Qwen3's head norm), k and v per QUERY head at the SOURCE position: which
+        tokens a head pulls its relevance from.  Pad columns under lengths are exactly 0; nothing else changes with it."""
+        hd = head_request(heads, self.cfg.get("head_dim"), self.dtype)
         lat = latent_request(latent, self.cfg["hidden"], self.cfg["inter"], self.dtype)
         B, S, emb, row_iv, idx = explain_inputs(input_ids, inputs_embeds, lengths, target, self.cfg["vocab"], self.max_seq, self.dtype,
                                                 self.device, seed)
         if inputs_embeds is None:
             input_ids = input_ids.to(self.device)
         if not graph:
-            return self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, lat)
+            return self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, lat, hd)
         if emb is not None or lengths is not None or seed is not None or return_G:
             raise ValueError("graph=True takes input_ids only (no inputs_embeds / lengths / seed / return_G)")
-        return self._graphs((B, S, idx is not None, bool(layer_relevance), self.mode, tuple(sorted(lat))),
-                            lambda ids, idx_: self._run(ids, None, B, S, None, idx_, layer_relevance, False, None, lat), input_ids, idx)
+        return self._graphs((B, S, idx is not None, bool(layer_relevance), self.mode, tuple(sorted(lat)), tuple(sorted(hd))),
+                            lambda ids, idx_: self._run(ids, None, B, S, None, idx_, layer_relevance, False, None, lat, hd), input_ids, idx)

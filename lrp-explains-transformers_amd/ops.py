@@ -864,6 +864,31 @@ def colsum_dot(x, g, B, S, out=None, ws=None):
     return out
 
 
+def headdot(x, g, B, S, nh, rep, d, scale=1.0, rope=None, out=None):
+    """out[b, h, t] = scale sum_j x[b S + t, (h // rep) d + j] g'[b S + t, h d + j]  ([B, nh, S] fp32): the relevance of every attention head at
+    every position.  x [B S, (nh // rep) d] and g [B S, nh d] token-major with unit column stride (any row pitch); rope = (cos, sin) fp32
+    [>= S, d]: g' = the forward rotate-half RoPE of g at position t (the fused dQ kernel's RoPE^T(dq) against the rotated q), else g' = g.
+    Fixed-order fp32 sums, a prompt's result depends on its rows only."""
+    M = x.shape[0]
+    if (x.dim() != 2 or g.dim() != 2 or g.shape[0] != M or x.shape[1] != (nh // max(rep, 1)) * d or g.shape[1] != nh * d
+            or x.stride(1) != 1 or g.stride(1) != 1):
+        raise ValueError(f"headdot: x {tuple(x.shape)} / g {tuple(g.shape)} must be [B S, {nh} // {rep} * {d}] / [B S, {nh} * {d}] with contiguous rows")
+    px, pg = p(x), p(g)                 # (device tensors only: raises before anything is allocated)
+    out = torch.empty(B, nh, S, device=x.device, dtype=torch.float32) if out is None else out
+    same(x, g)
+    f32(out)
+    if tuple(out.shape) != (B, nh, S) or not out.is_contiguous():
+        raise ValueError(f"headdot: out must be a contiguous [{B}, {nh}, {S}] tensor")
+    pc = ps = None
+    if rope is not None:
+        cos, sin = rope
+        f32(cos, sin)
+        assert cos.shape[0] >= S and sin.shape[0] >= S and cos.stride(0) == d and sin.stride(0) == d
+        pc, ps = p(cos), p(sin)
+    check(lib.lrp_headdot(px, pg, pc, ps, p(out), M, B, S, nh, rep, d, x.stride(0), g.stride(0), float(scale), dt(x), stream()), "lrp_headdot")
+    return out
+
+
 def argmax_rows(logits):
     B, V = logits.shape
     idx = torch.empty(B, device=logits.device, dtype=torch.int32)

@@ -5,7 +5,11 @@
       over it -- and that rate over the 8 TB/s HBM peak;
   (2) the per-step overhead of each LlamaLRP.explain(latent=...) option against a plain explain(), bf16, at the Llama-3-8B layer shape
       (H 4096, I 14336, 32 / 8 heads of 128) with --layers layers, B = 4, S = 2048; the requests alternate inside each round.
-usage: python tools/latent_bench.py [--out FILE] [--layers 2] [--reps 20] [--rounds 5]"""
+  --heads: the per-head attention read-outs instead (profiles/heads_bench.txt):
+  (3) lrp_headdot at B S = 8192 rows, 32 query heads of 128, bf16: rep = 1 (q, o) and rep = 4 (k, v over 8 kv heads), with and without the
+      rotated form, the bytes the algorithm must read (x, g and the fp32 output) over the median time, next to lrp_colsum_dot in the same run;
+  (4) the per-step overhead of each LlamaLRP.explain(heads=...) name, and of all four, against a plain explain() of the same process.
+usage: python tools/latent_bench.py [--heads] [--out FILE] [--layers 2] [--reps 20] [--rounds 5]"""
 import argparse
 import os
 import statistics
@@ -35,6 +39,7 @@ def main():
     ap.add_argument("--layers", type=int, default=2)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--heads", action="store_true", help="measure lrp_headdot and explain(heads=...) instead of the latent options")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("latent_bench needs a HIP device")
@@ -62,6 +67,23 @@ def main():
             f"(best {nbytes / best / 1e9:.2f} TB/s); workspace {ops.lib.lrp_colsum_dot_ws(B, S, N) / 1e6:.1f} MB of fp32 partials")
         del x, y
 
+    # ---- (3) the per-head kernel
+    if a.heads:
+        nq, d = 32, 128
+        cos, sin = E.rope_tables(1.0 / (5e5 ** (torch.arange(0, d, 2, dtype=torch.float32) / d)), 1.0, S, torch.bfloat16, "cuda")
+        for r in (1, 4):
+            x = torch.randn(B * S, nq // r * d, generator=g, device="cuda").bfloat16()
+            y = torch.randn(B * S, nq * d, generator=g, device="cuda").bfloat16()
+            out = torch.empty(B, nq, S, device="cuda")
+            for rope in (None, (cos, sin)):
+                for _ in range(5):
+                    ops.headdot(x, y, B, S, nq, r, d, rope=rope, out=out)
+                med, best = timed(lambda: ops.headdot(x, y, B, S, nq, r, d, rope=rope, out=out), 50)
+                nbytes = (x.numel() + y.numel()) * 2 + out.numel() * 4
+                say(f"headdot bf16 B={B} S={S} nh={nq} rep={r} d={d} {'rotated' if rope else 'plain  '}: {med * 1e3:7.1f} us median, {best * 1e3:7.1f} us "
+                    f"best over 50 calls; {nbytes / 1e6:.0f} MB -> {nbytes / med / 1e6:.0f} GB/s median = {nbytes / med / 1e9 / 8.0:.2f} of 8 TB/s "
+                    f"(best {nbytes / best / 1e6:.0f} GB/s)")
+            del x, y
     # ---- (2) the engine
     H, I, d, L = 4096, 14336, 128, a.layers
     cfg = dict(hidden=H, inter=I, n_layers=L, n_heads=32, n_kv=8, head_dim=d, vocab=4096, rope_theta=5e5, rms_eps=1e-5)
@@ -74,23 +96,28 @@ def main():
     del W
     ids = torch.randint(0, 4096, (B, S), generator=torch.Generator().manual_seed(1)).cuda()
     reqs = dict(plain=None, trace=("trace",), resid=("resid",), mlp=("mlp",), all=("trace", "resid", "mlp"))
+    kw = "latent"
+    if a.heads:
+        reqs, kw = dict(plain=None, out=("out",), q=("q",), k=("k",), v=("v",), all=E.HEADS), "heads"
     for lat in reqs.values():                                   # warm-up: every shape, every arena buffer
         for _ in range(2):
-            eng.explain(ids, latent=lat)
+            eng.explain(ids, **{kw: lat})
     torch.cuda.synchronize()
     arena0 = eng._arena.nbytes()
     ts = {k: [] for k in reqs}
     for _ in range(a.rounds):
         for k, lat in reqs.items():
-            ts[k].append(timed(lambda: eng.explain(ids, latent=lat), max(1, a.reps // a.rounds))[0])
+            ts[k].append(timed(lambda: eng.explain(ids, **{kw: lat}), max(1, a.reps // a.rounds))[0])
     base = statistics.median(ts["plain"])
     say(f"engine bf16, Llama-3-8B layer shape, {L} layers, B={B} S={S} (M = {B * S} rows), median of {a.rounds} rounds x "
         f"{max(1, a.reps // a.rounds)} steps, requests alternating:")
     for k in reqs:
         m = statistics.median(ts[k])
-        say(f"  latent={k:6s}: {m:8.2f} ms per step   +{m - base:6.2f} ms  ({100 * (m - base) / base:+5.1f} %)  "
+        say(f"  {kw}={k:6s}: {m:8.2f} ms per step   +{m - base:6.2f} ms  ({100 * (m - base) / base:+5.1f} %)  "
             f"= {(m - base) / L * 1e3:7.1f} us per layer   [spread {min(ts[k]):.2f} .. {max(ts[k]):.2f}]")
-    say(f"  arena after every request: {arena0 / 2**30:.2f} GiB (kept m: {L} x {B * S} x {I} bf16 = {L * B * S * I * 2 / 2**30:.2f} GiB of it)")
+    say(f"  arena after every request: {arena0 / 2**30:.2f} GiB" + (f"; outputs {L} x {B} x 32 x {S} fp32 = {L * B * 32 * S * 4 / 2**20:.0f} MiB per name"
+                                                                    if a.heads else
+                                                                    f" (kept m: {L} x {B * S} x {I} bf16 = {L * B * S * I * 2 / 2**30:.2f} GiB of it)"))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
