@@ -1,4 +1,4 @@
-/* lrp_hip_latent.h -- part of the C ABI of liblrp_hip.so (version 8): the per-head read-out of the latent feature attribution.
+/* lrp_hip_latent.h -- part of the C ABI of liblrp_hip.so (version 8): the per-head and token-to-token read-outs of the latent feature attribution.
  * Included by lrp_hip.h (include that one); error codes, dtype codes and conventions are lrp_hip.h's. */
 #ifndef LRP_HIP_LATENT_H
 #define LRP_HIP_LATENT_H
@@ -24,6 +24,30 @@ extern "C" {
  *   from the prompt's first row, and transposes its sums through LDS into runs along t. */
 int lrp_headdot(const void* x, const void* g, const float* cos, const float* sin, float* out, int M, int B, int S, int nh, int rep, int d,
                 int64_t ldx, int64_t ldg, float scale, int dtype, void* stream);
+
+/* lrp_attn_relmap (csrc/attnmap.hip): out[b, i, j] = gscale sum_{h_lo <= h < h_hi} P_h[i, j] (g[b S + i, h d :] . v[b S + j, (h / rep) d :]) with
+ * P_h[i, j] = exp(scale q[b S + i, h d :] . k[b S + j, (h / rep) d :] - lse[b, h, i]), rep = Hq / Hkv, for every (i, j) the mask lets through
+ * (causal: j <= i; row_lo / row_hi: row_lo[b S + i] <= j < row_hi[b S + i], as the attention entries of lrp_hip.h read them) and exactly 0
+ * elsewhere; fp32 [B, S, S] contiguous, EVERY element written (callers pass uninitialised memory) -- the token-to-token attention relevance
+ * `attn_weights * attn_weights.grad` of eager attention, summed over a range of query heads, recomputed per tile from what the flash-style
+ * kernels keep.  ref: retain_grad() on the probabilities inside HF's eager_attention_forward, which lxt/efficient/patches.py:193-203 wraps
+ * (divide_gradient sits on query / key / value, not on the probabilities: no 1/2 in the map).
+ *   q, g: [M = B S, Hq d] (row pitches ldq, ldg), k, v: [M, Hkv d] (ldk, ldv), token-major, consumed in place from the fused QKV output:
+ *   q / k as the attention kernels read them (rotated, after Qwen3's head norm); g = the gradient at the o projection's input, or the
+ *   dgrad epilogue's Gho = 1/2 of it with gscale = 2.  All four LRP_F32 or all four LRP_BF16.  lse fp32 [B, Hq, S] as lrp_attn_fwd writes
+ *   it: the natural-log sum-exp of the SCALED scores, -inf for a row with an empty interval (such a row gives exactly 0, never NaN).
+ *   LRP_BF16: d in {64, 128}, both contractions on the bf16 MFMA, fp32 from the accumulators to the store (P and G_P are never rounded).
+ *   LRP_F32: any d <= 256 that is a multiple of 4, LDS-tiled FMA (the parity path).
+ *   NULL q / k / v / g / lse / out, an unknown dtype -> LRP_EINVAL.  B S != M, B / S / Hq / Hkv / d < 1, Hq % Hkv != 0, a head range that is
+ *   empty or not inside [0, Hq), a d the dtype is not served at, ldq / ldg < Hq d, ldk / ldv < Hkv d, one of row_lo / row_hi without the
+ *   other, B > 65535 -> LRP_ESHAPE.  q / k / v / g bases or pitches off the 16-byte grid, out / lse / row_lo / row_hi off 4 bytes
+ *   -> LRP_EALIGN.  All of it before any launch.
+ *   One launch, no "_t" operands, no workspace, no atomics.  A workgroup owns one 64 x 64 tile of one prompt's map, counted from the prompt's
+ *   first row, walks the heads in ascending order with the tile in fp32 registers and stores it once: bitwise deterministic and batch
+ *   invariant.  A tile no row of it can see (above the diagonal, outside the union of its rows' intervals) is zero-filled without a load. */
+int lrp_attn_relmap(const void* q, const void* k, const void* v, const void* g, const float* lse, float* out, int M, int B, int S, int Hq,
+                    int Hkv, int d, int h_lo, int h_hi, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, float scale, float gscale,
+                    int causal, const int* row_lo, const int* row_hi, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

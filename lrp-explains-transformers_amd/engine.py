@@ -23,6 +23,7 @@ Python only sequences kernel launches on the current stream; it performs no arit
 """
 import collections
 import math
+import operator
 
 import torch
 
@@ -238,13 +239,14 @@ def fused_layer_fwd(h, rstd1, qkv, qkr, W, cos, sin, B, S, meta, alloc, row_iv=N
     return st
 
 
-def fused_layer_bwd(G, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm=None, heads=None):
+def fused_layer_bwd(G, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm=None, heads=None, attn_map=None):
     """efficient placement: G at the layer's output -> G at its input in 7 GEMMs, rules / norms in their epilogues, D and RoPE's backward in the
     attention backward.  st: what the forward left, plus rstd1; alloc("half", 1, M, ...) returns fp32 rows already set to 1/2 (no fill per layer).
     A q / k / v bias (Qwen2) changes nothing here: it receives relevance and passes none on, G_h is the same GEMM.  qk_norm = (wq, wk) (Qwen3;
     st then holds rstd_q, rstd_k): the dQ kernel leaves the gradient of the ROTATED q, and one site kernel builds the whole Aqkv operand -- RoPE
     transposed, the head norms' row-constant scale, the GQA group sums -- in place of gqa_reduce_rope + gqa_reduce.
-    heads: a HeadSink (explain(heads=...)) that reads the per-head relevance off the buffers while they are live; None: nothing is launched."""
+    heads: a HeadSink (explain(heads=...)) that reads the per-head relevance off the buffers while they are live; None: nothing is launched.
+    attn_map: an AttnMapSink (explain(attn_map=...)), the token-to-token maps off the same buffers; None: nothing is launched."""
     nq, nk, d, _, _, scale = meta
     M, H, I, dt, nqk, nqkv = B * S, G.shape[1], W["wd"].shape[1], G.dtype, (nq + nk) * d, (nq + 2 * nk) * d
     pt = fused_layout(H, I, nq, nk, d, dt)
@@ -257,6 +259,8 @@ def fused_layer_bwd(G, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm=
     Aqkv, dk_h, dv_h = new("Aqkv", nqkv, pt["Aqkv"]), new("dk_h", nq * d), new("dv_h", nq * d)
     if heads is not None:
         heads("out", st["o"], Gho, scale=2.0)          # (Gho = 1/2 G_o out of the dgrad's epilogue)
+    if attn_map is not None:
+        attn_map(q, k, v, Gho, st["lse"], 2.0, row_iv)
     if qk_norm is not None:
         dq = ops.attn_bwd_dq_d(q, k, v, Gho, st["o"], st["lse"], D, new("dq", nq * d), B, S, nq, nk, d, scale, row_iv=row_iv)
         ops.attn_bwd_dkv(q, k, v, None, Gho, None, st["lse"], D, dk_h, dv_h, B, S, nq, nk, d, scale, 0.0, 0.0, row_iv=row_iv)
@@ -469,6 +473,85 @@ class HeadSink:
         if name in self.out:
             dst = self.out[name][self.li].zero_()
             dst[:, :, self.S - 1].copy_(ops.headdot(x_l, g_l, self.B, 1, self.nq, 1, self.d)[:, :, 0])
+
+
+ATTN_MAP_SUM = "sum"
+
+
+def attn_map_request(attn_map, nL, nq, d, dtype, mode):
+    """explain(attn_map=...) -> (want_sum, pairs): "sum" asks for the token-to-token attention relevance summed over the query heads of every
+    layer, a (layer, head) pair for the map of one query head; an iterable may mix both, repeated entries count once and the pairs keep the
+    order of their first mention.  None -> (False, ()).  Raises ValueError before a kernel of the model runs: an unknown name, a non-iterable,
+    a pair outside [0, nL) x [0, nq) (negative indices are not wrapped), a head dim or dtype lrp_attn_relmap does not serve (bf16: 64 or 128;
+    fp32: a multiple of 4 up to 256), or the explicit placement (its Gho carries the eps_pv ratio: a different quantity, pinned by no fixture)"""
+    if attn_map is None:
+        return False, ()
+    if isinstance(attn_map, str):
+        items = (attn_map,)
+    else:
+        try:
+            items = tuple(attn_map)
+        except TypeError:
+            raise ValueError(f'attn_map must be "{ATTN_MAP_SUM}" or an iterable of (layer, head) pairs, got {attn_map!r}') from None
+    want_sum, pairs = False, []
+    for it in items:
+        if isinstance(it, str):
+            if it != ATTN_MAP_SUM:
+                raise ValueError(f'attn_map: unknown request {it!r}; choose "{ATTN_MAP_SUM}" or (layer, head) pairs')
+            want_sum = True
+            continue
+        try:
+            l, h = (operator.index(x) for x in it)
+        except (TypeError, ValueError):
+            raise ValueError(f'attn_map: {it!r} is neither "{ATTN_MAP_SUM}" nor a (layer, head) pair of integers') from None
+        if not (0 <= l < nL and 0 <= h < nq):
+            raise ValueError(f"attn_map: pair ({l}, {h}) outside the model's {nL} layers x {nq} query heads")
+        if (l, h) not in pairs:
+            pairs.append((l, h))
+    if want_sum or pairs:
+        if mode != "efficient":
+            raise ValueError(f"attn_map: token-to-token maps are defined for the efficient placement only, not mode={mode!r}")
+        ok = isinstance(d, int) and ((dtype == torch.bfloat16 and d in (64, 128)) or (dtype == torch.float32 and 1 <= d <= 256 and d % 4 == 0))
+        if not ok:
+            raise ValueError(f"attn_map: no kernel for head dim {d} in {dtype} (bf16: 64 or 128; fp32: a multiple of 4 up to 256)")
+    return want_sum, tuple(pairs)
+
+
+class AttnMapSink:
+    """the token-to-token maps of one explanation: total [L, B, S, S] fp32 ("sum": all query heads) and per_head [n, B, S, S] (the requested
+    (layer, head) pairs, in request order), one ops.attn_relmap per output and layer on the buffers the attention backward is about to read
+    (rotated q / k, v, Gho, lse); a layer nothing was requested of launches nothing"""
+
+    def __init__(self, req, nL, B, S, nq, nk, d, scale, device):
+        want_sum, self.pairs = req
+        self.B, self.S, self.nq, self.nk, self.d, self.scale, self.li = B, S, nq, nk, d, scale, None
+        self.total = torch.empty(nL, B, S, S, device=device, dtype=torch.float32) if want_sum else None
+        self.per_head = torch.empty(len(self.pairs), B, S, S, device=device, dtype=torch.float32) if self.pairs else None
+
+    def layer(self, li):
+        self.li = li
+        return self
+
+    def __call__(self, q, k, v, g, lse, gscale, row_iv=None):
+        a = (q, k, v, g, lse, self.B, self.S, self.nq, self.nk, self.d, self.scale)
+        if self.total is not None:
+            ops.attn_relmap(*a, gscale=gscale, row_iv=row_iv, out=self.total[self.li])
+        for n, (l, h) in enumerate(self.pairs):
+            if l == self.li:
+                ops.attn_relmap(*a, heads=(h, h + 1), gscale=gscale, row_iv=row_iv, out=self.per_head[n])
+
+    def top(self, ar, q, k, v, Gho, lse, gscale, last, row_iv=None):
+        """the sparse top layer: Gho is dense with one live row per prompt, and lse is written for those rows only -- every other row gets an
+        empty key interval, so it is exactly 0 whatever its lse holds.  The interval vectors are arena buffers (ar), as every temporary of
+        the backward"""
+        M = self.B * self.S
+        hi_live = ar.get("am_hi_l", (last.numel(),), torch.int32)
+        if row_iv is None:
+            lo, hi_live = ar.get("am_lo", (M,), torch.int32, zero=True), hi_live.fill_(self.S)
+        else:
+            lo, hi_live = row_iv[0].reshape(M), torch.index_select(row_iv[1].reshape(M), 0, last, out=hi_live)
+        hi = ar.get("am_hi", (M,), torch.int32, zero=True).index_copy_(0, last, hi_live)
+        self(q, k, v, Gho, lse, gscale, (lo, hi))
 
 
 class GraphCache:
@@ -764,9 +847,9 @@ class LlamaLRP:
         return dict(stash=stash, last=last, row_iv=row_iv, **head_fwd(ar, h_prev, branch, top, last, self.norm, self.lm_head, c["rms_eps"]))
 
     # ---------------------------------------------------------------------------------------------
-    def backward(self, fw, emb, idx, B, S, layer_relevance=False, seed=None, latent=frozenset(), heads=None):
+    def backward(self, fw, emb, idx, B, S, layer_relevance=False, seed=None, latent=frozenset(), heads=None, attn_map=None):
         """-> (G at the embedding, layer_R rows or None, dict of the token-summed latent read-outs: R_resid [L+1, B, H] / R_mlp [L, B, I]);
-        heads: a HeadSink that collects the per-head read-outs layer by layer, or None"""
+        heads: a HeadSink that collects the per-head read-outs layer by layer, or None; attn_map: an AttnMapSink, likewise"""
         c, E = self.cfg, self.eps
         H, I, d, nq, nk = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"]
         M, rep = B * S, nq // nk
@@ -825,8 +908,9 @@ class LlamaLRP:
                     Gm = self._lin_bwd(Adn, Lw["wd"], ar.new("Gm", M, I))
                     ops.colsum_dot(st["m"], Gm, B, S, out=lat["R_mlp"][li])
             hs = None if heads is None else heads.layer(li)
+            am = None if attn_map is None else attn_map.layer(li)
             if full and not st.get("top", False):          # (Adn = Gs: eps = 0)
-                Gs = Adn = fused_layer_bwd(Gs, st, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv, self._qk_norm(Lw), hs)
+                Gs = Adn = fused_layer_bwd(Gs, st, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv, self._qk_norm(Lw), hs, am)
                 layer_R = layer_R + [ops.readout(st["h"], Gs, out=ar.f32(("rel", li), M))] if layer_relevance else None
                 if "resid" in latent:
                     ops.colsum_dot(st["h"], Gs, B, S, out=lat["R_resid"][li])
@@ -877,6 +961,10 @@ class LlamaLRP:
                     if hs is not None:
                         hs("out", st["o"], Gof)
             q, k, v = qkr[:, : nq * d], qkr[:, nq * d:], qkv[:, nqk:]
+            if am is not None and q_begin == 0:          # (Gho = 1/2 G_o on every efficient path: the epilogue's row scale, or attn_bwd_prep's factor)
+                am(q, k, v, Gho, st["lse"], 2.0, row_iv)
+            elif am is not None:
+                am.top(ar, q, k, v, Gho, st["lse"], 2.0, last, row_iv)
             k_t = q_t = Gho_t = None
             if self.attn_t:        # kernels that read head-transposed copies (fp32, head dims other than 128)
                 k_t = ops.transpose_heads(k, B, S, nk, d)
@@ -956,7 +1044,7 @@ class LlamaLRP:
         return Gs, layer_R, lat
 
     # ---------------------------------------------------------------------------------------------
-    def _run(self, input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, latent=frozenset(), heads=frozenset()):
+    def _run(self, input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, latent=frozenset(), heads=frozenset(), attn_map=(False, ())):
         """forward + backward + read-out on the current stream: library launches only, no host synchronisation (capturable)"""
         if emb is None:
             emb = self.embed.index_select(0, input_ids.reshape(-1))
@@ -968,7 +1056,11 @@ class LlamaLRP:
         if heads:
             c = self.cfg
             hs = HeadSink(heads, len(self.layers), B, S, c["n_heads"], c["head_dim"], self.device, float(c.get("attention_scaling", 1.0)) ** -2)
-        G, layer_R, lat = self.backward(fw, emb, idx, B, S, layer_relevance or "trace" in latent, seed=seed, latent=latent, heads=hs)
+        am = None
+        if attn_map[0] or attn_map[1]:
+            c = self.cfg
+            am = AttnMapSink(attn_map, len(self.layers), B, S, c["n_heads"], c["n_kv"], c["head_dim"], self.meta[-1], self.device)
+        G, layer_R, lat = self.backward(fw, emb, idx, B, S, layer_relevance or "trace" in latent, seed=seed, latent=latent, heads=hs, attn_map=am)
         out = explanation(emb, G, idx, fw["logits"], B, S, return_G)
         if layer_relevance:
             rows = [layer_R[0]] + [r.view(B, S).sum(1) for r in layer_R[1:]]
@@ -987,11 +1079,16 @@ class LlamaLRP:
             out.update({"R_head_" + n: t for n, t in hs.out.items()})
             if "out" in hs.out:
                 out["R_head"] = hs.out["out"].sum(-1)
+        if am is not None:
+            if am.total is not None:
+                out["R_attn"] = am.total
+            if am.per_head is not None:
+                out["R_attn_heads"], out["attn_map_heads"] = am.per_head, list(am.pairs)
         return out
 
     @torch.no_grad()
     def explain(self, input_ids=None, inputs_embeds=None, target=None, layer_relevance=False, return_G=False, lengths=None,
-                seed=None, graph=False, latent=None, heads=None):
+                seed=None, graph=False, latent=None, heads=None, attn_map=None):
         """input_ids [B,S] (or inputs_embeds [B,S,H]); target: None (arg-max of the last position) or
         int tensor [B].  Returns dict(idx [B], logit [B], R_tok [B,S] fp32, and optionally
         layer_R [L+1, B] (sum_h h (*) G_h at every residual-stream boundary) and G_emb [B,S,H]).
@@ -1013,7 +1110,14 @@ class LlamaLRP:
         output [L, B, n_heads, S]: R_head_out = sum_d o (*) G_o at the o projection's input, per query head and query position (and R_head
         [L, B, n_heads] = R_head_out.sum(-1): which heads of which layer carry the prediction); R_head_q / R_head_k / R_head_v = sum_d x (*) G_x
         at the attention's query / key / value input (after RoPE and Qwen3's head norm), k and v per QUERY head at the SOURCE position: which
-        tokens a head pulls its relevance from.  Pad columns under lengths are exactly 0; nothing else changes with it."""
+        tokens a head pulls its relevance from.  Pad columns under lengths are exactly 0; nothing else changes with it.
+        attn_map (optional): "sum", (layer, head) pairs, or an iterable mixing both -- the token-to-token attention relevance (DESIGN.md
+        section 12.2) R[i, j] = P[i, j] (G_o[i] . v[j]), `attn_weights * attn_weights.grad` of eager attention: how much relevance query
+        position i draws from source position j.  "sum": R_attn [L, B, S, S] fp32 over all query heads; pairs: R_attn_heads [n, B, S, S] in
+        request order and attn_map_heads, the pairs.  A row sums to R_head_out (1/2 of it is the uniform-rule share of P in P V); masked and pad
+        (i, j) are exactly 0; efficient placement only; nothing else changes with it."""
+        am = attn_map_request(attn_map, len(getattr(self, "layers", ())), self.cfg.get("n_heads", 0), self.cfg.get("head_dim"), self.dtype,
+                              getattr(self, "mode", "efficient"))
         hd = head_request(heads, self.cfg.get("head_dim"), self.dtype)
         lat = latent_request(latent, self.cfg["hidden"], self.cfg["inter"], self.dtype)
         B, S, emb, row_iv, idx = explain_inputs(input_ids, inputs_embeds, lengths, target, self.cfg["vocab"], self.max_seq, self.dtype,
@@ -1021,8 +1125,8 @@ class LlamaLRP:
         if inputs_embeds is None:
             input_ids = input_ids.to(self.device)
         if not graph:
-            return self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, lat, hd)
+            return self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, lat, hd, am)
         if emb is not None or lengths is not None or seed is not None or return_G:
             raise ValueError("graph=True takes input_ids only (no inputs_embeds / lengths / seed / return_G)")
-        return self._graphs((B, S, idx is not None, bool(layer_relevance), self.mode, tuple(sorted(lat)), tuple(sorted(hd))),
-                            lambda ids, idx_: self._run(ids, None, B, S, None, idx_, layer_relevance, False, None, lat, hd), input_ids, idx)
+        return self._graphs((B, S, idx is not None, bool(layer_relevance), self.mode, tuple(sorted(lat)), tuple(sorted(hd)), am),
+                            lambda ids, idx_: self._run(ids, None, B, S, None, idx_, layer_relevance, False, None, lat, hd, am), input_ids, idx)

@@ -889,6 +889,30 @@ def headdot(x, g, B, S, nh, rep, d, scale=1.0, rope=None, out=None):
     return out
 
 
+def attn_relmap(q, k, v, g, lse, B, S, Hq, Hkv, d, scale, heads=None, gscale=1.0, causal=True, row_iv=None, out=None):
+    """out[b, i, j] = gscale sum_{lo <= h < hi} P_h[i, j] (g_h[i] . v_{h // rep}[j])  ([B, S, S] fp32, every element written): the token-to-token
+    attention relevance `attn_weights * attn_weights.grad`, summed over the query heads heads = (lo, hi) (None: all of them).  q, g [B S, Hq d]
+    and k, v [B S, Hkv d] token-major with unit column stride (any row pitch), lse [B, Hq, S] as attn_fwd left it; g is the gradient at the o
+    projection's input (gscale = 2 for the dgrad epilogue's Gho).  bf16: d in {64, 128}; fp32: any d <= 256 that is a multiple of 4.
+    Masked (i, j) -- causal, row_iv -- are exactly 0.  Fixed-order fp32 sums, a prompt's result depends on its rows only."""
+    lo, hi = (0, Hq) if heads is None else (int(heads[0]), int(heads[1]))
+    M = q.shape[0]
+    for name, t, nh in (("q", q, Hq), ("k", k, Hkv), ("v", v, Hkv), ("g", g, Hq)):
+        if t.dim() != 2 or t.shape[0] != M or t.shape[1] != nh * d or t.stride(1) != 1:
+            raise ValueError(f"attn_relmap: {name} {tuple(t.shape)} must be [B S = {M}, {nh} * {d}] with contiguous rows")
+    if M != B * S or tuple(lse.shape) != (B, Hq, S) or not lse.is_contiguous():
+        raise ValueError(f"attn_relmap: {M} rows / lse {tuple(lse.shape)} where B S = {B * S} rows and a contiguous [{B}, {Hq}, {S}] lse are expected")
+    pq, pk, pv, pg, pl = p(q), p(k), p(v), p(g), p(lse)                 # (device tensors only: raises before anything is allocated)
+    out = torch.empty(B, S, S, device=q.device, dtype=torch.float32) if out is None else out
+    same(q, k, v, g)
+    f32(lse, out)
+    if tuple(out.shape) != (B, S, S) or not out.is_contiguous():
+        raise ValueError(f"attn_relmap: out must be a contiguous [{B}, {S}, {S}] tensor")
+    check(lib.lrp_attn_relmap(pq, pk, pv, pg, pl, p(out), M, B, S, Hq, Hkv, d, lo, hi, q.stride(0), k.stride(0), v.stride(0), g.stride(0),
+                              float(scale), float(gscale), int(causal), *_iv(row_iv, B, S), dt(q), stream()), "lrp_attn_relmap")
+    return out
+
+
 def argmax_rows(logits):
     B, V = logits.shape
     idx = torch.empty(B, device=logits.device, dtype=torch.int32)

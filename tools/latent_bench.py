@@ -9,7 +9,13 @@
   (3) lrp_headdot at B S = 8192 rows, 32 query heads of 128, bf16: rep = 1 (q, o) and rep = 4 (k, v over 8 kv heads), with and without the
       rotated form, the bytes the algorithm must read (x, g and the fp32 output) over the median time, next to lrp_colsum_dot in the same run;
   (4) the per-step overhead of each LlamaLRP.explain(heads=...) name, and of all four, against a plain explain() of the same process.
-usage: python tools/latent_bench.py [--heads] [--out FILE] [--layers 2] [--reps 20] [--rounds 5]"""
+  --attn-map: the token-to-token attention relevance maps instead (profiles/attn_map_bench.txt), B = 4, S = 2048,
+  32 / 8 heads of 128, bf16:
+  (5) lrp_attn_relmap alone (all 32 heads into one map, and one head), next to two yardsticks of the same process: lrp_attn_fwd at the same
+      shape (the same number of contractions) and a torch restatement that materialises [B, nq, S, S];
+  (6) the per-step overhead of explain(attn_map="sum") and of one (layer, head) pair against a plain explain() (--layers 32 for the figure
+      the design document quotes).
+usage: python tools/latent_bench.py [--heads | --attn-map] [--out FILE] [--layers 2] [--reps 20] [--rounds 5]"""
 import argparse
 import os
 import statistics
@@ -40,6 +46,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--heads", action="store_true", help="measure lrp_headdot and explain(heads=...) instead of the latent options")
+    ap.add_argument("--attn-map", action="store_true", help="measure lrp_attn_relmap and explain(attn_map=...) instead of the latent options")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("latent_bench needs a HIP device")
@@ -54,7 +61,7 @@ def main():
     # ---- (1) the kernel
     B, S = 4, 2048
     g = torch.Generator(device="cuda").manual_seed(0)
-    for N, pad in ((4096, 0), (14336, 64)):
+    for N, pad in () if a.attn_map else ((4096, 0), (14336, 64)):
         x = torch.randn(B * S, N + pad, generator=g, device="cuda").bfloat16()[:, :N]
         y = torch.randn(B * S, N + pad, generator=g, device="cuda").bfloat16()[:, :N]
         out = torch.empty(B, N, device="cuda")
@@ -84,6 +91,37 @@ def main():
                     f"best over 50 calls; {nbytes / 1e6:.0f} MB -> {nbytes / med / 1e6:.0f} GB/s median = {nbytes / med / 1e9 / 8.0:.2f} of 8 TB/s "
                     f"(best {nbytes / best / 1e6:.0f} GB/s)")
             del x, y
+    # ---- (5) the token-to-token kernel and its yardsticks
+    if a.attn_map:
+        nq, nk, d = 32, 8, 128
+        scale = d ** -0.5
+        q, gq = (torch.randn(B * S, nq * d, generator=g, device="cuda").bfloat16() for _ in range(2))
+        k, v = (torch.randn(B * S, nk * d, generator=g, device="cuda").bfloat16() for _ in range(2))
+        o, lse, out = torch.empty_like(q), torch.empty(B, nq, S, device="cuda"), torch.empty(B, S, S, device="cuda")
+        up = torch.ones(S, S, dtype=torch.bool, device="cuda").triu(1)
+
+        def restated():
+            hd = lambda t, nh: t.view(B, S, nh, d).transpose(1, 2)                    # noqa: E731
+            kh, vh = hd(k, nk).repeat_interleave(nq // nk, 1), hd(v, nk).repeat_interleave(nq // nk, 1)
+            P = torch.exp((hd(q, nq) @ kh.transpose(2, 3)).float() * scale - lse[..., None])
+            return (P * (hd(gq, nq) @ vh.transpose(2, 3)).float()).masked_fill_(up, 0.0).sum(1)
+
+        runs = (("lrp_attn_fwd (yardstick: the same number of contractions)", lambda: ops.attn_fwd(q, k, v, None, o, lse, B, S, nq, nk, d, scale)),
+                ("lrp_attn_relmap, 32 heads into one map", lambda: ops.attn_relmap(q, k, v, gq, lse, B, S, nq, nk, d, scale, out=out)),
+                ("lrp_attn_relmap, one head", lambda: ops.attn_relmap(q, k, v, gq, lse, B, S, nq, nk, d, scale, heads=(5, 6), out=out)),
+                ("torch restatement materialising [B, nq, S, S]", restated))
+        med = {}
+        for name, fn in runs:
+            for _ in range(3):
+                fn()
+            med[name], best = timed(fn, 20)
+            say(f"{name:62s}: {med[name] * 1e3:9.1f} us median, {best * 1e3:9.1f} us best over 20 calls  (bf16 B={B} S={S} nq={nq} nk={nk} d={d})")
+        km = med[runs[1][0]]
+        say(f"  lrp_attn_relmap / lrp_attn_fwd = {km / med[runs[0][0]]:.2f};  torch restatement / lrp_attn_relmap = {med[runs[3][0]] / km:.2f}; "
+            f"causal flops 2 x 2 B nq d S^2 / 2 = {2 * B * nq * d * S * S / 1e9:.0f} GF -> {2 * B * nq * d * S * S / km / 1e9:.0f} TF/s")
+        err = float((restated() - out.copy_(ops.attn_relmap(q, k, v, gq, lse, B, S, nq, nk, d, scale))).abs().max() / out.abs().max())
+        say(f"  the two agree to {err:.1e} of the largest value (the restatement's products are bf16 GEMM outputs)")
+        del q, gq, k, v, o, lse, out
     # ---- (2) the engine
     H, I, d, L = 4096, 14336, 128, a.layers
     cfg = dict(hidden=H, inter=I, n_layers=L, n_heads=32, n_kv=8, head_dim=d, vocab=4096, rope_theta=5e5, rms_eps=1e-5)
@@ -99,6 +137,8 @@ def main():
     kw = "latent"
     if a.heads:
         reqs, kw = dict(plain=None, out=("out",), q=("q",), k=("k",), v=("v",), all=E.HEADS), "heads"
+    if a.attn_map:
+        reqs, kw = dict(plain=None, sum="sum", pair=[(L // 2, 5)]), "attn_map"
     for lat in reqs.values():                                   # warm-up: every shape, every arena buffer
         for _ in range(2):
             eng.explain(ids, **{kw: lat})
@@ -117,6 +157,7 @@ def main():
             f"= {(m - base) / L * 1e3:7.1f} us per layer   [spread {min(ts[k]):.2f} .. {max(ts[k]):.2f}]")
     say(f"  arena after every request: {arena0 / 2**30:.2f} GiB" + (f"; outputs {L} x {B} x 32 x {S} fp32 = {L * B * 32 * S * 4 / 2**20:.0f} MiB per name"
                                                                     if a.heads else
+                                                                    f"; R_attn {L} x {B} x {S} x {S} fp32 = {L * B * S * S * 4 / 2**30:.2f} GiB" if a.attn_map else
                                                                     f" (kept m: {L} x {B * S} x {I} bf16 = {L * B * S * I * 2 / 2**30:.2f} GiB of it)"))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
