@@ -1104,30 +1104,6 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 
 }  // namespace
 
-// bf16, d in {64, 96, 128}: 32x32x16 MFMA kernels of attention32.hip (no head-transposed operands)
-int lrp_attn32_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq, int Hkv, int d, int64_t ldq,
-                   int64_t ldk, int64_t ldv, int64_t ldo, float scale, int causal, int window, int q_begin, const int* row_lo,
-                   const int* row_hi, hipStream_t st);
-int lrp_attn32_dq(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dq, int B,
-                  int S, int Hq, int Hkv, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddq, float scale,
-                  float eps_mask, float eps_qk, int causal, int window, int q_begin, const int* row_lo, const int* row_hi,
-                  hipStream_t st, const void* o = nullptr, int64_t ldo = 0, float* Dout = nullptr, const float* cos_t = nullptr,
-                  const float* sin_t = nullptr);
-int lrp_attn32_dkv(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dk,
-                   void* dv, int B, int S, int Hq, int Hkv, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddk,
-                   int64_t lddv, float scale, float eps_mask, float eps_qk, int causal, int window, int q_begin,
-                   const int* row_lo, const int* row_hi, hipStream_t st);
-int lrp_attn32_fwd_d256(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq, int Hkv, int64_t ldq,
-                        int64_t ldk, int64_t ldv, int64_t ldo, float scale, int causal, int window, int q_begin, const int* row_lo,
-                        const int* row_hi, hipStream_t st);
-int lrp_attn32_dq_d256(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dq, int B,
-                       int S, int Hq, int Hkv, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddq, float scale,
-                       float eps_mask, float eps_qk, int causal, int window, int q_begin, const int* row_lo, const int* row_hi,
-                       hipStream_t st);
-int lrp_attn32_dkv_d256(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dk,
-                        void* dv, int B, int S, int Hq, int Hkv, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddk,
-                        int64_t lddv, float scale, float eps_mask, float eps_qk, int causal, int window, int q_begin,
-                        const int* row_lo, const int* row_hi, hipStream_t st);
 // bf16, d in {64, 96, 128, 256}: the 32x32x16 / transpose-read kernels of attention32.hip (no head-transposed operands)
 static inline bool use_attn32(int dtype, int d) { return dtype == LRP_BF16 && (d == 64 || d == 96 || d == 128 || d == 256); }
 extern "C" int lrp_attn_needs_transposed(int dtype, int d) { return use_attn32(dtype, d) ? 0 : 1; }
@@ -1135,7 +1111,7 @@ extern "C" int lrp_attn_needs_transposed(int dtype, int d) { return use_attn32(d
 #define ATT_DISPATCH_D(T, d, ...)                                   \
     if ((size_t)d * sizeof(T) < 64) return LRP_ESHAPE;              \
     switch (d) {                                                    \
-        case 16: { constexpr int DD = (sizeof(T) == 4) ? 16 : 32; __VA_ARGS__ } break;      \
+        case 16: if constexpr (sizeof(T) == 4) { constexpr int DD = 16; __VA_ARGS__ } break;   /* fp32 only: the line above refused bf16 */ \
         case 32: { constexpr int DD = 32; __VA_ARGS__ } break;      \
         case 64: { constexpr int DD = 64; __VA_ARGS__ } break;      \
         case 128: { constexpr int DD = 128; __VA_ARGS__ } break;    \
@@ -1226,19 +1202,14 @@ static int attn_dq_t(const void* q, const void* k, const void* v, const void* kt
             if constexpr (DD <= 128) {
                 const size_t lds = 2 * (3 * (size_t)128 * DD);
                 dim3 grid(xcd_group_grid(B * Hkv, (Hq / Hkv) * ((S + 127) / 128)));
-                if (eps_mask != 0.f || eps_qk != 0.f) {
-                    auto kern = attn_bwd_dq_v2_kernel<T, DD, true>;
+                auto launch = [&](auto kern) {
                     set_lds(kern, lds);
                     hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, (const T*)q, (const T*)k, (const T*)v, (const T*)kt,
                                        (const T*)gho, lse, D, (T*)dq, S, Hq, Hkv, ldq, ldk, ldv, ldt, ldg, lddq, scale, eps_mask,
                                        eps_qk, causal, window, B, q_begin, row_lo, row_hi);
-                } else {
-                    auto kern = attn_bwd_dq_v2_kernel<T, DD, false>;
-                    set_lds(kern, lds);
-                    hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, (const T*)q, (const T*)k, (const T*)v, (const T*)kt,
-                                       (const T*)gho, lse, D, (T*)dq, S, Hq, Hkv, ldq, ldk, ldv, ldt, ldg, lddq, scale, eps_mask,
-                                       eps_qk, causal, window, B, q_begin, row_lo, row_hi);
-                }
+                };
+                if (eps_mask != 0.f || eps_qk != 0.f) launch(attn_bwd_dq_v2_kernel<T, DD, true>);
+                else launch(attn_bwd_dq_v2_kernel<T, DD, false>);
             }
         })
         return lrp_check_launch();
@@ -1310,19 +1281,14 @@ static int attn_dkv_t(const void* q, const void* k, const void* v, const void* q
             if constexpr (DD <= 128) {
                 const size_t lds = 2 * (4 * (size_t)128 * DD + 512);
                 dim3 grid(xcd_group_grid(B * Hq, (S + 127) / 128));
-                if (eps_mask != 0.f || eps_qk != 0.f) {
-                    auto kern = attn_bwd_dkv_v2_kernel<T, DD, true>;
+                auto launch = [&](auto kern) {
                     set_lds(kern, lds);
                     hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, (const T*)q, (const T*)k, (const T*)v, (const T*)qt,
                                        (const T*)gho, (const T*)ghot, lse, D, (T*)dk, (T*)dv, S, Hq, Hkv, ldq, ldk, ldv, ldt,
                                        ldg, lddk, lddv, scale, eps_mask, eps_qk, causal, window, B, q_begin, row_lo, row_hi);
-                } else {
-                    auto kern = attn_bwd_dkv_v2_kernel<T, DD, false>;
-                    set_lds(kern, lds);
-                    hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, (const T*)q, (const T*)k, (const T*)v, (const T*)qt,
-                                       (const T*)gho, (const T*)ghot, lse, D, (T*)dk, (T*)dv, S, Hq, Hkv, ldq, ldk, ldv, ldt,
-                                       ldg, lddk, lddv, scale, eps_mask, eps_qk, causal, window, B, q_begin, row_lo, row_hi);
-                }
+                };
+                if (eps_mask != 0.f || eps_qk != 0.f) launch(attn_bwd_dkv_v2_kernel<T, DD, true>);
+                else launch(attn_bwd_dkv_v2_kernel<T, DD, false>);
             }
         })
         return lrp_check_launch();

@@ -14,7 +14,7 @@
 //     entirely visible / entirely masked takes a wave-uniform branch: no per-element mask arithmetic on interior tiles.
 // LDS tile: [64 rows][256 B], 16-byte chunk c of row r stored at chunk c ^ rot(r), rot(r) = ((r&3)<<2)|((r>>2)&3): the
 // ds_read_b128 row fragments (16 lanes = 16 distinct rows) and the transpose reads (4 consecutive rows x 64 B per 32 lanes)
-// are both conflict-free under it.  Direct-to-LDS staging (global_load_lds_dwordx4), swizzle on the source address, two
+// are both conflict-free under it.  Direct-to-LDS staging (buffer_load_dwordx4 .. lds), swizzle on the source address, two
 // stages, one barrier per 64-row tile.
 #include "common.hpp"
 
@@ -26,10 +26,7 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef const __attribute__((address_space(1))) void* glb_ptr_t;
 
 constexpr int NW = 8;              // waves per workgroup of the dK/dV kernel (256 keys)
-#ifndef A32_NWQ
-#define A32_NWQ 4
-#endif
-constexpr int NWQ = A32_NWQ;       // waves per workgroup of the forward / dQ kernels: 128 queries, TWO workgroups per CU, so that
+constexpr int NWQ = 4;             // waves per workgroup of the forward / dQ kernels: 128 queries, TWO workgroups per CU, so that
                                    // one workgroup's prologue / store tail and barrier waits run under the other's MFMAs
 constexpr int CT = 64;             // column-side rows per tile
 constexpr int KP = 256;            // bytes per LDS tile row: the head-dim-128 image for EVERY head dim DH in {64, 96, 128} (16-byte chunks
@@ -61,33 +58,16 @@ LRP_DEVICE bool xcd_item_major_decode(int L, int ngroups, int per_group, int& gr
     return group < ngroups;
 }
 
-// stage a [64 rows][256 B] tile of a token-major operand: 16 one-KiB groups of 4 rows, 16 / NWV per wave.
-// A32_BUFFER_STAGING (default): buffer_load_dwordx4 .. lds -- ONE per-lane byte offset (row (l >> 4) of the group, swizzled chunk; the
+// stage a [64 rows][256 B] tile of a token-major operand: 16 one-KiB groups of 4 rows, 16 / NWV per wave, each one
+// buffer_load_dwordx4 .. lds -- ONE per-lane byte offset (row (l >> 4) of the group, swizzled chunk; the
 // group index only enters the chunk through grp & 3 = wave & 3), the group's first row in the scalar offset, rows >= S read as zero
 // through num_records (a zero K / V / Q / Gho row contributes nothing: masked keys, and dS^T Q = P^T Gho = 0 for a zero query row).
 // A global_load_lds piece with its 64-bit per-lane address costs ~80-120 cycles at issue, a buffer piece ~35 (profiles/r03_gemm_experiments.txt).
-#ifndef A32_BUFFER_STAGING
-#define A32_BUFFER_STAGING 1
-#endif
-// dK / dV kernel (d <= 128) build switches, kept for A/B builds (tools/ab): A32_DKV_P1 = fragment read-ahead of the S^T / dP^T phase in
-// steps (0: the round 2-4 form), A32_DKV_EW = 1: one mask branch per 4-query group in the element-wise phase
-#ifndef A32_DKV_P1
-#define A32_DKV_P1 2
-#endif
-#ifndef A32_DKV_EW
-#define A32_DKV_EW 1
-#endif
-// A32_DKV_ORDER = 1: workgroups walk the (head, key block) grid key-block-major within a XCD (heaviest key blocks of ALL heads first)
-#ifndef A32_DKV_ORDER
-#define A32_DKV_ORDER 1
-#endif
-
 // Head dims below 128: a lane whose source chunk lies past the head (chunk >= DH / 8) gets an offset beyond num_records -- the buffer
 // unit returns zero without a memory request; its LDS slot is never read.
 constexpr int A32_OOB = 0x40000000;
 template <int NWV = NW, int DH = 128>
 LRP_DEVICE void stage_tile(const bf16_t* base, int64_t ld, int row0, int S, char* lds, int wave, int lane) {
-#if A32_BUFFER_STAGING
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, (int)(((int64_t)(S - 1) * ld + DH) * 2), 0x00020000);
     const int rl = lane >> 4, slot = lane & 15;
     const int chunk_ = slot ^ ((rl << 2) | (wave & 3));
@@ -97,18 +77,6 @@ LRP_DEVICE void stage_tile(const bf16_t* base, int64_t ld, int row0, int S, char
         const int grp = g * NWV + wave;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(lds + grp * 1024), 16, voff, (int)((int64_t)(row0 + grp * 4) * ld * 2), 0, 0);
     }
-#else
-#pragma unroll
-    for (int g = 0; g < 16 / NWV; ++g) {
-        const int grp = g * NWV + wave;
-        const int row = grp * 4 + (lane >> 4), slot = lane & 15;
-        const int chunk = slot ^ rot4(row);
-        int gr = row0 + row;
-        gr = gr < S ? gr : S - 1;
-        if (chunk * 8 < DH)
-            __builtin_amdgcn_global_load_lds((glb_ptr_t)(base + (int64_t)gr * ld + chunk * 8), (lds_ptr_t)(lds + grp * 1024), 16, 0, 0);
-    }
-#endif
 }
 // 64 fp32 row statistics -> lds[0..63]
 LRP_DEVICE void stage_stats(const float* base, int r0, int S, char* lds, int lane) {
@@ -198,8 +166,10 @@ template <int ND, int N> LRP_DEVICE void wait_tr2(u32x2 (&t)[NDX][2], u32x2 (&u)
 // wave already running at close to their single-wave time, i.e. the two waves of a SIMD are complementary; what is left is the
 // per-wave cost of the element-wise phase (VALU issue beside the other wave's MFMAs), the LDS-DMA issue cost of the staging
 // loads and the per-workgroup prologue / store tail.
-// dev builds only (-DA32_TIMELINE, tools/attn_timeline.py): per-wave shader-clock totals of the dQ kernel's loop segments, written
-// over the first words of the wave's first output row
+// A32_TIMELINE -- the one build switch of this file.  It is instrumentation, not a fork between two kernels: undefined (every shipped
+// build) A32_TS and the #ifdef A32_TIMELINE blocks compile to nothing; with -DA32_TIMELINE the dQ and dK / dV (d <= 128) kernels add up
+// per-wave shader-clock totals of their loop segments and write them over the first words of the wave's first output row.  Built only by
+// tools/attn_timeline.py, tools/attn_dkv_timeline.py and tools/attn_dkv_only.py.
 #ifdef A32_TIMELINE
 #define A32_TS(slot)                                                          \
     {                                                                         \
@@ -779,11 +749,7 @@ __global__ __launch_bounds__(512, 2) void dkv_kernel(
     const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int bh, kblk;
-#if A32_DKV_ORDER
     if (!xcd_item_major_decode(blockIdx.x, B * Hq, (S + BK - 1) / BK, bh, kblk)) return;
-#else
-    if (!xcd_group_decode(blockIdx.x, B * Hq, (S + BK - 1) / BK, bh, kblk)) return;
-#endif
     const int b = bh / Hq, h = bh % Hq, hk = h / (Hq / Hkv);
     const int k0 = kblk * BK, kw = k0 + wave * 32, ki = kw + l31;
     const bf16_t* qb_ = q + (int64_t)b * S * ldq + (int64_t)h * DH;
@@ -801,7 +767,6 @@ __global__ __launch_bounds__(512, 2) void dkv_kernel(
     char* sVw = smem + 2 * STAGE + wave * VROWS;
     {
         const bf16_t* vbase = v + (int64_t)b * S * ldv + (int64_t)hk * DH;
-#if A32_BUFFER_STAGING
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)vbase, 0, (int)(((int64_t)(S - 1) * ldv + DH) * 2), 0x00020000);
         const int rl = lane >> 4, slot = lane & 15;
 #pragma unroll
@@ -810,16 +775,6 @@ __global__ __launch_bounds__(512, 2) void dkv_kernel(
             const int voff = (DH == 128 || chunk_ < DH / 8) ? (int)(rl * ldv * 2) + (chunk_ << 4) : A32_OOB;
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_ptr_t)(sVw + g * 1024), 16, voff, (int)((int64_t)(kw + g * 4) * ldv * 2), 0, 0);
         }
-#else
-#pragma unroll
-        for (int g = 0; g < 8; ++g) {
-            const int row = g * 4 + (lane >> 4), slot = lane & 15;
-            int gr = kw + row;
-            gr = gr < S ? gr : S - 1;
-            if ((slot ^ rot4(row)) * 8 < DH)
-                __builtin_amdgcn_global_load_lds((glb_ptr_t)(vbase + (int64_t)gr * ldv + ((slot ^ rot4(row)) * 8)), (lds_ptr_t)(sVw + g * 1024), 16, 0, 0);
-        }
-#endif
     }
     f32x16 dkacc[ND32], dvacc[ND32];
 #pragma unroll
@@ -886,51 +841,22 @@ __global__ __launch_bounds__(512, 2) void dkv_kernel(
             // ---- S^T and dP^T
             f32x16 st = zero16(), dp = zero16();
             f32x4 sl[2], sd[2];                                         // lse / D of the queries 8 i + 4 hi + 0..3, double-buffered
-#if A32_DKV_P1 == 0
-            // (round 2-4 form, kept for A/B: the contractions one after the other, fragment reads ONE step = one MFMA = 32 pipe cycles ahead)
-            bf16x8 fq[2], fg[2], fv[2];
-            A32_RD128(fq[0], arm0, QO);
-            sfor<0, NK>([&](auto ksc) {
-                constexpr int ks = decltype(ksc)::value, cu = ks & 1, nx = cu ^ 1;
-                if constexpr (ks + 1 < NK) {
-                    { const uint32_t aq = frag_addr<ks + 1>(arm0); A32_RD128(fq[nx], aq, QO); }
-                    A32_WAIT(1, "+v"(fq[cu]));
-                } else {
-                    A32_RD128(fg[0], arm0, QO + TILE);
-                    A32_RD128(fv[0], avw0, 0);
-                    A32_WAIT(2, "+v"(fq[cu]));
-                }
-                st = mfma32(fq[cu], kf[ks], st);
-                A32_FENCE();
-            });
-            sfor<0, NK>([&](auto ksc) {
-                constexpr int ks = decltype(ksc)::value, cu = ks & 1, nx = cu ^ 1;
-                if constexpr (ks + 1 < NK) {
-                    { const uint32_t ag = frag_addr<ks + 1>(arm0); A32_RD128(fg[nx], ag, QO + TILE); }
-                    { const uint32_t av = frag_addr<ks + 1>(avw0); A32_RD128(fv[nx], av, 0); }
-                    A32_WAIT(2, "+v"(fg[cu]), "+v"(fv[cu]));
-                } else {
-                    A32_RD128(sl[0], ast, SO); A32_RD128(sd[0], ast, SO + 256);
-                    A32_WAIT(2, "+v"(fg[cu]), "+v"(fv[cu]));
-                }
-                dp = mfma32(fg[cu], fv[cu], dp);
-                A32_FENCE();
-            });
-#else
-            // round 5: S^T and dP^T step by step side by side (two independent accumulator chains: the MFMAs of a step issue back to back) with
-            // the step's three fragments -- Q, Gho, V -- read A32_DKV_P1 steps = 2 A32_DKV_P1 MFMAs = 64 A32_DKV_P1 pipe cycles ahead through a
-            // ring of A32_DKV_P1 + 1 slots.  With one MFMA of cover (32 cycles) every contraction step waited out the LDS latency: ~100+ cycles
-            // per MFMA in this phase, on BOTH waves of the SIMD at once (ISA: ds_read, s_waitcnt lgkmcnt(1), v_mfma per step).  The ring costs
-            // no registers at the kernel's peak: the transpose-read groups, P / dS operands and statistics of phase C are dead here.
-            constexpr int PD = A32_DKV_P1, RS = PD + 1;
+            // S^T and dP^T step by step side by side (two independent accumulator chains: the MFMAs of a step issue back to back) with the step's
+            // three fragments -- Q, Gho, V -- read PD steps = 2 PD MFMAs = 64 PD pipe cycles ahead through a ring of PD + 1 slots.  With one MFMA
+            // of cover (32 cycles; the contractions one after the other, reads one step ahead -- the form of rounds 2-4) every contraction step
+            // waited out the LDS latency: ~100+ cycles per MFMA in this phase, on BOTH waves of the SIMD at once (ISA: ds_read, s_waitcnt
+            // lgkmcnt(1), v_mfma per step); three steps ahead spills (profiles/r05_attention_experiments.txt).  The ring costs no registers at
+            // the kernel's peak: the transpose-read groups, P / dS operands and statistics of phase C are dead here.
+            constexpr int PD = 2, RS = PD + 1;
             bf16x8 fq[RS], fg[RS], fv[RS];
             static_assert(PD < NK, "read-ahead deeper than the contraction");
+            static_assert(PD == 2, "the prologue below issues the reads of steps 0 .. PD - 1");
 #define A32_P1_PRO(pk)                                                                                          \
-    if constexpr (PD > (pk)) {                                                                                  \
+    {                                                                                                           \
         const uint32_t aq = frag_addr<(pk)>(arm0), av = frag_addr<(pk)>(avw0);                                  \
         A32_RD128(fq[pk], aq, QO); A32_RD128(fg[pk], aq, QO + TILE); A32_RD128(fv[pk], av, 0);                  \
     }
-            A32_P1_PRO(0) A32_P1_PRO(1) A32_P1_PRO(2) A32_P1_PRO(3)
+            A32_P1_PRO(0) A32_P1_PRO(1)
 #undef A32_P1_PRO
             sfor<0, NK>([&](auto ksc) {
                 constexpr int ks = decltype(ksc)::value, cu = ks % RS, nx = (ks + PD) % RS;
@@ -949,7 +875,6 @@ __global__ __launch_bounds__(512, 2) void dkv_kernel(
                 dp = mfma32(fg[cu], fv[cu], dp);
                 A32_FENCE();
             });
-#endif
             A32_TS(1);                                                   // 1: S^T / dP^T phase
             // ---- element-wise work and the dV / dK contractions, one 16-query group j at a time:
             //   B(j): P and dS of the group's 8 accumulator registers (statistics double-buffered, one read pair ahead);
@@ -989,24 +914,8 @@ __global__ __launch_bounds__(512, 2) void dkv_kernel(
                 } else {
                     A32_WAIT(0, "+v"(sl[cu]), "+v"(sd[cu]), A32_TIE(0));
                 }
-#if A32_DKV_EW == 0
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int r = 4 * i + e;
-                    const float s_raw = st[r];
-                    float p = fast_exp2(__builtin_fmaf(s_raw, c1, -(sl[cu][e] * LRP_LOG2E)));
-                    if (masked) {
-                        const int qi = qq0 + 8 * i + 4 * hi + e;
-                        int ivlo = 0, ivhi = S;
-                        if constexpr (IV) { if (rlo_b != nullptr && qi < S) { ivlo = rlo_b[qi]; ivhi = rhi_b[qi]; } }
-                        p = ((qi < S) & visible(qi, ki, S, causal, window, ivlo, ivhi)) ? p : 0.f;
-                    }
-                    pf[i >> 1][4 * (i & 1) + e] = (bf16_t)p;
-                    df[i >> 1][4 * (i & 1) + e] = (bf16_t)lrp_ds<EXPL>(s_raw, p, dp[r], sd[cu][e], scale, eps_mask, eps_qk);
-                }
-#else
-                // round 5: ONE wave-uniform branch per 4-query group instead of one per element (the per-element form compiled to 16 taken
-                // s_cbranch per 32 x 32 block on the interior fast path, each between an exp2 and its consumers)
+                // ONE wave-uniform branch per 4-query group, not one per element (the per-element form compiled to 16 taken s_cbranch per
+                // 32 x 32 block on the interior fast path, each between an exp2 and its consumers: profiles/r05_attention_experiments.txt)
                 float pe[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) pe[e] = fast_exp2(__builtin_fmaf(st[4 * i + e], c1, -(sl[cu][e] * LRP_LOG2E)));
@@ -1025,7 +934,6 @@ __global__ __launch_bounds__(512, 2) void dkv_kernel(
                     pf[i >> 1][4 * (i & 1) + e] = (bf16_t)pe[e];
                     df[i >> 1][4 * (i & 1) + e] = (bf16_t)lrp_ds<EXPL>(st[r], pe[e], dp[r], sd[cu][e], scale, eps_mask, eps_qk);
                 }
-#endif
                 A32_FENCE();
             };
             // group g = (j, db) = (g / ND32, g % ND32) uses register slot g & 1; its reads are issued one group ahead
@@ -1515,11 +1423,7 @@ __global__ __launch_bounds__(NW2 * 64, 1) void dkv256_kernel(
     const int lane = threadIdx.x & 63, l31 = lane & 31, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     int bh, kblk;
-#if A32_DKV_ORDER
     if (!xcd_item_major_decode(blockIdx.x, B * Hq, (S + BK - 1) / BK, bh, kblk)) return;       // heaviest key blocks of all heads first (see above)
-#else
-    if (!xcd_group_decode(blockIdx.x, B * Hq, (S + BK - 1) / BK, bh, kblk)) return;
-#endif
     const int b = bh / Hq, h = bh % Hq, hk = h / (Hq / Hkv);
     const int k0 = kblk * BK, kw = k0 + wave * 32, ki = kw + l31;
     const bf16_t* qb_ = q + (int64_t)b * S * ldq + (int64_t)h * D2;

@@ -251,3 +251,29 @@ LRP_DEVICE int xcd_remap(int bid, int nwg) {
     const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return base + loc;
 }
+
+// ---- entry points of attention32.hip, called by the dispatchers of attention.hip: bf16 on the 32x32x16 MFMA kernels, no head-transposed
+// operands; d in {64, 96, 128}, and the _d256 forms.  lrp_attn32_dq with o != NULL computes D from (gho, o) and writes it to Dout.
+int lrp_attn32_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq, int Hkv, int d, int64_t ldq,
+                   int64_t ldk, int64_t ldv, int64_t ldo, float scale, int causal, int window, int q_begin, const int* row_lo,
+                   const int* row_hi, hipStream_t st);
+int lrp_attn32_dq(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dq, int B,
+                  int S, int Hq, int Hkv, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddq, float scale,
+                  float eps_mask, float eps_qk, int causal, int window, int q_begin, const int* row_lo, const int* row_hi,
+                  hipStream_t st, const void* o = nullptr, int64_t ldo = 0, float* Dout = nullptr, const float* cos_t = nullptr,
+                  const float* sin_t = nullptr);
+int lrp_attn32_dkv(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dk,
+                   void* dv, int B, int S, int Hq, int Hkv, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddk,
+                   int64_t lddv, float scale, float eps_mask, float eps_qk, int causal, int window, int q_begin,
+                   const int* row_lo, const int* row_hi, hipStream_t st);
+int lrp_attn32_fwd_d256(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq, int Hkv, int64_t ldq,
+                        int64_t ldk, int64_t ldv, int64_t ldo, float scale, int causal, int window, int q_begin, const int* row_lo,
+                        const int* row_hi, hipStream_t st);
+int lrp_attn32_dq_d256(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dq, int B,
+                       int S, int Hq, int Hkv, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddq, float scale,
+                       float eps_mask, float eps_qk, int causal, int window, int q_begin, const int* row_lo, const int* row_hi,
+                       hipStream_t st);
+int lrp_attn32_dkv_d256(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dk,
+                        void* dv, int B, int S, int Hq, int Hkv, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddk,
+                        int64_t lddv, float scale, float eps_mask, float eps_qk, int causal, int window, int q_begin,
+                        const int* row_lo, const int* row_hi, hipStream_t st);

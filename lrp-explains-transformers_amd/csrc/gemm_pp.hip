@@ -43,24 +43,20 @@
 // the weight is streamed exactly once and the tile count alone would leave most CUs idle (lrp_gemm_skinny, reduced by a second kernel).
 // Barriers: L | barrier | M | barrier per phase; group 1 executes ONE extra barrier up front, which puts it half a phase behind
 // for the whole kernel (and group 0 one at the very end to balance the count).
-// Round 5 -- PERSISTENT tile walk (PP_PERSIST, default on): the launch is min(tiles, CUs) workgroups; workgroup w computes the tiles w, w + grid,
-// w + 2 grid, ... (the same tile every CU got from the dispatcher before: block b runs on XCD b % 8 and the XCD remap keeps the 32 tiles a XCD
-// works on at any time a compact group).  What it buys: the K loop's prologue loads of the NEXT tile (14 LDS-DMA pieces per wave into the two
-// buffers the finished K loop no longer reads) are issued BEFORE the epilogue's stores, so their HBM / L2 latency -- paid by all 256 CUs at once
-// at every round boundary of the non-persistent launch, together with the dispatch of a fresh 512-thread, 128-KiB workgroup -- runs under the
-// store phase (and, in the fused down-projection dgrad, under its gu reads).  LDS safety: group 0 reaches that point one interval ahead of group 1,
-// which by then has finished every read of the shared B rows (B fragments are read in phase (t, 0) only) and otherwise reads only its OWN A rows,
+// Persistent tile walk: the launch is min(tiles, CUs) workgroups; workgroup w computes the tiles w, w + grid, w + 2 grid, ... (the same tile every
+// CU would get from the dispatcher in a one-tile-per-workgroup launch: block b runs on XCD b % 8 and the XCD remap keeps the 32 tiles a XCD
+// works on at any time a compact group); split-K launches are not clamped, each of their workgroups computes one tile of one slab.  What it
+// buys: the K loop's prologue loads of the NEXT tile (14 LDS-DMA pieces per wave into the two buffers the finished K loop no longer reads) are
+// issued BEFORE the epilogue's stores, so their HBM / L2 latency -- paid by all 256 CUs at once at every round boundary of a
+// one-tile-per-workgroup launch, together with the dispatch of a fresh 512-thread, 128-KiB workgroup -- runs under the store phase (and, in the
+// fused down-projection dgrad, under its gu reads).  LDS safety: group 0 reaches that point one interval ahead of group 1, which by then has finished every read of the shared B rows (B fragments are read in phase (t, 0) only) and otherwise reads only its OWN A rows,
 // which only its own waves re-stage.  vmcnt counts loads and stores in issue order on gfx9, so "the first two staging units of the new tile have
 // landed" is vmcnt(8 + stores issued since) -- the stores themselves are never waited for.
-// Measured (profiles/r05_gemm_experiments.txt): +0.8 % on the seven Llama shapes, +1.1 % on the short-K SigLIP / Gemma-3 shapes in the isolated A/B,
-// within noise in situ -- the per-tile prologue / dispatch cost the round-4 notes hoped to recover (3-15 %) is ~1 %.  A staggered first round
-// (workgroups starting up to 17 us apart to de-phase the CUs' epilogue bursts) changed nothing and was removed: the fused epilogues are bound by
-// their own VALU issue (see gated_bwd_pair_bf16 in common.hpp), not by a shared HBM burst.
+// Measured against the one-tile-per-workgroup launch (profiles/r05_gemm_experiments.txt): +0.8 % on the seven Llama shapes, +1.1 % on the short-K
+// SigLIP / Gemma-3 shapes in the isolated A/B, within noise in situ -- the per-tile prologue / dispatch cost the round-4 notes hoped to recover
+// (3-15 %) is ~1 %.  A staggered first round (workgroups starting up to 17 us apart to de-phase the CUs' epilogue bursts) changed nothing and was
+// removed: the fused epilogues are bound by their own VALU issue (see gated_bwd_pair_bf16 in common.hpp), not by a shared HBM burst.
 #include "common.hpp"
-
-#ifndef PP_PERSIST
-#define PP_PERSIST 1
-#endif
 
 namespace {
 
@@ -232,7 +228,8 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(
     auto issue_prologue = [&]() { stage_A(0, 0, 0); stage_B(0, 0); stage_A(1, 0, 0); stage_A(0, 1, 1); stage_B(1, 1); };
     issue_prologue();
     PP_VMWAIT(8);
-    // persistent walk: one iteration per tile (PP_PERSIST 0, split-K slabs and the timeline build: exactly one)
+    // persistent walk: one iteration per tile of this workgroup (exactly one for split-K slabs and for grids of at most one tile per workgroup,
+    // i.e. tiles <= CUs: the launch gives those gridDim.x = tiles)
     for (;;) {
     const int em0 = m0, en0 = n0;                                     // this tile = the epilogue's tile (m0 / n0 move on to the next one after the K loop)
     // epilogue coordinates.  D = mfma(Bfrag, Afrag): lane l holds C[m = .. + 16 i + (l & 15)][n = .. + 16 j + 4 (l >> 4) + e] in acc[a][i][j][e]
@@ -394,7 +391,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(
         load_rs();
         if (full) { issue_res(0, rpre[0]); issue_res(1, rpre[1]); }
     }
-#if PP_PERSIST
     if (tile + (int)gridDim.x < ntiles) {
         tile += gridDim.x;
         int tm, tn;
@@ -405,7 +401,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(
         set_soB(n0);
         issue_prologue();
     }
-#endif
     {
     // ---- epilogue
     const bool vec4 = ((ldc & 3) == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0);
@@ -755,12 +750,10 @@ int launch_pp_t(const void* A, const void* B, void* C, const void* bias, int M, 
                 int splits, int kt_per_split, int64_t slab_stride, PPEpi ep, hipStream_t st) {
     const int tiles_m = (M + 255) / 256, tiles_n = (N + 255) / 256;
     int gx = tiles_m * tiles_n;
-#if PP_PERSIST
     if (splits == 1) {
         const int ncu = lrp_num_cus();
         if (gx > ncu) gx = ncu;
     }
-#endif
     dim3 grid(gx, splits), block(512);
     const size_t lds = 4 * (size_t)PP_OPND;
     auto kern = gemm_pp_kernel<TO, NN, EPI, ACT, SK, LEAN, RS>;

@@ -98,7 +98,7 @@ def weights_from_hf(model):
     return config_from_hf(model.config), W
 
 
-PITCH_PAD = True          # module attribute, not an environment knob: tools/r3_ab_bench.sh-style A/B scripts set engine.PITCH_PAD = False
+PITCH_PAD = True          # module attribute, not an environment knob: A/B runs set `engine.PITCH_PAD = False`
 
 
 def pitch_pad(cols, elem_size):
