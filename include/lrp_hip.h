@@ -272,7 +272,8 @@ int lrp_gated_act_bwd_il(const void* Gm, const void* gu, void* Agu, int M, int I
  *   { cg x 4 | cu x 4 } of intermediate indices 4 t .. 4 t + 3 at columns 8 t .. 8 t + 7 of the row.
  *   rs (may be NULL): fp32 [M], the accumulators of the forward are scaled by rs[m] first (K1n below: the folded RMSNorm's 1 / rms).
  *   lrp_gemm_gated_coef_ok(M, I, H, ldx, ldwgu, lda, ldwd, act, dtype) -> 1 when BOTH launches are problems the fused epilogues take (bf16,
- *   I % 32 == 0, >= 190 tiles of 256 x 256 each, SiLU / tanh-GELU); the two entry points return LRP_ESHAPE otherwise (no fallback inside). */
+ *   I % 32 == 0, >= 190 tiles of 256 x 256 each, SiLU / tanh-GELU); the two entry points return LRP_ESHAPE otherwise (no fallback inside).
+ *   coef, m and Agu are stored / loaded 16 bytes at a time: base pointers 16-byte aligned, ldcoef / ldm / ldagu multiples of 8 (LRP_EALIGN). */
 int lrp_gemm_gated_coef_ok(int M, int I, int H, int64_t ldx, int64_t ldwgu, int64_t lda, int64_t ldwd, int act, int dtype);
 int lrp_gemm_gated_fwd_coef(const void* x, const void* Wgu, const float* rs, void* coef, void* m, int M, int I, int K, int64_t ldx, int64_t ldw,
                             int64_t ldcoef, int64_t ldm, float eps_g, float eps_lin, int act, int dtype, void* stream);
@@ -313,7 +314,8 @@ int lrp_gemm_nt_rs(const void* x, const void* W, const float* rs, void* out, int
  * (apply_rotary_pos_emb: q cos + rotate_half(q) sin; constant tables, un-patched in lxt.efficient; explicit form lxt/explicit/models/llama.py:226-260)
  * applied to the q / k head columns [0, rope_cols) in the epilogue, in fp32 on the un-rounded accumulators; columns >= rope_cols (v) only take the
  * row scale.  cos / sin: fp32 [>= seq, 128], row p = position p (both halves of a row equal); the position of output row m is m % seq.  Heads of
- * 128 columns, M and N multiples of 256, the 256 x 256 ping-pong kernel only: lrp_gemm_nt_rs_rope_ok() -> 1 when the entry point takes the problem,
+ * 128 columns (rope_cols any multiple of 128: "rotate" is decided per head, so a 256-column tile may hold the last k head and the first v head),
+ * M and N multiples of 256, the 256 x 256 ping-pong kernel only: lrp_gemm_nt_rs_rope_ok() -> 1 when the entry point takes the problem,
  * LRP_ESHAPE otherwise (the caller keeps lrp_gemm_nt_rs + lrp_rope_fwd for such shapes).  Weights and outputs stay in the standard head-dim order. */
 int lrp_gemm_nt_rs_rope_ok(int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols, int head_dim, int dtype);
 int lrp_gemm_nt_rs_rope(const void* x, const void* W, const float* rs, const float* cos, const float* sin, void* out, int M, int N, int K,
@@ -322,8 +324,8 @@ int lrp_gemm_nt_rs_rope(const void* x, const void* W, const float* rs, const flo
  *   lrp_gemm_nt_rs_bias      : out[m,n] = bf16(rs[m] * (x W^T)[m,n] + bias[n])
  *   lrp_gemm_nt_rs_bias_rope : the same, then RoPE on the columns [0, rope_cols): the bias is added in fp32 to the un-rounded scaled accumulator,
  *                              the rotation acts on the sum (HF rotates q_proj(x) = x W^T + b), one rounding at the store.  rope_cols must be a
- *                              multiple of 256 here (the kernel rotates whole 256-column tiles: an odd nq + nk at head_dim 128 would rotate the
- *                              first v head): lrp_gemm_nt_rs_bias_rope_ok() -> 0 and the entry point LRP_ESHAPE for such shapes (the caller keeps
+ *                              multiple of 256 here (an odd nq + nk at head_dim 128 is not admitted in the biased form):
+ *                              lrp_gemm_nt_rs_bias_rope_ok() -> 0 and the entry point LRP_ESHAPE for such shapes (the caller keeps
  *                              lrp_gemm_nt_rs_bias + lrp_rope_fwd).  The norm-weight fold W' = W diag(w) does not touch the bias. */
 int lrp_gemm_nt_rs_bias(const void* x, const void* W, const float* rs, const void* bias, void* out, int M, int N, int K, int64_t ldx, int64_t ldw,
                         int64_t ldout, int dtype, void* stream);

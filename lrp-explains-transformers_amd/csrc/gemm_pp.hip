@@ -263,7 +263,9 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(
     }
     // EPI 5: cos / sin of row block k in tpre[k & 1] = {cos tile 0, cos tile 1, sin tile 0, sin tile 1} of the lane's 2 x 4 table columns
     const int w5 = wc & 1, hb5 = (wc >> 1) * 128;
-    const bool rot5 = ROPE && en0 < ep.rope_cols;              // q / k tile (tile-uniform); v tiles only take the row scale
+    // q / k head (WAVE-uniform: a wave's 64 columns lie inside one head of 128, and a tile of 256 may hold the last k head next to the first
+    // v head when the number of rotated heads is odd); v heads only take the row scale
+    const bool rot5 = ROPE && en0 + hb5 < ep.rope_cols;
     f32x4 tpre[2][4];
     // (seq is a multiple of 16 -- lrp_gemm_nt_rs_rope_ok -- so the 16 rows of a row block share one prompt and their positions are
     // consecutive: the block's first position is WAVE-UNIFORM, scalar arithmetic incl. the modulo, and the lane part of the address one register)
@@ -850,8 +852,8 @@ int lrp_launch_gemm_pp_nt_rs_bias(const void* x, const void* W, const float* rs,
     ep.rs = rs;
     return launch_pp_t<bf16_t, false, 0, 0, false, false, true>(x, W, out, bias, M, N, K, ldx, ldw, ldout, 1, K / PP_KT, 0, ep, st);
 }
-// out = RoPE(rs (.) (x W^T) + bias) on the q / k head columns [0, rope_cols), rs (.) (x W^T) + bias on the rest (rope_cols a multiple of 256:
-// a tile never holds a k head and a v head)
+// out = RoPE(rs (.) (x W^T) + bias) on the q / k head columns [0, rope_cols), rs (.) (x W^T) + bias on the rest (the host admits rope_cols a
+// multiple of 256 only: lrp_gemm_nt_rs_bias_rope_ok)
 int lrp_launch_gemm_pp_nt_rs_bias_rope(const void* x, const void* W, const float* rs, const void* bias, const float* cos, const float* sin, void* out,
                                        int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols, hipStream_t st) {
     PPEpi ep{};

@@ -717,9 +717,21 @@ def head_rmsnorm_bwd(G, w, rstd, out, heads, d, w_offset=0.0):
 SITE_FUSION = True      # module attribute (A/B measurements, tests): False keeps Gemma-3's norms / q-k norm / RoPE on the per-module launch sequences
 
 
+def _sandwich_rows_ok(x):
+    return bool(x.dtype in _DT and x.dim() == 2 and x.is_contiguous() and lib.lrp_sandwich_norm_ok(x.shape[1], dt(x)))
+
+
 def sandwich_norm_ok(x):
     """can lrp_sandwich_norm_fwd / _bwd take rows of this width and dtype (the row stays in one workgroup's registers)?"""
-    return bool(SITE_FUSION and x.dtype in _DT and x.dim() == 2 and x.is_contiguous() and lib.lrp_sandwich_norm_ok(x.shape[1], dt(x)))
+    return bool(SITE_FUSION and _sandwich_rows_ok(x))
+
+
+def _rope_tables(cos, sin, seq, d, name):
+    """the site kernels index the tables as [row % seq][d] with a row pitch of d (no count, no pitch in the C ABI): a table shorter than seq or a
+    strided view would be read out of bounds"""
+    for t in (cos, sin):
+        if t.dim() != 2 or t.shape[0] < seq or t.shape[1] != d or t.stride(0) != d or t.stride(1) != 1:
+            raise ValueError(f"{name}: cos / sin must be [>= seq = {seq}, d = {d}] with row stride d, got {tuple(t.shape)} with strides {t.stride()}")
 
 
 def sandwich_norm_fwd(x, res, w_post, w_pre, eps, w_offset, hsum_out, y, rstd_post, rstd_pre):
@@ -741,6 +753,10 @@ def sandwich_norm_bwd(Gres, Gx, w_pre, rstd_pre, w_post, rstd_post, Gs_out, Ga_o
     M, H = Gx.shape
     same(Gx, Gres, Gs_out, Ga_out)
     f32(rstd_pre, rstd_post)
+    for t in (Gx, Gres, Gs_out, Ga_out):          # (no row pitch in the C ABI: [M, H] contiguous, rows of a width the forward's gate takes)
+        if t is not None and (tuple(t.shape) != (M, H) or not _sandwich_rows_ok(t)):
+            raise ValueError(f"lrp_sandwich_norm_bwd: operands must be contiguous [{M}, {H}] rows that sandwich_norm_ok accepts, got "
+                             f"{tuple(t.shape)} with strides {t.stride()}")
     check(lib.lrp_sandwich_norm_bwd(p(Gres), p(Gx), p(aux(w_pre, Gx, H)), p(rstd_pre), p(aux(w_post, Gx, H)), p(rstd_post), p(Gs_out), p(Ga_out), M, H,
                                     w_offset, dt(Gx), stream()), "lrp_sandwich_norm_bwd")
     return Gs_out, Ga_out
@@ -752,6 +768,7 @@ def qk_norm_rope_fwd(qkv, wq, wk, qr, kr, rstd_q, rstd_k, cos_t, sin_t, seq, nq,
     rows = qkv.shape[0]
     same(qkv, qr, kr)
     f32(rstd_q, rstd_k, cos_t, sin_t)
+    _rope_tables(cos_t, sin_t, seq, d, "lrp_qk_norm_rope_fwd")
     check(lib.lrp_qk_norm_rope_fwd(p(qkv), p(aux(wq, qkv, d)), p(aux(wk, qkv, d)), p(qr), p(kr), p(rstd_q), p(rstd_k), p(cos_t), p(sin_t), rows, seq,
                                    nq, nk, d, qkv.stride(0), qr.stride(0), kr.stride(0), eps, w_offset, dt(qkv), stream()), "lrp_qk_norm_rope_fwd")
     return qr, kr
@@ -763,6 +780,7 @@ def qkv_bwd_pack(dq, dk_h, dv_h, wq, wk, rstd_q, rstd_k, cos_t, sin_t, A, seq, n
     rows = dq.shape[0]
     same(dq, dk_h, dv_h, A)
     f32(rstd_q, rstd_k, cos_t, sin_t)
+    _rope_tables(cos_t, sin_t, seq, d, "lrp_qkv_bwd_pack")
     check(lib.lrp_qkv_bwd_pack(p(dq), p(dk_h), p(dv_h), p(aux(wq, dq, d)), p(aux(wk, dq, d)), p(rstd_q), p(rstd_k), p(cos_t), p(sin_t), p(A), rows, seq,
                                nq, nk, d, dq.stride(0), dk_h.stride(0), dv_h.stride(0), A.stride(0), w_offset, dt(dq), stream()), "lrp_qkv_bwd_pack")
     return A

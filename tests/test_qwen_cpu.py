@@ -38,8 +38,8 @@ def test_bias_rope_predicate_and_argument_checks():
     assert lib.lrp_gemm_nt_rs_bias_rope_ok(8192, 6144, 4096, 4096, 4224, 6144, 2048, 5120, 128, BF16) == 1
     assert lib.lrp_gemm_nt_rs_bias_rope_ok(24576, 1024, 512, 512, 512, 1024, 1024, 768, 128, BF16) == 1          # the d = 128 fixture layers
     assert lib.lrp_gemm_nt_rs_bias_rope_ok(8192, 6144, 4096, 4096, 4224, 6144, 2048, 5120, 64, BF16) == 0
-    # odd nq + nk at d = 128 (rope_cols % 256 == 128): the tile that holds the last k head holds the first v head -- refused here, while the
-    # un-biased predicate still takes the shape (that entry is not this change's to fix)
+    # odd nq + nk at d = 128 (rope_cols % 256 == 128): the tile that holds the last k head holds the first v head -- refused here; the
+    # un-biased predicate takes the shape, and rightly: the kernel decides "rotate" per wave = per head (test_gemm_nt_rs_rope_odd_head_count)
     assert lib.lrp_gemm_nt_rs_bias_rope_ok(8192, 4352, 4096, 4096, 4224, 4352, 2048, 4224, 128, BF16) == 0
     assert lib.lrp_gemm_nt_rs_rope_ok(8192, 4352, 4096, 4096, 4224, 4352, 2048, 4224, 128, BF16) == 1
     buf = (ctypes.c_char * 64)()
