@@ -277,3 +277,43 @@ int lrp_attn32_dkv_d256(const void* q, const void* k, const void* v, const void*
                         void* dv, int B, int S, int Hq, int Hkv, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddk,
                         int64_t lddv, float scale, float eps_mask, float eps_qk, int causal, int window, int q_begin,
                         const int* row_lo, const int* row_hi, hipStream_t st);
+
+// ---- the ping-pong GEMM of gemm_pp.hip as the dispatchers of gemm.hip see it.
+// What an epilogue form reads and writes beside A, B, C and bias (EPI 1 .. 6 and the row scale; the forms are described above gemm_pp_kernel)
+struct PPEpi {
+    bf16_t* c2;            // EPI 1: m [M, I]  (C is then the COEFFICIENT stash [M, 2 I]);  EPI 3: the Linear's own output beside the sum, or NULL
+    int64_t ldc2;
+    const bf16_t* gu;      // EPI 2: the coefficient stash [M, 2 I] the gate/up forward (EPI 1) left
+    int64_t ldgu;
+    float eps_g, eps_lin;
+    int act;
+    // RMSNorm folded into the GEMMs around it (K1n):
+    const float* rs;       // RS: per-row scale of the accumulators (rstd of the consumer's input row), applied before everything else
+    const bf16_t* res;     // EPI 3 / 4: residual [M, N] added to the (scaled) accumulators
+    int64_t ldres;
+    float* ssq;            // EPI 3: partial sums of squares of the bf16-rounded output rows, [N / 64][ldssq] (one 64-column block per wave)
+    int64_t ldssq;
+    // EPI 5 / 6: RoPE on the q / k columns of the fused QKV forward
+    const float* cos;      // fp32 [>= seq, 128] tables (rotate-half convention: both halves of a row equal; only the first is read)
+    const float* sin;
+    int seq;               // rows per prompt: the position of output row m is m % seq
+    int rope_cols;         // columns [0, rope_cols) are q / k heads of 128; the rest (v) pass through
+};
+
+// One launch with a fused epilogue: bf16 operands and output, one split over the whole K.  nn = 0: B is [N, K]; nn = 1: B is [K, N].
+// epi = the kernel's EPI; the row scale is on when ep.rs is set.
+struct PPFused {
+    const bf16_t* A;
+    const bf16_t* B;
+    bf16_t* C;
+    const bf16_t* bias;
+    int M, N, K;
+    int64_t lda, ldb, ldc;
+    int nn, epi;
+    PPEpi ep;
+};
+
+// plain / skinny / split-K / fp32-slab launches, and the fused ones (LRP_ESHAPE for a combination that has no instantiation)
+int lrp_launch_gemm_pp(const void* A, const void* B, void* C, const void* bias, int M, int N, int K, int64_t lda, int64_t ldb,
+                       int64_t ldc, int out_dtype, int nn, int splits, int kt_per_split, int64_t slab_stride, hipStream_t st);
+int lrp_launch_gemm_pp_fused(const PPFused& f, hipStream_t st);

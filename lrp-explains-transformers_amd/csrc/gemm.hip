@@ -10,31 +10,11 @@
 //   Common: operands swapped (mma(Bfrag, Afrag)) so a lane owns 4 CONSECUTIVE output columns of one row; LDS rows are 128 B with
 //   the 16-byte chunk index XOR-swizzled with (row & 7): every ds_read_b128 lane group touches 16 distinct 16-byte bank slots;
 //   XCD-aware block remap + grouped tile order keep an operand panel in one XCD's L2.
+// Host side of the ping-pong kernel: one launch addresses A through 32-bit buffer offsets, so every path to it goes through ONE row walker
+// (pp_walk_rows: a problem with more rows than pp_row_chunk(lda) is several launches over row chunks).  The entry points with a fused epilogue
+// (gated-MLP rules, K1n, RoPE, bias: the last section) are their argument checks plus a PPFused descriptor (common.hpp); advance() moves a
+// descriptor's row-indexed operands to a chunk, lrp_launch_gemm_pp_fused (gemm_pp.hip) picks the instantiation.
 #include "common.hpp"
-
-// gemm_pp.hip: 8-wave ping-pong kernel for the big bf16 problems (>= 190 tiles of 256 x 256; 32-bit buffer offsets)
-int lrp_launch_gemm_pp(const void* A, const void* B, void* C, const void* bias, int M, int N, int K, int64_t lda, int64_t ldb,
-                       int64_t ldc, int out_dtype, int nn, int splits, int kt_per_split, int64_t slab_stride, hipStream_t st);
-
-int lrp_launch_gemm_pp_gated_fwd(const void* x, const void* Wgu, const float* rs, void* coef, void* m, int M, int I, int K, int64_t ldx,
-                                 int64_t ldw, int64_t ldcoef, int64_t ldm, float eps_g, float eps_lin, int act, hipStream_t st);
-int lrp_launch_gemm_pp_gated_bwd(const void* Adn, const void* Wdn, const void* coef, void* Agu, int M, int I, int K, int64_t lda,
-                                 int64_t ldw, int64_t ldcoef, int64_t ldagu, hipStream_t st);
-
-int lrp_launch_gemm_pp_res_ssq(const void* x, const void* W, const void* res, void* out, float* ssq, int M, int N, int K, int64_t ldx,
-                               int64_t ldw, int64_t ldres, int64_t ldout, int64_t ldssq, void* raw, int64_t ldraw, hipStream_t st);
-int lrp_launch_gemm_pp_nt_rs(const void* x, const void* W, const float* rs, void* out, int M, int N, int K, int64_t ldx, int64_t ldw,
-                             int64_t ldout, hipStream_t st);
-int lrp_launch_gemm_pp_nn_rs(const void* s, const void* W, const float* rs, void* out, int M, int N, int K, int64_t lds_, int64_t ldw,
-                             int64_t ldout, hipStream_t st);
-int lrp_launch_gemm_pp_nt_rs_rope(const void* x, const void* W, const float* rs, const float* cos, const float* sin, void* out, int M, int N, int K,
-                                  int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols, hipStream_t st);
-int lrp_launch_gemm_pp_nn_rs_res(const void* s, const void* W, const float* rs, const void* res, void* out, int M, int N, int K, int64_t lds_,
-                                 int64_t ldw, int64_t ldres, int64_t ldout, hipStream_t st);
-int lrp_launch_gemm_pp_nt_rs_bias(const void* x, const void* W, const float* rs, const void* bias, void* out, int M, int N, int K, int64_t ldx,
-                                  int64_t ldw, int64_t ldout, hipStream_t st);
-int lrp_launch_gemm_pp_nt_rs_bias_rope(const void* x, const void* W, const float* rs, const void* bias, const float* cos, const float* sin, void* out,
-                                       int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols, hipStream_t st);
 
 namespace {
 
@@ -342,6 +322,16 @@ inline int pp_row_chunk(int64_t lda) {
     const int64_t r = (((1ll << 30) - 1) / (lda > 0 ? lda : 1)) / 256 * 256;
     return (int)(r < 256 ? 0 : (r > (1 << 30) ? (1 << 30) : r));
 }
+// The one row walker: launch(m0, rows) for every chunk of an M-row problem whose A has row pitch lda (pp_row_chunk(lda) > 0: pp_ok)
+template <typename F>
+int pp_walk_rows(int M, int64_t lda, F launch) {
+    const int chunk = pp_row_chunk(lda);
+    for (int m0 = 0; m0 < M; m0 += chunk) {
+        const int rc = launch(m0, M - m0 < chunk ? M - m0 : chunk);
+        if (rc != LRP_OK) return rc;
+    }
+    return LRP_OK;
+}
 template <typename T, typename TO>
 int launch_fast(const void* A, const void* B, void* C, const void* bias, int M, int N, int K, int64_t lda, int64_t ldb,
                 int64_t ldc, int batch, int64_t sA, int64_t sB, int64_t sC, hipStream_t st) {
@@ -351,13 +341,10 @@ int launch_fast(const void* A, const void* B, void* C, const void* bias, int M, 
     // instantiation accumulates in blocks
     if (sizeof(T) == 2 && tiles256 >= 190) {
         if (batch == 1 && K / KE >= 2 && pp_row_chunk(lda) > 0 && (int64_t)N * ldb < (1ll << 30)) {
-            const int chunk = pp_row_chunk(lda);
-            for (int m0 = 0; m0 < M; m0 += chunk) {
-                const int rc = lrp_launch_gemm_pp((const T*)A + (int64_t)m0 * lda, B, (TO*)C + (int64_t)m0 * ldc, bias, M - m0 < chunk ? M - m0 : chunk,
-                                                  N, K, lda, ldb, ldc, sizeof(TO) == 4 ? LRP_F32 : LRP_BF16, 0, 1, K / KE, 0, st);
-                if (rc != LRP_OK) return rc;
-            }
-            return LRP_OK;
+            return pp_walk_rows(M, lda, [&](int m0, int rows) {
+                return lrp_launch_gemm_pp((const T*)A + (int64_t)m0 * lda, B, (TO*)C + (int64_t)m0 * ldc, bias, rows, N, K, lda, ldb, ldc,
+                                          sizeof(TO) == 4 ? LRP_F32 : LRP_BF16, 0, 1, K / KE, 0, st);
+            });
         }
         return launch_glds<T, TO, 256, 256, 4, 4>(A, B, C, bias, M, N, K, lda, ldb, ldc, batch, sA, sB, sC, st);
     }
@@ -510,14 +497,11 @@ extern "C" int lrp_gemm_nn(const void* A, const void* Bt, void* C, const void* b
     if (dtype != LRP_BF16 || (out_dtype != LRP_BF16 && out_dtype != LRP_F32)) return LRP_ESHAPE;
     if ((lda % 8) || (ldb % 8) || (reinterpret_cast<uintptr_t>(A) & 15) || (reinterpret_cast<uintptr_t>(Bt) & 15)) return LRP_EALIGN;
     if (!pp_ok(M, N, K, lda, ldb, 1)) return LRP_ESHAPE;
-    const int chunk = pp_row_chunk(lda);
     const int64_t osz = (out_dtype == LRP_F32) ? 4 : 2;
-    for (int m0 = 0; m0 < M; m0 += chunk) {
-        const int rc = lrp_launch_gemm_pp((const char*)A + (int64_t)m0 * lda * 2, Bt, (char*)C + (int64_t)m0 * ldc * osz, bias,
-                                          M - m0 < chunk ? M - m0 : chunk, N, K, lda, ldb, ldc, out_dtype, 1, 1, K / 64, 0, (hipStream_t)stream);
-        if (rc != LRP_OK) return rc;
-    }
-    return LRP_OK;
+    return pp_walk_rows(M, lda, [&](int m0, int rows) {
+        return lrp_launch_gemm_pp((const char*)A + (int64_t)m0 * lda * 2, Bt, (char*)C + (int64_t)m0 * ldc * osz, bias, rows, N, K, lda, ldb, ldc,
+                                  out_dtype, 1, 1, K / 64, 0, (hipStream_t)stream);
+    });
 }
 
 extern "C" int lrp_gemm_skinny_splits(int M, int N, int K) {
@@ -561,23 +545,53 @@ extern "C" int lrp_gemm_skinny(const void* A, const void* B, void* C, const void
 }
 
 // =================================================================================================
-// gated-MLP rules fused into the GEMMs around them (interleaved gate/up layout, include/lrp_hip.h)
+// The fused-epilogue entry points.  Each one is its argument checks and a PPFused descriptor (common.hpp); launch_fused_rows issues the
+// descriptor over the row chunks of the problem, and advance() is the only place that knows how a chunk is addressed.
 // =================================================================================================
 namespace {
 bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+PPFused pp_fused(int epi, int nn, const void* A, const void* B, void* C, int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc) {
+    PPFused f{};
+    f.A = (const bf16_t*)A; f.B = (const bf16_t*)B; f.C = (bf16_t*)C;
+    f.M = M; f.N = N; f.K = K; f.lda = lda; f.ldb = ldb; f.ldc = ldc; f.nn = nn; f.epi = epi;
+    return f;
+}
+
+// moves every row-indexed operand a descriptor can carry to row m0 of the problem; a null pointer stays null
+void advance(PPFused& f, int m0) {
+    auto rows = [m0](auto*& ptr, int64_t pitch) { if (ptr) ptr += (int64_t)m0 * pitch; };
+    rows(f.A, f.lda); rows(f.C, f.ldc); rows(f.ep.c2, f.ep.ldc2); rows(f.ep.gu, f.ep.ldgu); rows(f.ep.res, f.ep.ldres);
+    rows(f.ep.rs, 1); rows(f.ep.ssq, 1);                 // (ssq is [N / 64][ldssq]: a row of the problem is a COLUMN of it)
+    // the kernel takes positions as row % seq: a chunk that starts inside a prompt is shifted by handing it tables that start at that position
+    // (lrp_gemm_nt_rs_rope_ok admits only chunk sizes for which a chunk then never runs past the tables' row seq)
+    if (f.ep.cos) { const int64_t p0 = m0 % f.ep.seq; f.ep.cos += p0 * 128; f.ep.sin += p0 * 128; }
+}
+
+int launch_fused_rows(const PPFused& whole, void* stream) {
+    return pp_walk_rows(whole.M, whole.lda, [&](int m0, int rows) {
+        PPFused f = whole;
+        advance(f, m0);
+        f.M = rows;
+        return lrp_launch_gemm_pp_fused(f, (hipStream_t)stream);
+    });
+}
+
 bool gated_fused_ok(int M, int Ncols, int K, int I, int64_t lda, int64_t ldb, int nn, int act) {
     const int64_t tiles = (int64_t)((M + 255) / 256) * ((Ncols + 255) / 256);
     return tiles >= 190 && (I % LRP_GATED_IL) == 0 && (act == LRP_ACT_SILU || act == LRP_ACT_GELU_TANH) && pp_ok(M, Ncols, K, lda, ldb, nn);
 }
 }  // namespace
 
-// ---- round 6: the fused form stashes the backward's COEFFICIENTS (include/lrp_hip.h).  Both launches of a layer must be problems the
-// ping-pong kernel's fused epilogues take: the gate/up forward [M, 2 I] over K = hidden (NT) and the down-projection dgrad [M, I] over hidden (NN)
+// ---- gated-MLP rules fused into the GEMMs around them (interleaved gate/up layout, include/lrp_hip.h): the fused form stashes the backward's
+// COEFFICIENTS.  Both launches of a layer must be problems the ping-pong kernel's fused epilogues take: the gate/up forward [M, 2 I] over
+// K = hidden (NT) and the down-projection dgrad [M, I] over hidden (NN)
 extern "C" int lrp_gemm_gated_coef_ok(int M, int I, int H, int64_t ldx, int64_t ldwgu, int64_t lda, int64_t ldwd, int act, int dtype) {
     if (dtype != LRP_BF16 || M <= 0 || I <= 0 || H <= 0 || (ldx % 8) || (ldwgu % 8) || (lda % 8) || (ldwd % 8)) return 0;
     return (gated_fused_ok(M, 2 * I, H, I, ldx, ldwgu, 0, act) && gated_fused_ok(M, I, H, I, lda, ldwd, 1, act)) ? 1 : 0;
 }
 
+// m[M, I] = act(g) (*) u and the coefficient stash coef[M, 2 I] from x[M, K] . Wgu[2 I, K]^T; rs != NULL: the accumulators are scaled by rs[row] first
 extern "C" int lrp_gemm_gated_fwd_coef(const void* x, const void* Wgu, const float* rs, void* coef, void* m, int M, int I, int K, int64_t ldx,
                                        int64_t ldw, int64_t ldcoef, int64_t ldm, float eps_g, float eps_lin, int act, int dtype, void* stream) {
     if (!x || !Wgu || !coef || !m || M < 0 || I < 0 || K < 0 || act < 0 || act > 3 || eps_g < 0.f || eps_lin < 0.f) return LRP_EINVAL;
@@ -585,17 +599,12 @@ extern "C" int lrp_gemm_gated_fwd_coef(const void* x, const void* Wgu, const flo
     if (dtype != LRP_BF16 || (ldx % 8) || (ldw % 8) || !gated_fused_ok(M, 2 * I, K, I, ldx, ldw, 0, act)) return LRP_ESHAPE;
     // (the epilogue stores the coefficient stash and m with 16-byte vector stores on full tiles)
     if (!a16(x) || !a16(Wgu) || !a16(coef) || !a16(m) || (ldcoef % 8) || (ldm % 8)) return LRP_EALIGN;
-    const int chunk = pp_row_chunk(ldx);
-    for (int m0 = 0; m0 < M; m0 += chunk) {
-        const int rc = lrp_launch_gemm_pp_gated_fwd((const char*)x + (int64_t)m0 * ldx * 2, Wgu, rs ? rs + m0 : nullptr,
-                                                    (char*)coef + (int64_t)m0 * ldcoef * 2, (char*)m + (int64_t)m0 * ldm * 2,
-                                                    M - m0 < chunk ? M - m0 : chunk, I, K, ldx, ldw, ldcoef, ldm, eps_g, eps_lin, act,
-                                                    (hipStream_t)stream);
-        if (rc != LRP_OK) return rc;
-    }
-    return LRP_OK;
+    PPFused f = pp_fused(1, 0, x, Wgu, coef, M, 2 * I, K, ldx, ldw, ldcoef);
+    f.ep.c2 = (bf16_t*)m; f.ep.ldc2 = ldm; f.ep.act = act; f.ep.rs = rs; f.ep.eps_g = eps_g; f.ep.eps_lin = eps_lin;
+    return launch_fused_rows(f, stream);
 }
 
+// Agu[M, 2 I] = Gm (*) coef with Gm = Adn[M, K] . Wdn[K, I] (NN) never stored
 extern "C" int lrp_gemm_gated_bwd_coef(const void* Adn, const void* Wdn, const void* coef, void* Agu, int M, int I, int K, int64_t lda,
                                        int64_t ldw, int64_t ldcoef, int64_t ldagu, int dtype, void* stream) {
     if (!Adn || !Wdn || !coef || !Agu || M < 0 || I < 0 || K < 0) return LRP_EINVAL;
@@ -603,20 +612,12 @@ extern "C" int lrp_gemm_gated_bwd_coef(const void* Adn, const void* Wdn, const v
     if (dtype != LRP_BF16 || (lda % 8) || (ldw % 8) || !gated_fused_ok(M, I, K, I, lda, ldw, 1, LRP_ACT_SILU)) return LRP_ESHAPE;
     // (the epilogue loads the stash and stores Agu 16 bytes at a time)
     if (!a16(Adn) || !a16(Wdn) || !a16(coef) || !a16(Agu) || (ldcoef % 8) || (ldagu % 8)) return LRP_EALIGN;
-    const int chunk = pp_row_chunk(lda);
-    for (int m0 = 0; m0 < M; m0 += chunk) {
-        const int rc = lrp_launch_gemm_pp_gated_bwd((const char*)Adn + (int64_t)m0 * lda * 2, Wdn, (const char*)coef + (int64_t)m0 * ldcoef * 2,
-                                                    (char*)Agu + (int64_t)m0 * ldagu * 2, M - m0 < chunk ? M - m0 : chunk, I, K, lda, ldw,
-                                                    ldcoef, ldagu, (hipStream_t)stream);
-        if (rc != LRP_OK) return rc;
-    }
-    return LRP_OK;
+    PPFused f = pp_fused(2, 1, Adn, Wdn, Agu, M, I, K, lda, ldw, ldagu);
+    f.ep.gu = (const bf16_t*)coef; f.ep.ldgu = ldcoef;
+    return launch_fused_rows(f, stream);
 }
 
-
-// =================================================================================================
-// K1n: Llama-type RMSNorm folded into the GEMMs around it (include/lrp_hip.h)
-// =================================================================================================
+// ---- K1n: Llama-type RMSNorm folded into the GEMMs around it (include/lrp_hip.h)
 extern "C" int lrp_gemm_norm_fused_ok(int M, int N, int K, int64_t lda, int64_t ldb, int nn, int dtype) {
     if (dtype != LRP_BF16 || M <= 0 || N <= 0 || K <= 0 || (N % 256) || (lda % 8) || (ldb % 8)) return 0;
     const int64_t tiles = (int64_t)((M + 255) / 256) * (N / 256);
@@ -629,14 +630,9 @@ extern "C" int lrp_gemm_res_ssq(const void* x, const void* W, const void* res, v
     if (M == 0 || N == 0) return LRP_OK;
     if (!lrp_gemm_norm_fused_ok(M, N, K, ldx, ldw, 0, dtype)) return LRP_ESHAPE;
     if (!a16(x) || !a16(W) || (ldout % 8) || (ldres % 8) || (raw && (!a16(raw) || (ldraw % 8)))) return LRP_EALIGN;
-    const int chunk = pp_row_chunk(ldx);
-    for (int m0 = 0; m0 < M; m0 += chunk) {
-        const int rc = lrp_launch_gemm_pp_res_ssq((const char*)x + (int64_t)m0 * ldx * 2, W, (const char*)res + (int64_t)m0 * ldres * 2,
-                                                  (char*)out + (int64_t)m0 * ldout * 2, ssq + m0, M - m0 < chunk ? M - m0 : chunk, N, K, ldx, ldw,
-                                                  ldres, ldout, ldssq, raw ? (char*)raw + (int64_t)m0 * ldraw * 2 : nullptr, ldraw, (hipStream_t)stream);
-        if (rc != LRP_OK) return rc;
-    }
-    return LRP_OK;
+    PPFused f = pp_fused(3, 0, x, W, out, M, N, K, ldx, ldw, ldout);
+    f.ep.res = (const bf16_t*)res; f.ep.ldres = ldres; f.ep.ssq = ssq; f.ep.ldssq = ldssq; f.ep.c2 = (bf16_t*)raw; f.ep.ldc2 = ldraw;
+    return launch_fused_rows(f, stream);
 }
 
 extern "C" int lrp_gemm_nt_rs(const void* x, const void* W, const float* rs, void* out, int M, int N, int K, int64_t ldx, int64_t ldw,
@@ -645,13 +641,9 @@ extern "C" int lrp_gemm_nt_rs(const void* x, const void* W, const float* rs, voi
     if (M == 0 || N == 0) return LRP_OK;
     if (!lrp_gemm_norm_fused_ok(M, N, K, ldx, ldw, 0, dtype)) return LRP_ESHAPE;
     if (!a16(x) || !a16(W) || (ldout % 8)) return LRP_EALIGN;
-    const int chunk = pp_row_chunk(ldx);
-    for (int m0 = 0; m0 < M; m0 += chunk) {
-        const int rc = lrp_launch_gemm_pp_nt_rs((const char*)x + (int64_t)m0 * ldx * 2, W, rs + m0, (char*)out + (int64_t)m0 * ldout * 2,
-                                                M - m0 < chunk ? M - m0 : chunk, N, K, ldx, ldw, ldout, (hipStream_t)stream);
-        if (rc != LRP_OK) return rc;
-    }
-    return LRP_OK;
+    PPFused f = pp_fused(0, 0, x, W, out, M, N, K, ldx, ldw, ldout);
+    f.ep.rs = rs;
+    return launch_fused_rows(f, stream);
 }
 
 extern "C" int lrp_gemm_nt_rs_rope_ok(int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols, int head_dim, int dtype) {
@@ -667,16 +659,9 @@ extern "C" int lrp_gemm_nt_rs_rope(const void* x, const void* W, const float* rs
     if (M == 0 || N == 0) return LRP_OK;
     if (!lrp_gemm_nt_rs_rope_ok(M, N, K, ldx, ldw, ldout, seq, rope_cols, head_dim, dtype)) return LRP_ESHAPE;
     if (!a16(x) || !a16(W) || !a16(out) || !a16(cos) || !a16(sin)) return LRP_EALIGN;
-    const int chunk = pp_row_chunk(ldx);
-    for (int m0 = 0; m0 < M; m0 += chunk) {
-        // (the kernel takes positions as row % seq: a chunk that starts inside a prompt is shifted by handing it tables that start at that position)
-        const int p0 = m0 % seq;
-        const int rc = lrp_launch_gemm_pp_nt_rs_rope((const char*)x + (int64_t)m0 * ldx * 2, W, rs + m0, cos + (int64_t)p0 * 128, sin + (int64_t)p0 * 128,
-                                                     (char*)out + (int64_t)m0 * ldout * 2, M - m0 < chunk ? M - m0 : chunk, N, K, ldx, ldw, ldout,
-                                                     seq, rope_cols, (hipStream_t)stream);
-        if (rc != LRP_OK) return rc;
-    }
-    return LRP_OK;
+    PPFused f = pp_fused(5, 0, x, W, out, M, N, K, ldx, ldw, ldout);
+    f.ep.rs = rs; f.ep.cos = cos; f.ep.sin = sin; f.ep.seq = seq; f.ep.rope_cols = rope_cols;
+    return launch_fused_rows(f, stream);
 }
 
 // Qwen2's q / k / v bias in the fused QKV forward: bias bf16 [N], added in fp32 after the row scale (and ahead of the rotation)
@@ -686,13 +671,9 @@ extern "C" int lrp_gemm_nt_rs_bias(const void* x, const void* W, const float* rs
     if (M == 0 || N == 0) return LRP_OK;
     if (!lrp_gemm_norm_fused_ok(M, N, K, ldx, ldw, 0, dtype)) return LRP_ESHAPE;
     if (!a16(x) || !a16(W) || !a16(bias) || (ldout % 8)) return LRP_EALIGN;
-    const int chunk = pp_row_chunk(ldx);
-    for (int m0 = 0; m0 < M; m0 += chunk) {
-        const int rc = lrp_launch_gemm_pp_nt_rs_bias((const char*)x + (int64_t)m0 * ldx * 2, W, rs + m0, bias, (char*)out + (int64_t)m0 * ldout * 2,
-                                                     M - m0 < chunk ? M - m0 : chunk, N, K, ldx, ldw, ldout, (hipStream_t)stream);
-        if (rc != LRP_OK) return rc;
-    }
-    return LRP_OK;
+    PPFused f = pp_fused(0, 0, x, W, out, M, N, K, ldx, ldw, ldout);
+    f.bias = (const bf16_t*)bias; f.ep.rs = rs;
+    return launch_fused_rows(f, stream);
 }
 
 // (rope_cols a multiple of 256 is still asked for HERE: an odd nq + nk at head_dim 128 puts the last k head and the first v head into one
@@ -711,15 +692,9 @@ extern "C" int lrp_gemm_nt_rs_bias_rope(const void* x, const void* W, const floa
     if (M == 0 || N == 0) return LRP_OK;
     if (!lrp_gemm_nt_rs_bias_rope_ok(M, N, K, ldx, ldw, ldout, seq, rope_cols, head_dim, dtype)) return LRP_ESHAPE;
     if (!a16(x) || !a16(W) || !a16(out) || !a16(bias) || !a16(cos) || !a16(sin)) return LRP_EALIGN;
-    const int chunk = pp_row_chunk(ldx);
-    for (int m0 = 0; m0 < M; m0 += chunk) {
-        const int p0 = m0 % seq;          // (a chunk that starts inside a prompt gets tables that start at that position, as lrp_gemm_nt_rs_rope)
-        const int rc = lrp_launch_gemm_pp_nt_rs_bias_rope((const char*)x + (int64_t)m0 * ldx * 2, W, rs + m0, bias, cos + (int64_t)p0 * 128,
-                                                          sin + (int64_t)p0 * 128, (char*)out + (int64_t)m0 * ldout * 2,
-                                                          M - m0 < chunk ? M - m0 : chunk, N, K, ldx, ldw, ldout, seq, rope_cols, (hipStream_t)stream);
-        if (rc != LRP_OK) return rc;
-    }
-    return LRP_OK;
+    PPFused f = pp_fused(6, 0, x, W, out, M, N, K, ldx, ldw, ldout);
+    f.bias = (const bf16_t*)bias; f.ep.rs = rs; f.ep.cos = cos; f.ep.sin = sin; f.ep.seq = seq; f.ep.rope_cols = rope_cols;
+    return launch_fused_rows(f, stream);
 }
 
 extern "C" int lrp_gemm_nn_rs(const void* s, const void* W, const float* rs, void* out, int M, int N, int K, int64_t lds_, int64_t ldw,
@@ -728,13 +703,9 @@ extern "C" int lrp_gemm_nn_rs(const void* s, const void* W, const float* rs, voi
     if (M == 0 || N == 0) return LRP_OK;
     if (!lrp_gemm_norm_fused_ok(M, N, K, lds_, ldw, 1, dtype)) return LRP_ESHAPE;
     if (!a16(s) || !a16(W) || (ldout % 8)) return LRP_EALIGN;
-    const int chunk = pp_row_chunk(lds_);
-    for (int m0 = 0; m0 < M; m0 += chunk) {
-        const int rc = lrp_launch_gemm_pp_nn_rs((const char*)s + (int64_t)m0 * lds_ * 2, W, rs + m0, (char*)out + (int64_t)m0 * ldout * 2,
-                                                M - m0 < chunk ? M - m0 : chunk, N, K, lds_, ldw, ldout, (hipStream_t)stream);
-        if (rc != LRP_OK) return rc;
-    }
-    return LRP_OK;
+    PPFused f = pp_fused(0, 1, s, W, out, M, N, K, lds_, ldw, ldout);
+    f.ep.rs = rs;
+    return launch_fused_rows(f, stream);
 }
 
 extern "C" int lrp_gemm_nn_rs_res(const void* s, const void* W, const float* rs, const void* res, void* out, int M, int N, int K, int64_t lds_,
@@ -743,12 +714,7 @@ extern "C" int lrp_gemm_nn_rs_res(const void* s, const void* W, const float* rs,
     if (M == 0 || N == 0) return LRP_OK;
     if (!lrp_gemm_norm_fused_ok(M, N, K, lds_, ldw, 1, dtype)) return LRP_ESHAPE;
     if (!a16(s) || !a16(W) || (ldout % 8) || (ldres % 8)) return LRP_EALIGN;
-    const int chunk = pp_row_chunk(lds_);
-    for (int m0 = 0; m0 < M; m0 += chunk) {
-        const int rc = lrp_launch_gemm_pp_nn_rs_res((const char*)s + (int64_t)m0 * lds_ * 2, W, rs + m0, (const char*)res + (int64_t)m0 * ldres * 2,
-                                                    (char*)out + (int64_t)m0 * ldout * 2, M - m0 < chunk ? M - m0 : chunk, N, K, lds_, ldw, ldres,
-                                                    ldout, (hipStream_t)stream);
-        if (rc != LRP_OK) return rc;
-    }
-    return LRP_OK;
+    PPFused f = pp_fused(4, 1, s, W, out, M, N, K, lds_, ldw, ldout);
+    f.ep.res = (const bf16_t*)res; f.ep.ldres = ldres; f.ep.rs = rs;
+    return launch_fused_rows(f, stream);
 }

@@ -56,6 +56,8 @@
 // SigLIP / Gemma-3 shapes in the isolated A/B, within noise in situ -- the per-tile prologue / dispatch cost the round-4 notes hoped to recover
 // (3-15 %) is ~1 %.  A staggered first round (workgroups starting up to 17 us apart to de-phase the CUs' epilogue bursts) changed nothing and was
 // removed: the fused epilogues are bound by their own VALU issue (see gated_bwd_pair_bf16 in common.hpp), not by a shared HBM burst.
+// Host side (the end of this file): lrp_launch_gemm_pp = the plain / skinny / split-K / fp32-slab launches; lrp_launch_gemm_pp_fused = every
+// launch with a fused epilogue, described by one PPFused (common.hpp) -- its switch is the list of fused instantiations.
 #include "common.hpp"
 
 namespace {
@@ -80,26 +82,7 @@ typedef __attribute__((address_space(3))) void* pp_lds_ptr_t;
 #define PP_DSRD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 #define PP_DSTR(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 
-// fused gated-MLP epilogues (EPI 1 / 2, see the end of the kernel); EPI 0 = plain (+ bias)
-struct PPEpi {
-    bf16_t* c2;            // EPI 1: m [M, I]  (C is then the COEFFICIENT stash [M, 2 I], see below)
-    int64_t ldc2;
-    const bf16_t* gu;      // EPI 2: the coefficient stash [M, 2 I] the gate/up forward (EPI 1) left
-    int64_t ldgu;
-    float eps_g, eps_lin;
-    int act;
-    // round 5, RMSNorm folded into the GEMMs around it (lrp_gemm_*_rs / _res entry points below):
-    const float* rs;       // RS: per-row scale of the accumulators (rstd of the consumer's input row), applied before everything else
-    const bf16_t* res;     // EPI 3 / 4: residual [M, N] added to the (scaled) accumulators
-    int64_t ldres;
-    float* ssq;            // EPI 3: partial sums of squares of the bf16-rounded output rows, [N / 64][ldssq] (one 64-column block per wave)
-    int64_t ldssq;
-    // round 6, EPI 5: RoPE on the q / k columns of the fused QKV forward (lrp_gemm_nt_rs_rope)
-    const float* cos;      // fp32 [>= seq, 128] tables (rotate-half convention: both halves of a row equal; only the first is read)
-    const float* sin;
-    int seq;               // rows per prompt: the position of output row m is m % seq
-    int rope_cols;         // columns [0, rope_cols) are q / k heads of 128; the rest (v) pass through
-};
+// (struct PPEpi -- what the fused epilogues read and write beside A, B, C and bias; EPI 0 = plain (+ bias) -- is in common.hpp)
 
 // SK ("skinny"): the problem has ONE row of tiles and fewer than 241 rows (the HBM-bound regime of the Linear eps-rule, M <~ 160): 16-row
 // blocks of the 256-row tile that lie past M are not multiplied -- the full tile's 2 x 256 x 256 x 64 FLOP per K tile would make a
@@ -789,88 +772,38 @@ int lrp_launch_gemm_pp(const void* A, const void* B, void* C, const void* bias, 
     return launch_pp_t<bf16_t, false, 0>(A, B, C, bias, M, N, K, lda, ldb, ldc, splits, kt_per_split, slab_stride, ep, st);
 }
 
-// gate/up forward with the gated rule in the epilogue: m[M, I] = act(g) (*) u and the backward's coefficient stash coef[M, 2 I] (accumulator order,
-// include/lrp_hip.h) from x[M, K] . Wgu[2 I, K]^T (rows interleaved [32 gate | 32 up]); rs != NULL: the accumulators are scaled by rs[row] first
-// (K1n: the folded RMSNorm's 1 / rms).  The activation is a compile-time parameter: with a run-time switch inside the 8-fold unrolled epilogue
-// hipcc gives up unrolling and moves the 128 accumulators to scratch.  LEAN = the lxt.efficient placement (eps_g >= 1e-30, no Linear stabiliser).
-namespace {
-template <int ACT, bool LEAN>
-int gated_fwd_t(const void* x, const void* Wgu, const float* rs, void* coef, int M, int I, int K, int64_t ldx, int64_t ldw, int64_t ldcoef,
-                const PPEpi& ep, hipStream_t st) {
-    if (rs) return launch_pp_t<bf16_t, false, 1, ACT, false, LEAN, true>(x, Wgu, coef, nullptr, M, 2 * I, K, ldx, ldw, ldcoef, 1, K / PP_KT, 0, ep, st);
-    return launch_pp_t<bf16_t, false, 1, ACT, false, LEAN, false>(x, Wgu, coef, nullptr, M, 2 * I, K, ldx, ldw, ldcoef, 1, K / PP_KT, 0, ep, st);
-}
-}  // namespace
-int lrp_launch_gemm_pp_gated_fwd(const void* x, const void* Wgu, const float* rs, void* coef, void* m, int M, int I, int K, int64_t ldx,
-                                 int64_t ldw, int64_t ldcoef, int64_t ldm, float eps_g, float eps_lin, int act, hipStream_t st) {
-    PPEpi ep{};
-    ep.c2 = (bf16_t*)m; ep.ldc2 = ldm; ep.act = act; ep.rs = rs; ep.eps_g = eps_g; ep.eps_lin = eps_lin;
-    const bool lean = eps_g >= 1e-30f && eps_lin == 0.f;
-    if (act == LRP_ACT_SILU)
-        return lean ? gated_fwd_t<LRP_ACT_SILU, true>(x, Wgu, rs, coef, M, I, K, ldx, ldw, ldcoef, ep, st)
-                    : gated_fwd_t<LRP_ACT_SILU, false>(x, Wgu, rs, coef, M, I, K, ldx, ldw, ldcoef, ep, st);
-    if (act == LRP_ACT_GELU_TANH)
-        return lean ? gated_fwd_t<LRP_ACT_GELU_TANH, true>(x, Wgu, rs, coef, M, I, K, ldx, ldw, ldcoef, ep, st)
-                    : gated_fwd_t<LRP_ACT_GELU_TANH, false>(x, Wgu, rs, coef, M, I, K, ldx, ldw, ldcoef, ep, st);
+// Every launch with a fused epilogue (descriptor: PPFused, common.hpp; filled by the entry points of gemm.hip, which also split a problem into
+// row chunks).  The table below IS the set of fused instantiations: a new form is one more case.
+//   EPI 0 + row scale   out = rs (.) (A B) (+ bias)                                                    NT: lrp_gemm_nt_rs, _nt_rs_bias;  NN: lrp_gemm_nn_rs
+//   EPI 1 (NT)          the gate/up forward with the gated rule: ep.c2 = m[M, N / 2] = act(g) (*) u and C = the backward's coefficient stash
+//                       [M, N] (accumulator order, include/lrp_hip.h) from x . Wgu^T (rows interleaved [32 gate | 32 up]); with or without the row scale
+//   EPI 2 (NN)          the down-projection dgrad with the gated rule: Gm = Adn . Wdn (never stored) -> C = Agu[M, 2 I] = Gm (*) ep.gu
+//   EPI 3 (NT)          out = res + x W^T and the partial sums of squares of out's rows, one per 64-column block: ep.ssq [N / 64][ldssq]
+//   EPI 4 (NN) + scale  out = rs (.) (s W) + res
+//   EPI 5 / 6 (NT) + scale  out = RoPE(rs (.) (x W^T) (+ bias)) on the q / k head columns [0, rope_cols), no rotation on the rest (heads of 128;
+//                       M, N multiples of 256; with the bias the host admits rope_cols a multiple of 256 only: lrp_gemm_nt_rs_bias_rope_ok)
+// The activation and LEAN (= the lxt.efficient placement: eps_g >= 1e-30, no Linear stabiliser) are compile-time parameters: with a run-time switch
+// inside the 8-fold unrolled epilogue hipcc gives up unrolling and moves the 128 accumulators to scratch.
+int lrp_launch_gemm_pp_fused(const PPFused& f, hipStream_t st) {
+    const bool rs = f.ep.rs != nullptr, lean = f.ep.eps_g >= 1e-30f && f.ep.eps_lin == 0.f;
+#define PP_FUSED(NN, EPI, ACT, LEAN, RS) \
+    launch_pp_t<bf16_t, NN, EPI, ACT, false, LEAN, RS>(f.A, f.B, f.C, f.bias, f.M, f.N, f.K, f.lda, f.ldb, f.ldc, 1, f.K / PP_KT, 0, f.ep, st)
+#define PP_GATED_FWD(ACT) \
+    (lean ? (rs ? PP_FUSED(false, 1, ACT, true, true) : PP_FUSED(false, 1, ACT, true, false)) \
+          : (rs ? PP_FUSED(false, 1, ACT, false, true) : PP_FUSED(false, 1, ACT, false, false)))
+    switch (f.epi) {
+        case 0: if (rs) return f.nn ? PP_FUSED(true, 0, 0, false, true) : PP_FUSED(false, 0, 0, false, true); break;
+        case 1:
+            if (!f.nn && f.ep.act == LRP_ACT_SILU) return PP_GATED_FWD(LRP_ACT_SILU);
+            if (!f.nn && f.ep.act == LRP_ACT_GELU_TANH) return PP_GATED_FWD(LRP_ACT_GELU_TANH);
+            break;
+        case 2: if (f.nn && !rs) return PP_FUSED(true, 2, 0, false, false); break;
+        case 3: if (!f.nn && !rs) return PP_FUSED(false, 3, 0, false, false); break;
+        case 4: if (f.nn && rs) return PP_FUSED(true, 4, 0, false, true); break;
+        case 5: if (!f.nn && rs) return PP_FUSED(false, 5, 0, false, true); break;
+        case 6: if (!f.nn && rs) return PP_FUSED(false, 6, 0, false, true); break;
+    }
+#undef PP_GATED_FWD
+#undef PP_FUSED
     return LRP_ESHAPE;
-}
-
-// down-projection dgrad with the gated rule in the epilogue: Gm = Adn[M, K] . Wdn[K, I] (NN, never stored) -> Agu[M, 2 I] = Gm (*) coef
-int lrp_launch_gemm_pp_gated_bwd(const void* Adn, const void* Wdn, const void* coef, void* Agu, int M, int I, int K, int64_t lda,
-                                 int64_t ldw, int64_t ldcoef, int64_t ldagu, hipStream_t st) {
-    PPEpi ep{};
-    ep.gu = (const bf16_t*)coef; ep.ldgu = ldcoef;
-    return launch_pp_t<bf16_t, true, 2>(Adn, Wdn, Agu, nullptr, M, I, K, lda, ldw, ldagu, 1, K / PP_KT, 0, ep, st);
-}
-
-// ---- RMSNorm folded into the GEMMs around it (round 5; include/lrp_hip.h "K1n").  Same kernel, three more epilogue forms.
-// out = res + x W^T (NT) and the partial sums of squares of out's rows, one per 64-column block: ssq [N / 64][ldssq]
-int lrp_launch_gemm_pp_res_ssq(const void* x, const void* W, const void* res, void* out, float* ssq, int M, int N, int K, int64_t ldx,
-                               int64_t ldw, int64_t ldres, int64_t ldout, int64_t ldssq, void* raw, int64_t ldraw, hipStream_t st) {
-    PPEpi ep{};
-    ep.res = (const bf16_t*)res; ep.ldres = ldres; ep.ssq = ssq; ep.ldssq = ldssq; ep.c2 = (bf16_t*)raw; ep.ldc2 = ldraw;
-    return launch_pp_t<bf16_t, false, 3>(x, W, out, nullptr, M, N, K, ldx, ldw, ldout, 1, K / PP_KT, 0, ep, st);
-}
-// out = rs (.) (x W^T) (NT), rs [M] fp32
-int lrp_launch_gemm_pp_nt_rs(const void* x, const void* W, const float* rs, void* out, int M, int N, int K, int64_t ldx, int64_t ldw,
-                             int64_t ldout, hipStream_t st) {
-    PPEpi ep{};
-    ep.rs = rs;
-    return launch_pp_t<bf16_t, false, 0, 0, false, false, true>(x, W, out, nullptr, M, N, K, ldx, ldw, ldout, 1, K / PP_KT, 0, ep, st);
-}
-// out = RoPE(rs (.) (x W^T)) on the q / k head columns [0, rope_cols), rs (.) (x W^T) on the rest (NT; heads of 128; M, N multiples of 256)
-int lrp_launch_gemm_pp_nt_rs_rope(const void* x, const void* W, const float* rs, const float* cos, const float* sin, void* out, int M, int N, int K,
-                                  int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols, hipStream_t st) {
-    PPEpi ep{};
-    ep.rs = rs; ep.cos = cos; ep.sin = sin; ep.seq = seq; ep.rope_cols = rope_cols;
-    return launch_pp_t<bf16_t, false, 5, 0, false, false, true>(x, W, out, nullptr, M, N, K, ldx, ldw, ldout, 1, K / PP_KT, 0, ep, st);
-}
-// out = rs (.) (x W^T) + bias (NT; EPI 0's bias add follows the row scale), bias bf16 [N]
-int lrp_launch_gemm_pp_nt_rs_bias(const void* x, const void* W, const float* rs, const void* bias, void* out, int M, int N, int K, int64_t ldx,
-                                  int64_t ldw, int64_t ldout, hipStream_t st) {
-    PPEpi ep{};
-    ep.rs = rs;
-    return launch_pp_t<bf16_t, false, 0, 0, false, false, true>(x, W, out, bias, M, N, K, ldx, ldw, ldout, 1, K / PP_KT, 0, ep, st);
-}
-// out = RoPE(rs (.) (x W^T) + bias) on the q / k head columns [0, rope_cols), rs (.) (x W^T) + bias on the rest (the host admits rope_cols a
-// multiple of 256 only: lrp_gemm_nt_rs_bias_rope_ok)
-int lrp_launch_gemm_pp_nt_rs_bias_rope(const void* x, const void* W, const float* rs, const void* bias, const float* cos, const float* sin, void* out,
-                                       int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldout, int seq, int rope_cols, hipStream_t st) {
-    PPEpi ep{};
-    ep.rs = rs; ep.cos = cos; ep.sin = sin; ep.seq = seq; ep.rope_cols = rope_cols;
-    return launch_pp_t<bf16_t, false, 6, 0, false, false, true>(x, W, out, bias, M, N, K, ldx, ldw, ldout, 1, K / PP_KT, 0, ep, st);
-}
-// out = rs (.) (s W) (NN: W [K, N] as stored)
-int lrp_launch_gemm_pp_nn_rs(const void* s, const void* W, const float* rs, void* out, int M, int N, int K, int64_t lds_, int64_t ldw,
-                             int64_t ldout, hipStream_t st) {
-    PPEpi ep{};
-    ep.rs = rs;
-    return launch_pp_t<bf16_t, true, 0, 0, false, false, true>(s, W, out, nullptr, M, N, K, lds_, ldw, ldout, 1, K / PP_KT, 0, ep, st);
-}
-// out = rs (.) (s W) + res (NN: W [K, N] as stored)
-int lrp_launch_gemm_pp_nn_rs_res(const void* s, const void* W, const float* rs, const void* res, void* out, int M, int N, int K, int64_t lds_,
-                                 int64_t ldw, int64_t ldres, int64_t ldout, hipStream_t st) {
-    PPEpi ep{};
-    ep.rs = rs; ep.res = (const bf16_t*)res; ep.ldres = ldres;
-    return launch_pp_t<bf16_t, true, 4, 0, false, false, true>(s, W, out, nullptr, M, N, K, lds_, ldw, ldout, 1, K / PP_KT, 0, ep, st);
 }

@@ -157,6 +157,16 @@ class KernelTimer:
 GEMM_TIMER = None
 
 
+def _timed(flops, tag, fn, name):
+    ev = GEMM_TIMER.span(flops, tag) if GEMM_TIMER is not None else None
+    if ev:
+        ev[0].record()
+    rc = fn()
+    if ev:
+        ev[1].record()
+    check(rc, name)
+
+
 def gemm_nt_2d(a, b, out, bias=None):
     """strict 2-D fast path used by the engine: no reshapes, no copies; row strides may exceed K."""
     M, K = a.shape
@@ -533,16 +543,6 @@ def norm_fusion_part(part):
 def norm_fused_ok(M, N, K, lda, ldb, nn, dtype):
     """the K1n entry points take this problem (bf16, N % 256 == 0, K % 64 == 0, >= 190 output tiles of the ping-pong kernel)"""
     return bool(NORM_FUSION and dtype == torch.bfloat16 and lib.lrp_gemm_norm_fused_ok(M, N, K, lda, ldb, 1 if nn else 0, _DT[dtype]))
-
-
-def _timed(flops, tag, fn, name):
-    ev = GEMM_TIMER.span(flops, tag) if GEMM_TIMER is not None else None
-    if ev:
-        ev[0].record()
-    rc = fn()
-    if ev:
-        ev[1].record()
-    check(rc, name)
 
 
 _CONST_ROWS = {}

@@ -56,6 +56,33 @@ def test_rope_gemm_predicates_on_an_odd_head_count():
     assert lib.lrp_gemm_nt_rs_rope_ok(3072, 4352, 128, 128, 128, 4352, 192, 4352 + 128, 128, BF16) == 0
 
 
+def test_fused_row_chunk_shapes_are_taken():
+    """the shapes of test_kernels_gpu.test_gemm_fused_epilogues_row_chunks: 512 rows at a row pitch of 2^21 elements (two row chunks of 256), K = 128,
+    24320 columns = 190 tiles.  Every predicate says yes, and every entry point gets past LRP_ESHAPE: with a misaligned row operand it answers
+    LRP_EALIGN, the check that follows the shape check (nothing is launched)"""
+    import lxt_amd._lib as L
+    lib, BF16 = L.lib, L.BF16
+    keep, A = _aligned()
+    M, K, N, P, seq = 512, 128, 24320, 2 ** 21, 512
+    assert lib.lrp_gemm_norm_fused_ok(M, N, K, P, K, 0, BF16) == 1 and lib.lrp_gemm_norm_fused_ok(M, N, K, P, N, 1, BF16) == 1
+    assert lib.lrp_gemm_norm_fused_ok(256, N, K, P, K, 0, BF16) == 0                                   # (one chunk alone is 95 tiles)
+    assert lib.lrp_gemm_nt_rs_rope_ok(M, N, K, P, K, N, seq, 24064, 128, BF16) == 1
+    assert lib.lrp_gemm_nt_rs_bias_rope_ok(M, N, K, P, K, N, seq, 23552, 128, BF16) == 1
+    assert lib.lrp_gemm_nt_rs_rope_ok(M, N, K, P, K, N, 384, 24064, 128, BF16) == 0                    # (256-row chunks against prompts of 384)
+    assert lib.lrp_gemm_gated_coef_ok(M, N, K, P, K, P, N, 0, BF16) == 1
+    x = A + 2
+    assert lib.lrp_gemm_gated_fwd_coef(x, A, A, A, A, M, N // 2, K, P, K, N, N // 2, 1e-10, 0.0, 0, BF16, None) == -2
+    assert lib.lrp_gemm_gated_bwd_coef(x, A, A, A, M, N, K, P, N, 2 * N, 2 * N, BF16, None) == -2
+    assert lib.lrp_gemm_res_ssq(x, A, A, A, A, M, N, K, P, K, N, N, M, A, N, BF16, None) == -2
+    assert lib.lrp_gemm_nt_rs(x, A, A, A, M, N, K, P, K, N, BF16, None) == -2
+    assert lib.lrp_gemm_nt_rs_rope(x, A, A, A, A, A, M, N, K, P, K, N, seq, 24064, 128, BF16, None) == -2
+    assert lib.lrp_gemm_nt_rs_bias(x, A, A, A, A, M, N, K, P, K, N, BF16, None) == -2
+    assert lib.lrp_gemm_nt_rs_bias_rope(x, A, A, A, A, A, A, M, N, K, P, K, N, seq, 23552, 128, BF16, None) == -2
+    assert lib.lrp_gemm_nn_rs(x, A, A, A, M, N, K, P, N, N, BF16, None) == -2
+    assert lib.lrp_gemm_nn_rs_res(x, A, A, A, A, M, N, K, P, N, N, N, BF16, None) == -2
+    del keep
+
+
 def _site_operands(rows, nq, nk, d, seq):
     e = lambda c, dt=BF: torch.zeros(rows, c, dtype=dt)      # noqa: E731
     tab = torch.zeros(seq, d)

@@ -523,6 +523,135 @@ def test_gemm_norm_fused_epilogues(ops, M, H, K, I):
     assert torch.equal(inpl, Gh)
 
 
+# the nine ops wrappers whose C entry points walk row chunks with a fused epilogue (gemm.hip: launch_fused_rows / advance)
+FUSED_FORMS = ["gemm_gated_fwd_coef", "gemm_gated_bwd_coef", "gemm_res_ssq", "gemm_nt_rs", "gemm_nt_rs_rope", "gemm_nt_rs_bias", "gemm_nt_rs_bias_rope",
+               "gemm_nn_rs", "gemm_nn_rs_res"]
+FUSED_BAR = 1e-2        # nmax vs fp64 of every fused form: the bar of test_gemm_norm_fused_epilogues, test_gemm_nt_rs_rope, test_gemm_gated_coef_epilogues
+                        # (m, stash, Agu on the stored stash) and test_qwen_kernels_gpu.test_gemm_nt_rs_bias_and_bias_rope
+
+
+@pytest.mark.parametrize("form", FUSED_FORMS)
+def test_gemm_fused_epilogues_row_chunks(ops, form):
+    """every fused-epilogue entry point across a row-chunk boundary.  Two chunks without a large problem: the row operand is a [512, 128] view with
+    a row pitch of 2^21 elements (2 GiB reserved, 128 KiB written), for which one launch addresses ((2^30 - 1) // 2^21) // 256 * 256 = 256 rows, so the
+    library issues rows [0, 256) and [256, 512) separately and has to move every row-indexed operand of the form (row scales, residual, stash, m,
+    raw, the ssq columns, and -- seq = 512 -- the RoPE tables by 256 positions) to the second chunk.  Width 24320 = 95 tile columns x 2 tile rows =
+    the 190 tiles the fused forms ask for.  Reference: the SAME wrapper on a contiguous copy of the 512 rows (pitch 128: one chunk, one launch), to
+    which each half of every output must be bit-equal; rows 0, 255, 256, 511 against fp64 under FUSED_BAR.  (The halves cannot be run alone
+    through the wrappers: 256 rows x 24320 columns are 95 tiles, which every one of these entry points refuses.)"""
+    bf = torch.bfloat16
+    M, K, N, pitch, seq, d = 512, 128, 24320, 2 ** 21, 512, 128
+    g = torch.Generator(device="cuda").manual_seed(11)
+    mk = lambda *sh, sc=1.0: (torch.randn(*sh, generator=g, device="cuda") * sc).bfloat16()                    # noqa: E731
+    nan = lambda *sh, dtype=bf: torch.full(sh, float("nan"), dtype=dtype, device="cuda")                     # noqa: E731
+    buf = torch.empty((M - 1) * pitch + K, dtype=bf, device="cuda")
+    try:
+        a = buf.as_strided((M, K), (pitch, 1))
+        a.copy_(mk(M, K))
+        assert M * a.stride(0) >= 2 ** 30
+        rs = torch.rand(M, generator=g, device="cuda") + 0.5
+        nn = form in ("gemm_gated_bwd_coef", "gemm_nn_rs", "gemm_nn_rs_res")
+        W = mk(K, N, sc=K ** -0.5) if nn else mk(N, K, sc=K ** -0.5)
+        res, bias = mk(M, N), mk(N)
+        inv = 1.0 / (10000.0 ** (torch.arange(0, d, 2, dtype=torch.float32) / d))
+        emb = torch.cat((torch.arange(seq, dtype=torch.float32)[:, None] * inv[None],) * 2, -1)
+        cos, sin = emb.cos().to(bf).float().cuda().contiguous(), emb.sin().to(bf).float().cuda().contiguous()
+        rope_cols = {"gemm_nt_rs_rope": 24064, "gemm_nt_rs_bias_rope": 23552}.get(form, 0)
+        if form == "gemm_gated_fwd_coef":             # I = 12160: [M, 2 I = 24320] from the interleaved gate/up weight
+            W = ops.interleave_gate_up(W[: N // 2].contiguous(), W[N // 2:].contiguous())
+        # gemm_gated_bwd_coef at I = 24320: any stash will do, the epilogue is Gm (*) stash
+        stash = mk(M, 2 * N, sc=0.5) if form == "gemm_gated_bwd_coef" else None
+
+        # the form's own gate takes the shape (the same values, without a GPU: test_kernel_edges_cpu.test_fused_row_chunk_shapes_are_taken)
+        if form == "gemm_gated_fwd_coef":
+            pass                                       # (ops.gated_coef_ok speaks for the forward AND the down dgrad of one layer; the entry point's own
+                                                       # check is the call below, which raises on LRP_ESHAPE)
+        elif form == "gemm_gated_bwd_coef":
+            assert ops.gated_coef_ok(M, N, K, pitch, K, pitch, N, "silu", bf)
+        elif form == "gemm_nt_rs_rope":
+            assert ops.gemm_nt_rs_rope_ok(a, W, nan(M, N), seq, rope_cols, d)
+        elif form == "gemm_nt_rs_bias_rope":
+            assert ops.gemm_nt_rs_bias_rope_ok(a, W, nan(M, N), seq, rope_cols, d)
+        else:
+            assert ops.norm_fused_ok(M, N, K, pitch, W.stride(0), nn, bf)
+
+        def run(x):
+            """the wrapper on the row operand x [512, 128] -> every output it writes, each pre-filled with NaN"""
+            if form == "gemm_gated_fwd_coef":
+                return ops.gemm_gated_fwd_coef(x, W, nan(M, N), nan(M, N // 2), 1e-10, 0.0, "silu", rs=rs)
+            if form == "gemm_gated_bwd_coef":
+                return (ops.gemm_gated_bwd_coef(x, W, stash, nan(M, 2 * N)),)
+            if form == "gemm_res_ssq":
+                out, ssq, raw = nan(M, N), nan(N // 64, M, dtype=torch.float32), nan(M, N)
+                ops.gemm_res_ssq(x, W, res, out, ssq, raw=raw)
+                return out, ssq.T, raw                 # (ssq transposed: rows of the problem first, as every other output)
+            if form == "gemm_nt_rs":
+                return (ops.gemm_nt_rs(x, W, rs, nan(M, N)),)
+            if form == "gemm_nt_rs_rope":
+                return (ops.gemm_nt_rs_rope(x, W, rs, cos, sin, nan(M, N), seq, rope_cols, d),)
+            if form == "gemm_nt_rs_bias":
+                return (ops.gemm_nt_rs_bias(x, W, rs, bias, nan(M, N)),)
+            if form == "gemm_nt_rs_bias_rope":
+                return (ops.gemm_nt_rs_bias_rope(x, W, rs, bias, cos, sin, nan(M, N), seq, rope_cols, d),)
+            if form == "gemm_nn_rs":
+                return (ops.gemm_nn_rs(x, W, rs, nan(M, N)),)
+            return (ops.gemm_nn_rs_res(x, W, rs, res, nan(M, N)),)
+
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        outs = run(a)
+        ev1.record()
+        one = run(a.contiguous())
+        torch.cuda.synchronize()
+        print(f"[{form} two chunks] {ev0.elapsed_time(ev1):.2f} ms")
+        for i, (o, r) in enumerate(zip(outs, one)):
+            assert not torch.isnan(o).any(), f"output {i}: NaN left"
+            assert torch.equal(o[:256], r[:256]), f"output {i}: first chunk"
+            assert torch.equal(o[256:], r[256:]), f"output {i}: second chunk"
+
+        rows = torch.tensor([0, 255, 256, 511], device="cuda")
+        z = f64(a[rows]) @ (f64(W) if nn else f64(W).T)
+        sc = rs.double()[rows][:, None]
+
+        def rope64(y):
+            yr = y[:, :rope_cols].view(len(rows), rope_cols // d, d)
+            c, s_ = cos.double()[rows % seq][:, None, :], sin.double()[rows % seq][:, None, :]
+            rot = torch.cat((-yr[..., d // 2:], yr[..., : d // 2]), -1)
+            return torch.cat(((yr * c + rot * s_).view(len(rows), rope_cols), y[:, rope_cols:]), 1)
+
+        if form == "gemm_gated_fwd_coef":
+            I = N // 2
+            zv = (sc * z).view(len(rows), I // 32, 2, 32)
+            g64, u64 = zv[:, :, 0].reshape(-1, I), zv[:, :, 1].reshape(-1, I)
+            y64 = _act64(g64, "silu")
+            live = g64.abs() > 1e-3                  # (the stabilised ratio is compared away from its pole, as test_gemm_gated_coef_epilogues does)
+            cg, cu = _coef_split(outs[0][rows], I)
+            assert nmax(outs[1][rows], y64 * u64) < FUSED_BAR
+            assert nmax(torch.where(live, cg.double(), torch.zeros_like(g64)), torch.where(live, 0.5 * u64 * y64 / (g64 + 1e-10), torch.zeros_like(g64))) < FUSED_BAR
+            assert nmax(torch.where(u64.abs() > 1e-3, cu.double(), 0.5 * y64), 0.5 * y64) < FUSED_BAR
+        elif form == "gemm_gated_bwd_coef":
+            cg, cu = _coef_split(stash[rows], N)
+            av = outs[0][rows].view(len(rows), N // 32, 2, 32)
+            assert nmax(av[:, :, 0].reshape(-1, N), z * cg.double()) < FUSED_BAR and nmax(av[:, :, 1].reshape(-1, N), z * cu.double()) < FUSED_BAR
+        elif form == "gemm_res_ssq":
+            assert nmax(outs[0][rows], f64(res[rows]) + z) < FUSED_BAR and nmax(outs[2][rows], z) < FUSED_BAR
+            ssq_ref = (outs[0][rows].double() ** 2).view(len(rows), N // 64, 64).sum(-1)        # from the STORED rows: exact up to fp32 summation
+            assert torch.allclose(outs[1][rows].double(), ssq_ref, rtol=1e-5, atol=1e-6)
+        else:
+            ref = sc * z
+            if "bias" in form:
+                ref = ref + f64(bias)[None]
+            if rope_cols:
+                ref = rope64(ref)
+            if form == "gemm_nn_rs_res":
+                ref = ref + f64(res[rows])
+            assert nmax(outs[0][rows], ref) < FUSED_BAR
+    finally:
+        del buf
+        a = outs = one = None
+        torch.cuda.empty_cache()
+
+
 def test_gemm_batched_and_f32_out(ops):
     a, b = rnd(3, 70, 96, seed=4), rnd(3, 50, 96, seed=5)
     assert nmax(ops.gemm_nt(a, b), f64(a) @ f64(b).transpose(1, 2)) < 2e-5
