@@ -182,6 +182,7 @@ int lrp_head_rmsnorm_fwd(const void* x, const void* w, void* y, float* rstd, int
                          float eps, float w_offset, int dtype, void* stream);
 int lrp_head_rmsnorm_bwd(const void* G, const void* w, const float* rstd, void* out, int64_t rows, int heads, int d, int64_t ldg,
                          int64_t ldo, float w_offset, int dtype, void* stream);
+/* (lrp_add_rmsnorm_fwd: y == NULL writes hsum_out and rstd only -- the caller applies the norm elsewhere, e.g. in a GEMM epilogue; w is then not read) */
 int lrp_add_rmsnorm_fwd(const void* h, const void* branch, const void* w, void* hsum_out,
                         void* y, float* rstd, int M, int H, float eps, float w_offset,
                         int dtype, void* stream);
@@ -535,4 +536,5 @@ int lrp_moe_gate_up_dgrad(const void* Agu, const void* Wgu, const int* plan, voi
 #endif
 /* the per-head read-out of the latent feature attribution (same ABI version, same conventions; a header of its own) */
 #include "lrp_hip_latent.h"
+#include "lrp_hip_moe_router.h"
 #endif /* LRP_HIP_H */

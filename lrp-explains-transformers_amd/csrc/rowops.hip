@@ -53,6 +53,7 @@ __global__ void add_rmsnorm_fwd_kernel(const T* h, const T* branch, const T* w, 
     ss = block_sum(ss, red);
     const float rs = rsqrtf(ss / (float)H + eps);
     if (threadIdx.x == 0) rstd[row] = rs;
+    if (!y) return;    // (block-uniform: the caller wants the residual sum and rstd only)
     __syncthreads();   // hsum_out written by this block is re-read below (same threads, same addresses)
     const T* src = ps ? ps : ph;
     for (int c = threadIdx.x * W; c < H; c += blockDim.x * W) {
@@ -419,7 +420,7 @@ __global__ void head_rmsnorm_bwd_kernel(const T* G, const T* w, const float* rst
 
 extern "C" int lrp_add_rmsnorm_fwd(const void* h, const void* branch, const void* w, void* hsum_out, void* y,
                                    float* rstd, int M, int H, float eps, float w_offset, int dtype, void* stream) {
-    if (!h || !w || !y || !rstd || M < 0 || H < 1) return LRP_EINVAL;
+    if (!h || !rstd || (!w && y) || M < 0 || H < 1) return LRP_EINVAL;          // (y == NULL: hsum_out and rstd only; w is then not read)
     if (M == 0) return LRP_OK;
     hipStream_t st = (hipStream_t)stream;
     DISPATCH_T(dtype, {

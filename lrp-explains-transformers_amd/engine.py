@@ -210,6 +210,23 @@ def fused_qkv_fwd(h, rstd1, Wqkv, cos, sin, S, meta, alloc, explicit=False, bias
     return qkv, ops.rope_fwd(qkv, alloc("qkr", M, nqk, 0, h.dtype), cos, sin, S, nq + nk, d)
 
 
+def fused_attn_fwd(h, qkv, qkr, W, B, S, meta, alloc, row_iv=None, explicit=False):
+    """the attention half of fused_layer_fwd (the MoE driver runs it on its own): attention, h1 = h + o Wo^T with its sums of squares in the
+    epilogue -> (dict(o, lse, h1, a, rstd2), ssq)"""
+    nq, nk, d, rms_eps, _, scale = meta
+    M, H, dt = B * S, h.shape[1], h.dtype
+    new = lambda tag, cols: alloc(tag, M, cols, 0, dt)      # noqa: E731
+    v = qkv[:, (nq + nk) * d:]
+    v_t = ops.transpose_heads(v, B, S, nk, d) if ops.attn_needs_transposed(v, d) else None
+    st = dict(o=new("o", nq * d), lse=alloc("lse", B * nq, S, 0, torch.float32).view(B, nq, S))
+    ops.attn_fwd(qkr[:, : nq * d], qkr[:, nq * d:], v, v_t, st["o"], st["lse"], B, S, nq, nk, d, scale, True, 0, row_iv=row_iv)
+    ssq = alloc("ssq", H // 64, M, 0, torch.float32)
+    st.update(h1=new("h1", H), a=new("a", H) if explicit else None)
+    ops.gemm_res_ssq(st["o"], W["wo"], h, st["h1"], ssq, raw=st["a"])
+    st["rstd2"] = ops.rms_rstd(ssq, M, H, rms_eps, alloc("rstd2", 1, M, 0, torch.float32)[0])
+    return st, ssq
+
+
 def fused_layer_fwd(h, rstd1, qkv, qkr, W, cos, sin, B, S, meta, alloc, row_iv=None, explicit=False, eps=(EFFICIENT["act"], EFFICIENT["lin"]),
                     chain=True):
     """attention, h1 = h + o Wo^T with its sums of squares in the epilogue, the gate/up GEMM on rstd2 (.) h1 with the coefficient stash of the
@@ -220,14 +237,8 @@ def fused_layer_fwd(h, rstd1, qkv, qkr, W, cos, sin, B, S, meta, alloc, row_iv=N
     M, H, I, dt = B * S, h.shape[1], W["wd"].shape[1], h.dtype
     new = lambda tag, cols, pitch=None: alloc(tag, M, cols, (pitch or cols) - cols, dt)      # noqa: E731
     vec = lambda tag: alloc(tag, 1, M, 0, torch.float32)[0]                                  # noqa: E731
-    v = qkv[:, (nq + nk) * d:]
-    v_t = ops.transpose_heads(v, B, S, nk, d) if ops.attn_needs_transposed(v, d) else None
-    st = dict(o=new("o", nq * d), lse=alloc("lse", B * nq, S, 0, torch.float32).view(B, nq, S))
-    ops.attn_fwd(qkr[:, : nq * d], qkr[:, nq * d:], v, v_t, st["o"], st["lse"], B, S, nq, nk, d, scale, True, 0, row_iv=row_iv)
-    ssq, pt = alloc("ssq", H // 64, M, 0, torch.float32), fused_layout(H, I, nq, nk, d, dt)
-    st.update(h1=new("h1", H), a=new("a", H) if explicit else None)
-    ops.gemm_res_ssq(st["o"], W["wo"], h, st["h1"], ssq, raw=st["a"])
-    st["rstd2"] = ops.rms_rstd(ssq, M, H, rms_eps, vec("rstd2"))
+    st, ssq = fused_attn_fwd(h, qkv, qkr, W, B, S, meta, alloc, row_iv, explicit)
+    pt = fused_layout(H, I, nq, nk, d, dt)
     st["gu"], m = ops.gemm_gated_fwd_coef(st["h1"], W["wgu"], new("gu", 2 * I), new("m", I, pt["m"]), *eps, act, rs=st["rstd2"])
     st["m"] = m
     if chain:
@@ -247,12 +258,22 @@ def fused_layer_bwd(G, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm=
     transposed, the head norms' row-constant scale, the GQA group sums -- in place of gqa_reduce_rope + gqa_reduce.
     heads: a HeadSink (explain(heads=...)) that reads the per-head relevance off the buffers while they are live; None: nothing is launched.
     attn_map: an AttnMapSink (explain(attn_map=...)), the token-to-token maps off the same buffers; None: nothing is launched."""
-    nq, nk, d, _, _, scale = meta
-    M, H, I, dt, nqk, nqkv = B * S, G.shape[1], W["wd"].shape[1], G.dtype, (nq + nk) * d, (nq + 2 * nk) * d
+    nq, nk, d = meta[:3]
+    M, H, I, dt = B * S, G.shape[1], W["wd"].shape[1], G.dtype
     pt = fused_layout(H, I, nq, nk, d, dt)
     new = lambda tag, cols, pitch=None: alloc(tag, M, cols, (pitch or cols) - cols, dt)      # noqa: E731
     Agu = ops.gemm_gated_bwd_coef(G, W["wd"], st["gu"], new("Agu", 2 * I, pt["Agu"]))
     Gs1 = ops.gemm_nn_rs_res(Agu, W["wgu"], st["rstd2"], G, new("Gs1", H))
+    return fused_attn_bwd(Gs1, st, W, cos, sin, B, S, meta, alloc, row_iv, qk_norm, heads, attn_map)
+
+
+def fused_attn_bwd(Gs1, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm=None, heads=None, attn_map=None):
+    """the attention half of fused_layer_bwd (the MoE driver runs it on its own): Gs1, the gradient at h1 -> G at the layer's input; everything
+    from the o projection's dgrad on.  Arguments as fused_layer_bwd's"""
+    nq, nk, d, _, _, scale = meta
+    M, H, dt, nqk, nqkv = B * S, Gs1.shape[1], Gs1.dtype, (nq + nk) * d, (nq + 2 * nk) * d
+    pt = fused_layout(H, 0, nq, nk, d, dt)          # (Aqkv's pitch does not depend on I)
+    new = lambda tag, cols, pitch=None: alloc(tag, M, cols, (pitch or cols) - cols, dt)      # noqa: E731
     Gho = ops.gemm_nn_rs(Gs1, W["wo"], alloc("half", 1, M, 0, torch.float32)[0], new("Gho", nq * d))      # ("half": the allocator's 1/2 rows)
     q, k, v = st["qkr"][:, : nq * d], st["qkr"][:, nq * d:], st["qkv"][:, nqk:]
     D = alloc("D", B * nq, S, 0, torch.float32).view(B, nq, S)
@@ -289,11 +310,12 @@ FUSED_SCRATCH = frozenset(("ssq", "m", "half", "Agu", "Gs1", "Gho", "D", "Aqkv",
 def pack_flat(top, layer, n_layers, dtype, device):
     """ONE flat buffer holds every weight of a model (a multi-GPU start-up is then a single broadcast of it, lxt_amd.dist.broadcast_weights).
     top / layer: {name: (shape, row pitch or None)} of the model-wide weights and of one layer's, in storage order; the buffer's size follows
-    from these lists alone.  -> (flat, {name: view}, one {name: view} per layer).  Every view starts 128-byte aligned; with a row pitch it is a
+    from these lists alone; layer may be a list of n_layers specs (layers of different forms: the MoE driver).  -> (flat, {name: view}, one
+    {name: view} per layer).  Every view starts 128-byte aligned; with a row pitch it is a
     [rows, cols] view of [rows, pitch] storage.  device="meta" gives the layout without memory."""
     up = lambda n: (n + 63) // 64 * 64                                   # noqa: E731
     stored = lambda shape, pitch: (*shape[:-1], pitch or shape[-1])      # noqa: E731  (the [rows, pitch] block behind a view)
-    specs = [top] + [layer] * n_layers
+    specs = [top] + (list(layer) if isinstance(layer, (list, tuple)) else [layer] * n_layers)
     flat = torch.empty(sum(up(math.prod(stored(*e))) for spec in specs for e in spec.values()), device=device, dtype=dtype)
     views, o = [], 0
     for spec in specs:
@@ -661,17 +683,7 @@ class LlamaLRP:
         self.lm_head = put_rows(top["lm_head"], W["lm_head"]) if "lm_head" in top else self.embed      # (cfg["tied"]: one stored copy serves both)
         self.lm_head_t = None                        # [H, V] copy, made on the first dense-seed explanation
         for Lw, L in zip(self.layers, W["layers"]):
-            for k in ("ln1", "ln2", "wo", "wd") + (("qn", "kn") if "qn" in Lw else ()):
-                put_rows(Lw[k], L[k])
-            if "bqkv" in Lw:
-                put_rows(Lw["bqkv"], L["bq"], L["bk"], L["bv"])
-            put_rows(Lw["wqkv"], L["wq"], L["wk"], L["wv"])
-            put_gate_up(Lw["wgu"], L["wg"], L["wu"])
-            if self.folded:          # (in place, on the weights as stored: the product sees the storage dtype's rounding of W)
-                fold_rows(Lw["wqkv"], (Lw["wqkv"],), L["ln1"])
-                fold_rows(Lw["wgu"], (Lw["wgu"],), L["ln2"])
-                Lw["ln1"].fill_(1.0)
-                Lw["ln2"].fill_(1.0)
+            self._put_layer(Lw, L)
         self.attn_t = ops.attn_needs_transposed(self.embed, hd)
         inv = cfg.get("inv_freq")                    # scaled rope types: HF's own frequencies (config_from_hf)
         if inv is None:
@@ -679,6 +691,20 @@ class LlamaLRP:
         self.cos, self.sin = rope_tables(inv, float(cfg.get("attention_scaling", 1.0)), max_seq, dtype, dev)
         self.max_seq = max_seq
         torch.cuda.synchronize(dev)
+
+    def _put_layer(self, Lw, L):
+        """one layer's weights L (the caller's tensors) into its views Lw of the flat buffer"""
+        for k in ("ln1", "ln2", "wo", "wd") + (("qn", "kn") if "qn" in Lw else ()):
+            put_rows(Lw[k], L[k])
+        if "bqkv" in Lw:
+            put_rows(Lw["bqkv"], L["bq"], L["bk"], L["bv"])
+        put_rows(Lw["wqkv"], L["wq"], L["wk"], L["wv"])
+        put_gate_up(Lw["wgu"], L["wg"], L["wu"])
+        if self.folded:          # (in place, on the weights as stored: the product sees the storage dtype's rounding of W)
+            fold_rows(Lw["wqkv"], (Lw["wqkv"],), L["ln1"])
+            fold_rows(Lw["wgu"], (Lw["wgu"],), L["ln2"])
+            Lw["ln1"].fill_(1.0)
+            Lw["ln2"].fill_(1.0)
 
     # ops.linear_fwd / ops.linear_dgrad pick the kernel by row count: W-streaming small-M kernels and the split-K skinny path for the
     # one-row-per-prompt top layer and the LM head, the 256x256 ping-pong GEMM (NT forward, NN backward) for M = B*S rows
@@ -846,18 +872,10 @@ class LlamaLRP:
         top = bool(stash) and stash[-1].get("top", False)
         return dict(stash=stash, last=last, row_iv=row_iv, **head_fwd(ar, h_prev, branch, top, last, self.norm, self.lm_head, c["rms_eps"]))
 
-    # ---------------------------------------------------------------------------------------------
-    def backward(self, fw, emb, idx, B, S, layer_relevance=False, seed=None, latent=frozenset(), heads=None, attn_map=None):
-        """-> (G at the embedding, layer_R rows or None, dict of the token-summed latent read-outs: R_resid [L+1, B, H] / R_mlp [L, B, I]);
-        heads: a HeadSink that collects the per-head read-outs layer by layer, or None; attn_map: an AttnMapSink, likewise"""
-        c, E = self.cfg, self.eps
-        H, I, d, nq, nk = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"]
-        M, rep = B * S, nq // nk
-        dev, dt = self.device, self.dtype
-        nqk, nqkv = (nq + nk) * d, (nq + 2 * nk) * d
-        scale = d ** -0.5
-        ar = self._arena
-        # LM head eps rule + final-norm identity rule on the single explained row of each prompt
+    def _head_bwd(self, fw, idx, B, seed, layer_relevance):
+        """LM head eps rule + final-norm identity rule on the single explained row of each prompt, then add2 at h_L = h1 + dn and the eps scale
+        of the last down_proj, still one row per prompt -> (Gh_last, Gs_last, A_last, rel_last or None)"""
+        E, H, dev, dt, ar = self.eps, self.cfg["hidden"], self.device, self.dtype, self._arena
         if seed is None:
             Gh_last = ops.head_seed(self.lm_head, fw["logits"], idx, self.norm, fw["rstd_f"], ar.new("Gh_last", B, H), 0.0, E["lin"])
         else:
@@ -874,6 +892,20 @@ class LlamaLRP:
         rel_last = ar.f32("rel_last", B) if layer_relevance else None
         ops.rmsnorm_bwd_add2(Gh_last, None, None, None, fw["hL_last"], fw["dn_last"], Gs_last, A_last, rel_last,
                              0.0, E["add"], E["lin"])
+        return Gh_last, Gs_last, A_last, rel_last
+
+    # ---------------------------------------------------------------------------------------------
+    def backward(self, fw, emb, idx, B, S, layer_relevance=False, seed=None, latent=frozenset(), heads=None, attn_map=None):
+        """-> (G at the embedding, layer_R rows or None, dict of the token-summed latent read-outs: R_resid [L+1, B, H] / R_mlp [L, B, I]);
+        heads: a HeadSink that collects the per-head read-outs layer by layer, or None; attn_map: an AttnMapSink, likewise"""
+        c, E = self.cfg, self.eps
+        H, I, d, nq, nk = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"]
+        M, rep = B * S, nq // nk
+        dev, dt = self.device, self.dtype
+        nqk, nqkv = (nq + nk) * d, (nq + 2 * nk) * d
+        scale = d ** -0.5
+        ar = self._arena
+        Gh_last, Gs_last, A_last, rel_last = self._head_bwd(fw, idx, B, seed, layer_relevance)
         nL, lat = len(self.layers), {}
         if "resid" in latent:          # index L: the head's explained rows, the gradient rel_last is formed from (S = 1)
             lat["R_resid"] = torch.empty(nL + 1, B, H, device=dev, dtype=torch.float32)
@@ -1044,11 +1076,13 @@ class LlamaLRP:
         return Gs, layer_R, lat
 
     # ---------------------------------------------------------------------------------------------
-    def _run(self, input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, latent=frozenset(), heads=frozenset(), attn_map=(False, ())):
-        """forward + backward + read-out on the current stream: library launches only, no host synchronisation (capturable)"""
+    def _run(self, input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, latent=frozenset(), heads=frozenset(), attn_map=(False, ()),
+             **opts):
+        """forward + backward + read-out on the current stream: library launches only, no host synchronisation (capturable); opts: further
+        keywords of a subclass's forward / backward (Qwen3MoeLRP: experts)"""
         if emb is None:
             emb = self.embed.index_select(0, input_ids.reshape(-1))
-        fw = self.forward(emb, B, S, row_iv, keep_m="mlp" in latent)
+        fw = self.forward(emb, B, S, row_iv, keep_m="mlp" in latent, **opts)
         if idx is None:
             # (a dense seed explains no single logit; idx / logit then report the arg-max for convenience)
             idx, _ = ops.argmax_rows(fw["logits"])
@@ -1060,7 +1094,7 @@ class LlamaLRP:
         if attn_map[0] or attn_map[1]:
             c = self.cfg
             am = AttnMapSink(attn_map, len(self.layers), B, S, c["n_heads"], c["n_kv"], c["head_dim"], self.meta[-1], self.device)
-        G, layer_R, lat = self.backward(fw, emb, idx, B, S, layer_relevance or "trace" in latent, seed=seed, latent=latent, heads=hs, attn_map=am)
+        G, layer_R, lat = self.backward(fw, emb, idx, B, S, layer_relevance or "trace" in latent, seed=seed, latent=latent, heads=hs, attn_map=am, **opts)
         out = explanation(emb, G, idx, fw["logits"], B, S, return_G)
         if layer_relevance:
             rows = [layer_R[0]] + [r.view(B, S).sum(1) for r in layer_R[1:]]

@@ -1,0 +1,338 @@
+"""Whole-model AttnLRP engine for Qwen3-MoE (Qwen3MoeForCausalLM; Qwen3-30B-A3B and the like), efficient placement
+(ref wiring: lxt/efficient/models/qwen3_moe.py; the router is left to plain autograd there).
+
+A layer is QwenLRP's Qwen3 attention half -- per-head q / k RMSNorm, on the fused launch sequence where its GEMMs take the shape (bf16, M = B S
+rows: engine.fused_qkv_fwd / fused_attn_fwd / fused_attn_bwd), else kernel by kernel (fp32, the parity engine, and small row counts) -- and
+then either the dense gated MLP (mlp_only_layers / decoder_sparse_step) or the sparse block:
+    forward   xn = rstd2 (.) ln2 (.) h1 (row kernel; ln2 is NOT folded into the expert weights -- they are read as stored, no copy),
+              logits = xn Wr^T, ops.moe_router_fwd -> (idx, w, lse), ops.MoePlan, moe_gate_up_fwd, moe_down_fwd, moe_combine(y, plan, w), h1 + out
+    backward  moe_down_dgrad -> (Agu, G_w);  G_xn = moe_combine(moe_gate_up_dgrad(Agu)) + moe_router_bwd(G_w) Wr;  the norm's identity rule
+              (rstd held constant) and the residual: Gs1 = G + ln2 (.) rstd2 (.) G_xn
+Stash per MoE layer: the coefficients [T k, 2 I] and m [T k, I], the int32 plan, and the router's logits, lse, idx, w.
+explain(experts=True) adds R_expert [L, B, E] (ops.moe_expert_relevance: `routing_weights * routing_weights.grad` scattered by expert and
+summed over a prompt's tokens; = 1/2 of the block-output relevance when summed over the experts) and expert_index [L, B, S, k]."""
+import torch
+
+from . import engine as E
+from . import engine_qwen as Q
+from . import ops
+from .efficient.moe import _ACTS
+
+
+def config_from_hf(hf_cfg):
+    """HF Qwen3MoeConfig -> engine cfg.  What the driver does not implement is refused here, before any kernel runs."""
+    mt = getattr(hf_cfg, "model_type", None)
+    if mt != "qwen3_moe":
+        raise NotImplementedError(f"Qwen3MoeLRP drives Qwen3-MoE decoders only (model_type={mt!r}); dense Qwen2 / Qwen3 run on "
+                                  "lxt_amd.engine_qwen.QwenLRP, Llama on lxt_amd.engine.LlamaLRP, other families through "
+                                  "lxt_amd.efficient.monkey_patch")
+    nL = hf_cfg.num_hidden_layers
+    types = getattr(hf_cfg, "layer_types", None)
+    if getattr(hf_cfg, "use_sliding_window", False) or (types is not None and any(t != "full_attention" for t in list(types)[:nL])):
+        raise NotImplementedError("Qwen3MoeLRP: sliding-window layers (use_sliding_window=True / layer_types other than 'full_attention') are "
+                                  "not supported by the fused driver (use the monkey_patch drop-in path)")
+    if getattr(hf_cfg, "attention_bias", False) or getattr(hf_cfg, "mlp_bias", False):
+        raise NotImplementedError("Qwen3MoeLRP: attention_bias / mlp_bias = True are not supported by the fused driver (use the monkey_patch "
+                                  "drop-in path)")
+    act = getattr(hf_cfg, "hidden_act", "silu")
+    act = "gelu_tanh" if act == "gelu_pytorch_tanh" else act
+    if act not in _ACTS:
+        raise NotImplementedError(f"Qwen3MoeLRP: activation {act!r} is not served (the grouped expert kernels implement {', '.join(_ACTS)})")
+    H, Im, Ne, k = hf_cfg.hidden_size, hf_cfg.moe_intermediate_size, hf_cfg.num_experts, hf_cfg.num_experts_per_tok
+    if H % 128 or Im % 128:
+        raise NotImplementedError(f"Qwen3MoeLRP: hidden size {H} and moe_intermediate_size {Im} must be multiples of 128 (the grouped GEMMs' "
+                                  "128 x 128 tiles)")
+    if Ne > ops.ROUTER_EMAX or k > ops.ROUTER_KMAX or not 1 <= k <= Ne:
+        raise NotImplementedError(f"Qwen3MoeLRP: top-{k} of {Ne} experts; the routing plan serves at most {ops.ROUTER_EMAX} experts and the "
+                                  f"router kernel at most {ops.ROUTER_KMAX} per token")
+    kind = E.rope_kind(hf_cfg)
+    if kind not in E._STATIC_ROPE:
+        raise NotImplementedError(f"Qwen3MoeLRP: rope_type {kind!r} (sequence-length dependent frequencies) is not supported")
+    hd = getattr(hf_cfg, "head_dim", None) or H // hf_cfg.num_attention_heads
+    rp = getattr(hf_cfg, "rope_parameters", None)
+    theta = rp.get("rope_theta") if isinstance(rp, dict) else None
+    if theta is None:
+        theta = getattr(hf_cfg, "rope_theta", 10000.0)
+    only, step = set(getattr(hf_cfg, "mlp_only_layers", None) or ()), int(getattr(hf_cfg, "decoder_sparse_step", 1))
+    cfg = dict(hidden=H, inter=hf_cfg.intermediate_size, n_layers=nL, n_heads=hf_cfg.num_attention_heads, n_kv=hf_cfg.num_key_value_heads,
+               head_dim=hd, vocab=hf_cfg.vocab_size, rope_theta=float(theta), rms_eps=float(hf_cfg.rms_norm_eps), act=act, family=mt,
+               qkv_bias=False, qk_norm=True, tied=bool(getattr(hf_cfg, "tie_word_embeddings", False)), moe_inter=Im, n_experts=Ne, top_k=k,
+               norm_topk=bool(getattr(hf_cfg, "norm_topk_prob", False)),
+               moe_layers=tuple(li not in only and Ne > 0 and (li + 1) % step == 0 for li in range(nL)))      # (HF Qwen3MoeDecoderLayer.__init__)
+    if kind != "default":
+        from transformers.modeling_rope_utils import ROPE_INIT_FUNCTIONS
+        inv_freq, att = ROPE_INIT_FUNCTIONS[kind](hf_cfg, "cpu")
+        cfg["inv_freq"], cfg["attention_scaling"] = inv_freq.float().cpu(), float(att)
+    return cfg
+
+
+def weights_from_hf(model):
+    """plain (cfg, W) view of a HF Qwen3MoeForCausalLM (no copies).  A MoE layer holds wr (the router), wgu_e [E, 2 I, H] and wd_e [E, H, I]
+    (HF's gate_up_proj / down_proj) in place of wg / wu / wd"""
+    cfg = config_from_hf(model.config)
+    m = model.model
+    W = dict(embed=m.embed_tokens.weight.detach(), norm=m.norm.weight.detach(), layers=[])
+    if model.lm_head.weight.data_ptr() != m.embed_tokens.weight.data_ptr():
+        W["lm_head"], cfg["tied"] = model.lm_head.weight.detach(), False
+    else:
+        cfg["tied"] = True
+    for li, L in enumerate(m.layers):
+        a, mlp = L.self_attn, L.mlp
+        if a.o_proj.bias is not None or a.q_proj.bias is not None:
+            raise NotImplementedError("Qwen3MoeLRP: a bias on the attention projections is not supported by the fused driver")
+        Lw = dict(ln1=L.input_layernorm.weight.detach(), ln2=L.post_attention_layernorm.weight.detach(), wq=a.q_proj.weight.detach(),
+                  wk=a.k_proj.weight.detach(), wv=a.v_proj.weight.detach(), wo=a.o_proj.weight.detach(), qn=a.q_norm.weight.detach(),
+                  kn=a.k_norm.weight.detach())
+        if cfg["moe_layers"][li]:
+            Lw.update(wr=mlp.gate.weight.detach(), wgu_e=mlp.experts.gate_up_proj.detach(), wd_e=mlp.experts.down_proj.detach())
+        else:
+            if any(t.bias is not None for t in (mlp.gate_proj, mlp.up_proj, mlp.down_proj)):
+                raise NotImplementedError("Qwen3MoeLRP: a bias in the dense MLP is not supported by the fused driver")
+            Lw.update(wg=mlp.gate_proj.weight.detach(), wu=mlp.up_proj.weight.detach(), wd=mlp.down_proj.weight.detach())
+        W["layers"].append(Lw)
+    return cfg, W
+
+
+class Qwen3MoeLRP(Q.QwenLRP):
+    """QwenLRP for Qwen3-MoE: cfg carries moe_layers (which layers are sparse), n_experts, top_k, norm_topk, moe_inter (config_from_hf);
+    W["layers"][i] of a sparse layer holds wr, wgu_e, wd_e.  The expert weights stay the caller's tensors (moved to the engine's device and
+    dtype only if they are elsewhere); everything else lives in the flat buffer.  explain() is LlamaLRP.explain plus `experts`."""
+
+    def __init__(self, cfg, W, dtype=torch.bfloat16, device="cuda", mode="efficient", max_seq=4096, sparse_top=False, fold_norm=None):
+        self._af_cache = {}
+        super().__init__(cfg, W, dtype=dtype, device=device, mode=mode, max_seq=max_seq, sparse_top=False, fold_norm=fold_norm)
+
+    @staticmethod
+    def flat_layout(cfg, dtype):
+        """one spec per layer: a sparse layer keeps the attention half's weights and the router [E, H]; a dense one is QwenLRP's layer"""
+        top, dense = E.LlamaLRP.flat_layout(cfg, dtype)
+        sparse = {k: v for k, v in dense.items() if k not in ("wgu", "wd")}
+        sparse["wr"] = ((cfg["n_experts"], cfg["hidden"]), None)
+        return top, [sparse if moe else dense for moe in cfg["moe_layers"]]
+
+    def _put_layer(self, Lw, L):
+        if "wr" not in L:
+            return super()._put_layer(Lw, L)
+        for k in ("ln1", "ln2", "wo", "qn", "kn", "wr"):
+            E.put_rows(Lw[k], L[k])
+        E.put_rows(Lw["wqkv"], L["wq"], L["wk"], L["wv"])
+        if self.folded:          # (ln1 into the QKV columns as in the dense layers; ln2 stays a vector: the expert weights are read as stored)
+            E.fold_rows(Lw["wqkv"], (Lw["wqkv"],), L["ln1"])
+            Lw["ln1"].fill_(1.0)
+        for k in ("wgu_e", "wd_e"):
+            w = L[k].detach().to(device=self.device, dtype=self.dtype)
+            if not w.is_contiguous():
+                raise NotImplementedError("Qwen3MoeLRP: gate_up_proj / down_proj must be contiguous (the grouped kernels read them as stored)")
+            Lw[k] = w
+
+    def set_mode(self, mode):
+        if mode == "explicit":
+            raise NotImplementedError("Qwen3MoeLRP: mode='explicit' is not implemented -- the reference defines no explicit composite for "
+                                      "Qwen3-MoE; the driver runs the efficient placement only")
+        super().set_mode(mode)
+
+    def build_transposes(self):
+        for L in self.layers:
+            ops.clear_weight_cache(*(L[k] for k in ("wqkv", "wo", "wgu", "wd", "wr") if k in L))
+        self.lm_head_t = None
+
+    def _fused(self, M):
+        """fused_layer_ok of the DENSE layers' shapes (the sparse layers have no wgu / wd); without a dense layer nothing of it applies"""
+        dense = next((Lw for Lw in self.layers if "wgu" in Lw), None)
+        if dense is None:
+            return E.FusedOk(False, False, False, False)
+        return E.fused_layer_ok(M, dense, self.meta, self.dtype, self._nf_cache)
+
+    def _attn_fused(self, M):
+        """the attention half of every layer runs on the fused launch sequence at M rows: folded norm weights, and each of its four GEMMs is
+        a problem the ping-pong kernel's fused epilogues take (bf16, >= 190 tiles), the dQ kernel forms D, head dim 64 or 128"""
+        key = (M, E.PITCH_PAD, repr(ops.NORM_FUSION), ops.PREP_FUSION)
+        hit = self._af_cache.get(key)
+        if hit is None:
+            nq, nk, d = self.meta[:3]
+            H, nqkv, dt, Lw = self.cfg["hidden"], (nq + 2 * nk) * d, self.dtype, self.layers[0]
+            ldo, ldqkv = Lw["wo"].stride(0), Lw["wqkv"].stride(0)
+            hit = self._af_cache[key] = bool(
+                self.folded and ops.NORM_FUSION is True and self.mode == "efficient" and not self.attn_t and d in (64, 128)
+                and ops.attn_dq_d_ok(dt, d)
+                and ops.norm_fused_ok(M, H, nq * d, nq * d, ldo, False, dt)                                        # h1 = h + o Wo^T
+                and ops.norm_fused_ok(M, nqkv, H, H, ldqkv, False, dt)                                             # qkv = rstd (h W'qkv^T)
+                and ops.norm_fused_ok(M, nq * d, H, H, ldo, True, dt)                                              # Gho = 1/2 (Gs1 Wo)
+                and ops.norm_fused_ok(M, H, nqkv, E.fused_layout(H, 0, nq, nk, d, dt)["Aqkv"], ldqkv, True, dt))   # G_h = rstd (Aqkv W'qkv) + Gs1
+        return hit
+
+    # ---------------------------------------------------------------------------------------------
+    def forward(self, emb, B, S, row_iv=None, keep_m=False, experts=False):
+        """experts: every sparse block's output is kept for the R_block read-out of the backward"""
+        c, ar = self.cfg, self._arena
+        H, I, d, nq, nk, eps = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"], c["rms_eps"]
+        M, nqk, nqkv, scale = B * S, (nq + nk) * d, (nq + 2 * nk) * d, d ** -0.5
+        last = torch.arange(B, device=self.device) * S + (S - 1)
+        fa, coef = self._attn_fused(M), self._gated_coef(M)
+        stash, h_prev, branch = [], emb, None
+        for li, Lw in enumerate(self.layers):
+            st = dict(rstd1=ar.f32(("rstd1", li), M), moe="wr" in Lw)
+            x = None if fa else ar.new("x", M, H)          # (fused: the QKV GEMM's epilogue applies the norm; only the sum and rstd1 are formed)
+            if branch is None:
+                st["h"] = h_prev
+                ops.add_rmsnorm_fwd(h_prev, None, Lw["ln1"], eps, y=x, rstd=st["rstd1"], norm_out=not fa)
+            else:
+                st["h"] = ar.new(("h", li), M, H)
+                ops.add_rmsnorm_fwd(h_prev, branch, Lw["ln1"], eps, hsum_out=st["h"], y=x, rstd=st["rstd1"], norm_out=not fa)
+            qkn = self._qk_norm(Lw)
+            # ---- attention half -> h1, rstd2 and x2 = rstd2 (.) ln2 (.) h1
+            x2 = ar.new("x2", M, H)
+            if fa:
+                qkv, qkr, st["rstd_q"], st["rstd_k"] = E.fused_qkv_fwd(st["h"], st["rstd1"], Lw["wqkv"], self.cos, self.sin, S, self.meta,
+                                                                      self._alloc(li), qk_norm=qkn)
+                st.update(E.fused_attn_fwd(st["h"], qkv, qkr, Lw, B, S, self.meta, self._alloc(li), row_iv)[0], qkv=qkv, qkr=qkr)
+                ops.rmsnorm_bwd_add2(None, st["h1"], Lw["ln2"], st["rstd2"], None, None, x2, None)      # (the row-scale kernel: x w rstd)
+            else:
+                qkv, qn = ops.linear_fwd(x, Lw["wqkv"], out=ar.new(("qkv", li), M, nqkv)), ar.new("qkn", M, nqk)
+                st["rstd_q"], st["rstd_k"] = ar.f32(("rstd_q", li), M * nq), ar.f32(("rstd_k", li), M * nk)
+                ops.head_rmsnorm_fwd(qkv[:, : nq * d], qkn[0], qn[:, : nq * d], st["rstd_q"], nq, d, eps)
+                ops.head_rmsnorm_fwd(qkv[:, nq * d: nqk], qkn[1], qn[:, nq * d:], st["rstd_k"], nk, d, eps)
+                qkr = ops.rope_fwd(qn, ar.new(("qkr", li), M, nqk), self.cos, self.sin, S, nq + nk, d)
+                v = qkv[:, nqk:]
+                v_t = ops.transpose_heads(v, B, S, nk, d) if self.attn_t else None
+                o, lse = ar.new(("o", li), M, nq * d), ar.f32(("lse", li), B, nq, S)
+                ops.attn_fwd(qkr[:, : nq * d], qkr[:, nq * d:], v, v_t, o, lse, B, S, nq, nk, d, scale, True, 0, row_iv=row_iv)
+                a = self._lin_fwd(o, Lw["wo"], ar.new("a", M, H))
+                st.update(qkv=qkv, qkr=qkr, o=o, lse=lse, h1=ar.new(("h1", li), M, H), rstd2=ar.f32(("rstd2", li), M))
+                ops.add_rmsnorm_fwd(st["h"], a, Lw["ln2"], eps, hsum_out=st["h1"], y=x2, rstd=st["rstd2"])
+            # ---- MLP half
+            if st["moe"]:
+                logits = ops.linear_fwd(x2, Lw["wr"], out=ar.new(("logits", li), M, c["n_experts"]))
+                idx, w, lse_r = ops.moe_router_fwd(logits, c["top_k"], c["norm_topk"])
+                plan = ops.MoePlan(idx, c["n_experts"])
+                st["coef"], st["m"] = ops.moe_gate_up_fwd(x2, Lw["wgu_e"], plan, self.act)
+                branch = ops.moe_combine(ops.moe_down_fwd(st["m"], Lw["wd_e"], plan), plan, w)
+                st.update(logits=logits, lse_r=lse_r, idx=idx, w=w, plan=plan, out=branch if experts else None)
+            else:
+                gu, m = ar.new(("gu", li), M, 2 * I), ar.wide("m", M, I)
+                if coef:
+                    st["gu"], m = ops.gemm_gated_fwd_coef(x2, Lw["wgu"], gu, m, self.eps_g, self.eps["lin"], self.act)
+                else:
+                    st["gu"], m = ops.gemm_gated_fwd(x2, Lw["wgu"], gu, m, self.act)
+                branch = self._lin_fwd(m, Lw["wd"], ar.new(("dn", li), M, H))
+            stash.append(st)
+            h_prev = st["h1"]
+        return dict(stash=stash, last=last, row_iv=row_iv, coef=coef, fa=fa,
+                    **E.head_fwd(ar, h_prev, branch, False, last, self.norm, self.lm_head, eps))
+
+    # ---------------------------------------------------------------------------------------------
+    def backward(self, fw, emb, idx, B, S, layer_relevance=False, seed=None, latent=frozenset(), heads=None, attn_map=None, experts=False):
+        """-> (G at the embedding, layer_R rows or None, dict of the extra read-outs: R_resid [L+1, B, H]; experts: R_expert [L, B, E],
+        expert_index [L, B, S, k] and R_block [L, B])"""
+        c, ar, dev, dt = self.cfg, self._arena, self.device, self.dtype
+        H, I, d, nq, nk, Ne, k = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"], c["n_experts"], c["top_k"]
+        M, rep, nqk, nqkv, scale = B * S, nq // nk, (nq + nk) * d, (nq + 2 * nk) * d, d ** -0.5
+        Gh_last, Gs_last, _, rel_last = self._head_bwd(fw, idx, B, seed, layer_relevance)
+        nL, lat = len(self.layers), {}
+        if "resid" in latent:
+            lat["R_resid"] = torch.empty(nL + 1, B, H, device=dev, dtype=torch.float32)
+            ops.colsum_dot(fw["hL_last"], Gh_last, B, 1, out=lat["R_resid"][nL])
+        if experts:      # (dense layers: exactly 0 / -1)
+            lat["R_expert"] = torch.zeros(nL, B, Ne, device=dev, dtype=torch.float32)
+            lat["R_block"] = torch.zeros(nL, B, device=dev, dtype=torch.float32)
+            lat["expert_index"] = torch.full((nL, B, S, k), -1, device=dev, dtype=torch.int64)
+        last, row_iv, fa = fw["last"], fw["row_iv"], fw["fa"]
+        Gs = ar.zeros(("Gs", nL & 1), M, H).index_copy_(0, last, Gs_last)
+        layer_R = [rel_last] if layer_relevance else None
+        if fa:
+            ar.f32("half", M).fill_(0.5)          # (fused_attn_bwd's row scale)
+        for li in range(nL - 1, -1, -1):
+            Lw, st = self.layers[li], fw["stash"][li]
+            hs = None if heads is None else heads.layer(li)
+            am = None if attn_map is None else attn_map.layer(li)
+            # ---- MLP half: Gs at the layer's output -> Gs1 at h1 (the norm's identity rule, rstd held constant, and the residual)
+            Gs1 = ar.new("Gs1", M, H)
+            if st["moe"]:
+                Agu, gw = ops.moe_down_dgrad(Gs, Lw["wd_e"], st["coef"], st["m"], st["w"], st["plan"])
+                if experts:
+                    ops.moe_expert_relevance(st["idx"], st["w"], gw, B, S, Ne, out=lat["R_expert"][li])
+                    torch.sum(ops.readout(st["out"], Gs, out=ar.f32("rel_blk", M)).view(B, S), 1, out=lat["R_block"][li])
+                    lat["expert_index"][li].copy_(st["idx"].view(B, S, k))
+                Gx_e = ops.moe_combine(ops.moe_gate_up_dgrad(Agu, Lw["wgu_e"], st["plan"]), st["plan"])
+                Gl = ops.moe_router_bwd(st["logits"], st["lse_r"], st["idx"], st["w"], gw, c["norm_topk"], out=ar.new("Glogits", M, Ne))
+                Gx_r = self._lin_bwd(Gl, Lw["wr"], ar.new("Gx2", M, H))
+                Gs1e = ar.new("Gs1e", M, H)
+                ops.rmsnorm_bwd_add2(Gs, Gx_e, Lw["ln2"], st["rstd2"], None, None, Gs1e, None)
+                ops.rmsnorm_bwd_add2(Gs1e, Gx_r, Lw["ln2"], st["rstd2"], None, None, Gs1, None)
+            else:
+                if fw["coef"]:
+                    Agu = ops.gemm_gated_bwd_coef(Gs, Lw["wd"], st["gu"], ar.wide("Agu", M, 2 * I))
+                else:
+                    Agu = ops.gemm_gated_bwd(Gs, Lw["wd"], st["gu"], ar.wide("Agu", M, 2 * I), self.eps_g, 0.0, self.act)
+                Gx2 = self._lin_bwd(Agu, Lw["wgu"], ar.new("Gx2", M, H))
+                ops.rmsnorm_bwd_add2(Gs, Gx2, Lw["ln2"], st["rstd2"], None, None, Gs1, None)
+            # ---- attention half: Gs1 -> Gs at the layer's input
+            qkn = self._qk_norm(Lw)
+            if fa:
+                Gs = E.fused_attn_bwd(Gs1, st, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv, qkn, hs, am)
+            else:
+                qkv, qkr = st["qkv"], st["qkr"]
+                q, kk, v = qkr[:, : nq * d], qkr[:, nq * d:], qkv[:, nqk:]
+                Gof = self._lin_bwd(Gs1, Lw["wo"], ar.new("Gof", M, nq * d))
+                Gho, D = ar.new("Gho", M, nq * d), ar.f32("D", B, nq, S)
+                ops.attn_bwd_prep(Gof, st["o"], Gho, D, B, S, nq, d, 0.0, 0.5)
+                if hs is not None:
+                    hs("out", st["o"], Gof)
+                if am is not None:
+                    am(q, kk, v, Gho, st["lse"], 2.0, row_iv)
+                k_t = q_t = Gho_t = None
+                if self.attn_t:
+                    k_t, q_t = ops.transpose_heads(kk, B, S, nk, d), ops.transpose_heads(q, B, S, nq, d)
+                    Gho_t = ops.transpose_heads(Gho, B, S, nq, d)
+                dk_h, dv_h, dqk = ar.new("dk_h", M, nq * d), ar.new("dv_h", M, nq * d), ar.new("dqk", M, nqk)
+                Aqkv = ar.new("Aqkv", M, nqkv)
+                ops.attn_bwd_dq(q, kk, v, k_t, Gho, st["lse"], D, dqk[:, : nq * d], B, S, nq, nk, d, scale, 0.0, 0.0, row_iv=row_iv)
+                ops.attn_bwd_dkv(q, kk, v, q_t, Gho, Gho_t, st["lse"], D, dk_h, dv_h, B, S, nq, nk, d, scale, 0.0, 0.0, row_iv=row_iv)
+                if hs is not None:
+                    hs("q", q, dqk[:, : nq * d])
+                    hs("k", kk, dk_h, rep)
+                    hs("v", v, dv_h, rep)
+                ops.gqa_reduce(dk_h, dqk[:, nq * d:], M, nk, rep, d)
+                ops.gqa_reduce(dv_h, Aqkv[:, nqk:], M, nk, rep, d)
+                Gqk = ops.rope_bwd(dqk, None, None, ar.new("Gqkn", M, nqk), self.cos, self.sin, S, nq + nk, d, 0.0, 0.0)
+                ops.head_rmsnorm_bwd(Gqk[:, : nq * d], qkn[0], st["rstd_q"], Aqkv[:, : nq * d], nq, d)
+                ops.head_rmsnorm_bwd(Gqk[:, nq * d:], qkn[1], st["rstd_k"], Aqkv[:, nq * d: nqk], nk, d)
+                Gx = self._lin_bwd(Aqkv, Lw["wqkv"], ar.new("Gx", M, H))
+                Gs = ar.new(("Gs", li & 1), M, H)
+                ops.rmsnorm_bwd_add2(Gs1, Gx, Lw["ln1"], st["rstd1"], None, None, Gs, None)
+            if layer_relevance:
+                layer_R.append(ops.readout(st["h"], Gs, out=ar.f32(("rel", li), M)))
+            if "resid" in latent:
+                ops.colsum_dot(st["h"], Gs, B, S, out=lat["R_resid"][li])
+        return Gs, layer_R, lat
+
+    @torch.no_grad()
+    def explain(self, input_ids=None, inputs_embeds=None, target=None, layer_relevance=False, return_G=False, lengths=None, seed=None,
+                graph=False, latent=None, heads=None, attn_map=None, experts=False):
+        """LlamaLRP.explain for Qwen3-MoE (same arguments and outputs), with
+        experts=True: two more outputs -- R_expert [L, B, E] fp32, the relevance of every expert of every layer per prompt (`routing_weights *
+        routing_weights.grad` scattered by expert, summed over the prompt's tokens; rows of dense layers are exactly 0, pad tokens contribute
+        exactly 0), expert_index [L, B, S, k] int64, the experts each token was routed to (-1 on dense layers), and R_block [L, B] fp32 =
+        sum_{t, j} out (*) G at the sparse block's output (0 on dense layers), read off the block's own output and the gradient that reaches
+        it: sum_e R_expert[l, b] = 1/2 R_block[l, b].  Every other output is bitwise what it is without the keyword.
+        Not served: latent="mlp" (a sparse layer has no single MLP) and graph=True -- both raise ValueError."""
+        names = (latent,) if isinstance(latent, str) else tuple(latent or ())
+        if "mlp" in names:
+            raise ValueError('Qwen3MoeLRP: latent="mlp" is not defined for a model with sparse layers (no single MLP per layer); '
+                             '"trace" and "resid" are served')
+        if graph:
+            raise ValueError("Qwen3MoeLRP: graph=True is not supported (the routing plan and the expert stashes are allocated per call)")
+        am = E.attn_map_request(attn_map, len(self.layers), self.cfg["n_heads"], self.cfg["head_dim"], self.dtype, self.mode)
+        hd = E.head_request(heads, self.cfg["head_dim"], self.dtype)
+        lat = E.latent_request(latent, self.cfg["hidden"], self.cfg["inter"], self.dtype)
+        B, S, emb, row_iv, idx = E.explain_inputs(input_ids, inputs_embeds, lengths, target, self.cfg["vocab"], self.max_seq, self.dtype,
+                                                  self.device, seed)
+        if inputs_embeds is None:
+            input_ids = input_ids.to(self.device)
+        return self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, lat, hd, am, experts=bool(experts))
+
+    @classmethod
+    def from_hf(cls, model, **kw):
+        cfg, W = weights_from_hf(model)
+        kw.setdefault("dtype", next(model.parameters()).dtype)
+        return cls(cfg, W, **kw)

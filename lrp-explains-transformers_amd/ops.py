@@ -670,9 +670,10 @@ def gemm_nn_rs_res(s, W, rs, res, out):
     return out
 
 
-def add_rmsnorm_fwd(h, branch, w, eps, w_offset=0.0, hsum_out=None, y=None, rstd=None):
+def add_rmsnorm_fwd(h, branch, w, eps, w_offset=0.0, hsum_out=None, y=None, rstd=None, norm_out=True):
+    """norm_out=False: only the residual sum (hsum_out) and rstd are written, no normalised rows -> (None, rstd)"""
     M, H = h.shape
-    y = torch.empty_like(h) if y is None else y
+    y = (torch.empty_like(h) if y is None else y) if norm_out else None
     rstd = torch.empty(M, device=h.device, dtype=torch.float32) if rstd is None else rstd
     same(h, branch, hsum_out, y)
     f32(rstd)
@@ -1371,3 +1372,88 @@ def moe_gate_up_dgrad(Agu, Wgu, plan):
         p(Agu), p(Wgu), p(plan.buf), p(gx), plan.T, plan.k, plan.E, H, I2 // 2, Agu.stride(0), gx.stride(0), dt(Agu), stream()),
         "lrp_moe_gate_up_dgrad")
     return gx
+
+
+# ------------------------------------------------------------------------------------------- MoE router (csrc/moe_router.hip)
+ROUTER_EMAX, ROUTER_KMAX = 1024, 16
+
+
+def _router_rows(name, t, what, cols=None):
+    """a [T, cols] activation operand of the router kernels: 2-D, unit column stride (a row pitch is allowed), float32 or bfloat16"""
+    if t.dim() != 2 or (cols is not None and t.shape[1] != cols):
+        raise ValueError(f"{name}: {what} must be [T, {cols if cols is not None else 'E'}], got {tuple(t.shape)}")
+    if t.stride(1) != 1:
+        raise ValueError(f"{name}: {what} must have contiguous rows (a row pitch is allowed)")
+    if t.dtype not in _DT:
+        raise ValueError(f"{name}: {what} must be float32 or bfloat16, got {t.dtype}")
+
+
+def _router_slots(name, ref, T, k, idx, **acts):
+    """idx int64 [T, k] and the [T, k] activation operands next to it, all contiguous"""
+    if tuple(idx.shape) != (T, k) or idx.dtype != torch.int64 or not idx.is_contiguous():
+        raise ValueError(f"{name}: idx must be a contiguous int64 [{T}, {k}] tensor, got {idx.dtype} {tuple(idx.shape)}")
+    for what, t in acts.items():
+        if tuple(t.shape) != (T, k) or not t.is_contiguous():
+            raise ValueError(f"{name}: {what} must be a contiguous [{T}, {k}] tensor, got {tuple(t.shape)}")
+        if t.dtype != ref.dtype:
+            raise ValueError(f"{name}: {what} is {t.dtype} next to {ref.dtype} activations")
+
+
+def moe_router_fwd(logits, k, norm_topk):
+    """HF's Qwen3MoeTopKRouter after its F.linear, on the device: logits [T, E] (a row pitch is allowed) -> (idx int64 [T, k],
+    w [T, k] in the logits' dtype, lse fp32 [T]); fp32 softmax, top-k (ties to the lower index), optional renorm, one rounding"""
+    _router_rows("lrp_moe_router_fwd", logits, "logits")
+    T, E = logits.shape
+    k = int(k)
+    if not (1 <= k <= min(E, ROUTER_KMAX)) or E > ROUTER_EMAX:
+        raise ValueError(f"lrp_moe_router_fwd: k = {k} of E = {E} experts; the kernel serves k <= {ROUTER_KMAX}, k <= E <= {ROUTER_EMAX}")
+    idx = torch.empty(T, k, device=logits.device, dtype=torch.int64)
+    w = torch.empty(T, k, device=logits.device, dtype=logits.dtype)
+    lse = torch.empty(T, device=logits.device, dtype=torch.float32)
+    check(lib.lrp_moe_router_fwd(p(logits), p(idx), p(w), p(lse), T, E, k, logits.stride(0), int(bool(norm_topk)), dt(logits), stream()),
+          "lrp_moe_router_fwd")
+    return idx, w, lse
+
+
+def moe_router_bwd(logits, lse, idx, w, gw, norm_topk, out=None):
+    """-> G_logits [T, E] in the logits' dtype, dense (zeros where no gradient arrives): the exact backward of moe_router_fwd given
+    G_w [T, k] (what moe_down_dgrad returns).  w, the forward's rounded routing weights, is part of the C signature and is checked like the
+    other operands, but the kernel does NOT read it: the renorm's backward needs the fp32 weight p[i_s] / V that autograd holds, which it
+    recomputes from logits and lse"""
+    _router_rows("lrp_moe_router_bwd", logits, "logits")
+    T, E = logits.shape
+    if idx.dim() != 2:
+        raise ValueError(f"lrp_moe_router_bwd: idx must be [T, k], got {tuple(idx.shape)}")
+    k = idx.shape[1]
+    _router_slots("lrp_moe_router_bwd", logits, T, k, idx, w=w, G_w=gw)
+    if tuple(lse.shape) != (T,) or lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise ValueError(f"lrp_moe_router_bwd: lse must be a contiguous float32 [{T}] tensor, got {lse.dtype} {tuple(lse.shape)}")
+    if not (1 <= k <= min(E, ROUTER_KMAX)) or E > ROUTER_EMAX:
+        raise ValueError(f"lrp_moe_router_bwd: k = {k} of E = {E} experts; the kernel serves k <= {ROUTER_KMAX}, k <= E <= {ROUTER_EMAX}")
+    if out is None:
+        out = torch.empty(T, E, device=logits.device, dtype=logits.dtype)
+    else:
+        _router_rows("lrp_moe_router_bwd", out, "out", E)
+        if out.shape[0] != T or out.dtype != logits.dtype:
+            raise ValueError(f"lrp_moe_router_bwd: out must be [{T}, {E}] {logits.dtype}, got {tuple(out.shape)} {out.dtype}")
+    check(lib.lrp_moe_router_bwd(p(logits), p(lse), p(idx), p(w), p(gw), p(out), T, E, k, logits.stride(0), out.stride(0),
+                                 int(bool(norm_topk)), dt(logits), stream()), "lrp_moe_router_bwd")
+    return out
+
+
+def moe_expert_relevance(idx, w, gw, B, S, E, out=None):
+    """-> fp32 [B, E]: out[b, e] = sum over prompt b's tokens and slots with idx = e of w G_w (a slot index outside [0, E) is skipped)"""
+    if idx.dim() != 2 or idx.shape[0] != B * S:
+        raise ValueError(f"lrp_moe_expert_relevance: idx must be [B S = {B * S}, k], got {tuple(idx.shape)}")
+    k = idx.shape[1]
+    if w.dtype not in _DT:
+        raise ValueError(f"lrp_moe_expert_relevance: w must be float32 or bfloat16, got {w.dtype}")
+    _router_slots("lrp_moe_expert_relevance", w, B * S, k, idx, w=w, G_w=gw)
+    if not (1 <= k <= min(E, ROUTER_KMAX)) or E > ROUTER_EMAX:
+        raise ValueError(f"lrp_moe_expert_relevance: k = {k} of E = {E} experts; the kernel serves k <= {ROUTER_KMAX}, k <= E <= {ROUTER_EMAX}")
+    if out is None:
+        out = torch.empty(B, E, device=w.device, dtype=torch.float32)
+    elif tuple(out.shape) != (B, E) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"lrp_moe_expert_relevance: out must be a contiguous float32 [{B}, {E}] tensor, got {out.dtype} {tuple(out.shape)}")
+    check(lib.lrp_moe_expert_relevance(p(idx), p(w), p(gw), p(out), B, S, k, E, dt(w), stream()), "lrp_moe_expert_relevance")
+    return out
