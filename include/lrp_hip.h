@@ -537,4 +537,5 @@ int lrp_moe_gate_up_dgrad(const void* Agu, const void* Wgu, const int* plan, voi
 /* the per-head read-out of the latent feature attribution (same ABI version, same conventions; a header of its own) */
 #include "lrp_hip_latent.h"
 #include "lrp_hip_moe_router.h"
+#include "lrp_hip_mxfp4.h"
 #endif /* LRP_HIP_H */

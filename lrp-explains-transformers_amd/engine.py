@@ -307,13 +307,14 @@ FUSED_SCRATCH = frozenset(("ssq", "m", "half", "Agu", "Gs1", "Gho", "D", "Aqkv",
 
 # ---- the scaffolding of the fused drivers (LlamaLRP here, Gemma3LRP / Gemma3MMLRP / BertLRP in their modules): one owner per decision
 
-def pack_flat(top, layer, n_layers, dtype, device):
+def pack_flat(top, layer, n_layers, dtype, device, align=64):
     """ONE flat buffer holds every weight of a model (a multi-GPU start-up is then a single broadcast of it, lxt_amd.dist.broadcast_weights).
     top / layer: {name: (shape, row pitch or None)} of the model-wide weights and of one layer's, in storage order; the buffer's size follows
     from these lists alone; layer may be a list of n_layers specs (layers of different forms: the MoE driver).  -> (flat, {name: view}, one
     {name: view} per layer).  Every view starts 128-byte aligned; with a row pitch it is a
-    [rows, cols] view of [rows, pitch] storage.  device="meta" gives the layout without memory."""
-    up = lambda n: (n + 63) // 64 * 64                                   # noqa: E731
+    [rows, cols] view of [rows, pitch] storage (align: the grid of the view starts in ELEMENTS -- 64 of a 2-byte type; the uint8 buffer of the
+    quantised weights passes 128).  device="meta" gives the layout without memory."""
+    up = lambda n: (n + align - 1) // align * align                      # noqa: E731
     stored = lambda shape, pitch: (*shape[:-1], pitch or shape[-1])      # noqa: E731  (the [rows, pitch] block behind a view)
     specs = [top] + (list(layer) if isinstance(layer, (list, tuple)) else [layer] * n_layers)
     flat = torch.empty(sum(up(math.prod(stored(*e))) for spec in specs for e in spec.values()), device=device, dtype=dtype)
@@ -339,6 +340,35 @@ def put_rows(dst, *srcs):
 def put_gate_up(dst, wg, wu):
     """gate / up rows interleaved in blocks of 32 (ops.interleave_gate_up): the gated-MLP rules then run inside the GEMM epilogues"""
     return ops.interleave_gate_up(wg.to(device=dst.device, dtype=dst.dtype), wu.to(device=dst.device, dtype=dst.dtype), out=dst)
+
+
+WEIGHT_FORMATS = (None, "mxfp4")
+MX_MATRICES = ("wqkv", "wo", "wgu", "wd")          # the Linears of a decoder layer: what weight_format="mxfp4" stores as codes + scales
+
+
+def weight_format_request(weight_format, cfg):
+    """LlamaLRP(weight_format=...) -> the format; raises ValueError before any device work: an unknown name, or (mxfp4: blocks of 32 along the
+    contraction dimension K of every stored [N, K] Linear) a K off the 32 grid -- hidden (q/k/v, gate/up), n_heads * head_dim (o), inter (down)"""
+    if weight_format not in WEIGHT_FORMATS:
+        raise ValueError(f"weight_format must be one of {WEIGHT_FORMATS}, got {weight_format!r}")
+    if weight_format == "mxfp4":
+        for name, K in (("hidden", cfg["hidden"]), ("n_heads * head_dim", cfg["n_heads"] * cfg["head_dim"]), ("inter", cfg["inter"])):
+            if K % ops.MX_BLOCK:
+                raise ValueError(f"weight_format='mxfp4': {name} = {K} is not a multiple of {ops.MX_BLOCK} (one scale per {ops.MX_BLOCK} "
+                                 "elements along a Linear's contraction dimension)")
+    return weight_format
+
+
+def quant_layout(layer):
+    """one layer's spec of flat_layout -> (the spec without the four Linears, the Linears alone, the uint8 spec of their MXFP4 storage:
+    name_c -- codes [N, K / 2], name_s -- scales [N, K / 32] with the row pitch on the 4-byte grid)"""
+    rest = {k: v for k, v in layer.items() if k not in MX_MATRICES}
+    lin = {k: layer[k] for k in MX_MATRICES}
+    q = {}
+    for k, ((N, K), _) in lin.items():
+        q[k + "_c"] = ((N, K // 2), None)
+        q[k + "_s"] = ((N, K // ops.MX_BLOCK), (K // ops.MX_BLOCK + 3) // 4 * 4)
+    return rest, lin, q
 
 
 def rope_tables(inv_freq, attention_scaling, max_seq, dtype, device):
@@ -650,9 +680,12 @@ def explanation(emb, G, idx, logits, B, S, return_G=False):
 
 
 class LlamaLRP:
-    """Device-resident weights (each ONCE, forward layout, one flat buffer) + explain()."""
+    """Device-resident weights (each ONCE, forward layout, one flat buffer) + explain().  weight_format="mxfp4": the four Linears of every
+    layer are resident as MXFP4 codes + scales only (`flat_q`) and dequantised layer by layer into one scratch layer."""
 
-    def __init__(self, cfg, W, dtype=torch.bfloat16, device="cuda", mode="efficient", max_seq=4096, sparse_top=True, fold_norm=None):
+    def __init__(self, cfg, W, dtype=torch.bfloat16, device="cuda", mode="efficient", max_seq=4096, sparse_top=True, fold_norm=None,
+                 weight_format=None):
+        self.weight_format = weight_format_request(weight_format, cfg)
         if not torch.cuda.is_available():
             raise RuntimeError("LlamaLRP needs a HIP device: the LRP kernels have no CPU fallback")
         self.cfg, self.dtype, self.device = dict(cfg), dtype, torch.device(device)
@@ -678,12 +711,30 @@ class LlamaLRP:
         # single broadcast of `self.flat` (lxt_amd.dist.broadcast_weights) followed by the LOCAL W^T copies
         nq, hd = cfg["n_heads"], cfg["head_dim"]
         self.meta = (nq, cfg["n_kv"], hd, cfg["rms_eps"], self.act, hd ** -0.5)      # (the layer description of the fused-layer functions above)
-        self.flat, top, self.layers = pack_flat(*self.flat_layout(cfg, dtype), len(W["layers"]), dtype, dev)
+        # weight_format="mxfp4": the four Linears of every layer live ONLY as e2m1 codes + e8m0 scales in the uint8 buffer flat_q (0.27 of
+        # their bf16 bytes); embedding, LM head, norms and biases stay in `flat`.  ONE scratch layer in the model dtype, at fused_layout's
+        # pitches, allocated once (stable addresses for graph capture): every layer's dict points its four matrices at it, a layer is loaded
+        # through it (_put_layer as ever, then the quantiser) and dequantised into it in front of its forward and its backward (_load_layer),
+        # so fused_layer_ok, the pitches and every kernel dispatch see what they see without it
+        self.flat_q = self.scratch = self._qlayers = None
+        top_spec, layer_spec = self.flat_layout(cfg, dtype)
+        if self.weight_format is None:
+            self.flat, top, self.layers = pack_flat(top_spec, layer_spec, len(W["layers"]), dtype, dev)
+        else:
+            rest, lin, qspec = quant_layout(layer_spec)
+            self.flat, top, self.layers = pack_flat(top_spec, rest, len(W["layers"]), dtype, dev)
+            self.flat_q, _, self._qlayers = pack_flat({}, qspec, len(W["layers"]), torch.uint8, dev, align=128)
+            self.scratch, _, (views,) = pack_flat({}, lin, 1, dtype, dev)
+            self.scratch.zero_()                  # (the pitch padding is never written: the load's finiteness check reads the whole buffer)
+            for Lw in self.layers:
+                Lw.update(views)
         self.embed, self.norm = put_rows(top["embed"], W["embed"]), put_rows(top["norm"], W["norm"])
         self.lm_head = put_rows(top["lm_head"], W["lm_head"]) if "lm_head" in top else self.embed      # (cfg["tied"]: one stored copy serves both)
         self.lm_head_t = None                        # [H, V] copy, made on the first dense-seed explanation
-        for Lw, L in zip(self.layers, W["layers"]):
+        for li, (Lw, L) in enumerate(zip(self.layers, W["layers"])):
             self._put_layer(Lw, L)
+            if self.flat_q is not None:
+                self._quantize_layer(li)
         self.attn_t = ops.attn_needs_transposed(self.embed, hd)
         inv = cfg.get("inv_freq")                    # scaled rope types: HF's own frequencies (config_from_hf)
         if inv is None:
@@ -705,6 +756,53 @@ class LlamaLRP:
             fold_rows(Lw["wgu"], (Lw["wgu"],), L["ln2"])
             Lw["ln1"].fill_(1.0)
             Lw["ln2"].fill_(1.0)
+
+    def _quantize_layer(self, li):
+        """the scratch layer, as _put_layer has just left it (fused rows, interleave, folded norms) -> layer li's codes and scales"""
+        if not bool(torch.isfinite(self.scratch).all()):
+            raise ValueError(f"weight_format={self.weight_format!r}: layer {li} holds non-finite weights")
+        Lw, Q = self.layers[li], self._qlayers[li]
+        for k in MX_MATRICES:
+            ops.mxfp4_quantize(Lw[k], Q[k + "_c"], Q[k + "_s"])
+
+    def _load_layer(self, li):
+        """weight_format="mxfp4": layer li's four Linears, dequantised into the scratch layer on the current stream -- in front of the layer's
+        forward and of its backward, each matrix once per layer and pass (capturable: kernel launches only); nothing otherwise.  The W^T
+        copies ops.weight_t caches on a weight (fp32 parity engine, odd shapes) are keyed on the scratch: dropped at every load"""
+        if self.flat_q is None:
+            return
+        Lw, Q = self.layers[li], self._qlayers[li]
+        for k in MX_MATRICES:
+            ops.mxfp4_dequant(Q[k + "_c"], Q[k + "_s"], Lw[k])
+        ops.clear_weight_cache(self.scratch)
+
+    def weight_bytes(self):
+        """exact bytes of device memory the weights hold: resident -- `flat` (+ `flat_q`); scratch -- the one scratch layer of a quantised engine"""
+        nb = lambda t: 0 if t is None else t.numel() * t.element_size()      # noqa: E731
+        return dict(resident=nb(self.flat) + nb(self.flat_q), scratch=nb(self.scratch))
+
+    def dequantized_weights(self):
+        """-> (cfg, W) in the form LlamaLRP(cfg, W) takes, holding what this engine computes with: the Linears dequantised (q / k / v split,
+        gate / up de-interleaved), the norm vectors as stored -- ones when folded, so an ordinary engine built from it folds by exactly 1.0 and
+        ends up with the same bits in its matrices.  Copies on the device, the whole model in the model dtype: for checks, not for serving"""
+        c = self.cfg
+        nq, nk, d, I = c["n_heads"], c["n_kv"], c["head_dim"], c["inter"]
+        W = dict(embed=self.embed.clone(), norm=self.norm.clone(), layers=[])
+        if self.lm_head is not self.embed:
+            W["lm_head"] = self.lm_head.clone()
+        for li, Lw in enumerate(self.layers):
+            self._load_layer(li)
+            wq, wk, wv = (t.clone() for t in Lw["wqkv"].split((nq * d, nk * d, nk * d), 0))
+            gu = Lw["wgu"].unflatten(0, (I // ops.GATED_IL, 2, ops.GATED_IL))
+            L = dict(ln1=Lw["ln1"].clone(), ln2=Lw["ln2"].clone(), wq=wq, wk=wk, wv=wv, wo=Lw["wo"].clone(),
+                     wg=gu[:, 0].reshape(I, -1).clone(), wu=gu[:, 1].reshape(I, -1).clone(), wd=Lw["wd"].clone())
+            if "bqkv" in Lw:
+                L["bq"], L["bk"], L["bv"] = (t.clone() for t in Lw["bqkv"].split((nq * d, nk * d, nk * d), 0))
+            if "qn" in Lw:
+                L.update(qn=Lw["qn"].clone(), kn=Lw["kn"].clone())
+            W["layers"].append(L)
+        torch.cuda.synchronize(self.device)
+        return dict(c), W
 
     # ops.linear_fwd / ops.linear_dgrad pick the kernel by row count: W-streaming small-M kernels and the split-K skinny path for the
     # one-row-per-prompt top layer and the LM head, the 256x256 ping-pong GEMM (NT forward, NN backward) for M = B*S rows
@@ -806,6 +904,7 @@ class LlamaLRP:
         ready = None                      # (h, rstd1) of this layer, left by the previous layer's down-projection epilogue
         nL = len(self.layers)
         for li, Lw in enumerate(self.layers):
+            self._load_layer(li)
             st = {}
             top = self.sparse_top and li == nL - 1
             if ready is not None:
@@ -928,6 +1027,7 @@ class LlamaLRP:
 
         for li in range(len(self.layers) - 1, -1, -1):
             Lw, st = self.layers[li], fw["stash"][li]
+            self._load_layer(li)
             qkv, qkr = st["qkv"], st["qkr"]
             q_begin = 0
             if "mlp" in latent:

@@ -1457,3 +1457,56 @@ def moe_expert_relevance(idx, w, gw, B, S, E, out=None):
         raise ValueError(f"lrp_moe_expert_relevance: out must be a contiguous float32 [{B}, {E}] tensor, got {out.dtype} {tuple(out.shape)}")
     check(lib.lrp_moe_expert_relevance(p(idx), p(w), p(gw), p(out), B, S, k, E, dt(w), stream()), "lrp_moe_expert_relevance")
     return out
+
+
+# ------------------------------------------------------------------------------------- MXFP4 weights
+MX_BLOCK = 32            # elements per e8m0 scale (include/lrp_hip_mxfp4.h)
+
+
+def _mx_matrix(name, t, what):
+    """the un-quantised side of the MXFP4 pair: [rows, cols] float32 / bfloat16 on the device, unit column stride (a row pitch is allowed)"""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: lrp_hip kernels need device tensors (no CPU fallback)")
+    if t.dim() != 2 or t.stride(1) != 1 or t.dtype not in _DT:
+        raise ValueError(f"{name}: {what} must be a 2-D float32 / bfloat16 matrix with contiguous rows, got {t.dtype} {tuple(t.shape)}")
+    if t.shape[0] < 1 or t.shape[1] < MX_BLOCK or t.shape[1] % MX_BLOCK:
+        raise ValueError(f"{name}: {what} is {tuple(t.shape)}; the blocks run along the columns, which must be a multiple of {MX_BLOCK}")
+
+
+def _mx_bytes(name, t, what, rows, cols, ref):
+    """codes [rows, cols / 2] / scales [rows, cols / 32]: uint8 on ref's device, unit column stride (a row pitch is allowed)"""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: lrp_hip kernels need device tensors (no CPU fallback)")
+    if t.dtype != torch.uint8 or tuple(t.shape) != (rows, cols) or t.stride(1) != 1 or t.device != ref.device:
+        raise ValueError(f"{name}: {what} must be uint8 [{rows}, {cols}] with contiguous rows on {ref.device}, got {t.dtype} {tuple(t.shape)} "
+                         f"on {t.device}")
+
+
+def mxfp4_quantize(w, codes=None, scales=None):
+    """w [rows, cols] (float32 / bfloat16, cols % 32 == 0; a row pitch is allowed) -> (codes uint8 [rows, cols / 2], scales uint8
+    [rows, cols / 32]): OCP MXFP4, e2m1 codes (two per byte, low nibble first) and one e8m0 scale per 32 elements along the columns;
+    round-to-nearest, ties to the even code (include/lrp_hip_mxfp4.h states the format in full)"""
+    name = "lrp_mxfp4_quantize"
+    _mx_matrix(name, w, "w")
+    rows, cols = w.shape
+    if codes is None:
+        codes = torch.empty(rows, cols // 2, device=w.device, dtype=torch.uint8)
+    if scales is None:
+        scales = torch.empty(rows, (cols // MX_BLOCK + 3) // 4 * 4, device=w.device, dtype=torch.uint8)[:, : cols // MX_BLOCK]      # (pitch on the 4-byte grid)
+    _mx_bytes(name, codes, "codes", rows, cols // 2, w)
+    _mx_bytes(name, scales, "scales", rows, cols // MX_BLOCK, w)
+    check(lib.lrp_mxfp4_quantize(p(w), p(codes), p(scales), rows, cols, w.stride(0), codes.stride(0), scales.stride(0), dt(w), stream()), name)
+    return codes, scales
+
+
+def mxfp4_dequant(codes, scales, out):
+    """out [rows, cols] (float32 / bfloat16; a row pitch is allowed) <- the matrix codes [rows, cols / 2] / scales [rows, cols / 32] hold;
+    every value is exact in both types"""
+    name = "lrp_mxfp4_dequant"
+    _mx_matrix(name, out, "out")
+    rows, cols = out.shape
+    _mx_bytes(name, codes, "codes", rows, cols // 2, out)
+    _mx_bytes(name, scales, "scales", rows, cols // MX_BLOCK, out)
+    check(lib.lrp_mxfp4_dequant(p(codes), p(scales), p(out), rows, cols, codes.stride(0), scales.stride(0), out.stride(0), dt(out), stream()),
+          name)
+    return out
