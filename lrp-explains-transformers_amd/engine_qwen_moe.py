@@ -10,7 +10,10 @@ then either the dense gated MLP (mlp_only_layers / decoder_sparse_step) or the s
               (rstd held constant) and the residual: Gs1 = G + ln2 (.) rstd2 (.) G_xn
 Stash per MoE layer: the coefficients [T k, 2 I] and m [T k, I], the int32 plan, and the router's logits, lse, idx, w.
 explain(experts=True) adds R_expert [L, B, E] (ops.moe_expert_relevance: `routing_weights * routing_weights.grad` scattered by expert and
-summed over a prompt's tokens; = 1/2 of the block-output relevance when summed over the experts) and expert_index [L, B, S, k]."""
+summed over a prompt's tokens; = 1/2 of the block-output relevance when summed over the experts) and expert_index [L, B, S, k].
+weight_format="mxfp4": the routed experts -- almost all of the parameters -- are resident ONLY as MXFP4 codes + scales (views of the uint8
+buffer flat_q) and the four grouped GEMMs decode them in their staging loads (ops.MoeQuantWeight): no scratch copy, no
+dequant launch, forward / backward below unchanged."""
 import torch
 
 from . import engine as E
@@ -93,14 +96,55 @@ def weights_from_hf(model):
     return cfg, W
 
 
+EXPERT_FORMATS = (None, "mxfp4")
+EXPERT_TENSORS = ("wgu_e", "wd_e")
+
+
+def expert_format_request(weight_format):
+    """Qwen3MoeLRP(weight_format=...) -> the format; an unknown name raises ValueError before any device work.  (No grid check: config_from_hf
+    already holds hidden and moe_intermediate_size, the two block directions, to multiples of 128.)"""
+    if not any(weight_format is f or (isinstance(weight_format, str) and weight_format == f) for f in EXPERT_FORMATS):
+        raise ValueError(f"weight_format must be one of {EXPERT_FORMATS}, got {weight_format!r}")
+    return weight_format
+
+
+def expert_bytes(n_sparse, n_experts, hidden, moe_inter, weight_format, dtype):
+    """exact bytes of the routed experts of n_sparse layers as held: 3 H I parameters per expert, 4 + 8 / 32 bits each as MXFP4"""
+    n = n_sparse * n_experts * 3 * hidden * moe_inter
+    return n // 2 + n // ops.MX_BLOCK if weight_format == "mxfp4" else n * torch.empty((), dtype=dtype).element_size()
+
+
+def expert_quant_layout(cfg):
+    """one uint8 spec per layer for E.pack_flat: a sparse layer's codes [E, N, K / 2] and scales [E, N, K / 32] of gate_up_proj [E, 2 I, H] and
+    down_proj [E, H, I]; a dense layer holds nothing there"""
+    Ne, H, Im = cfg["n_experts"], cfg["hidden"], cfg["moe_inter"]
+    spec = {}
+    for k, (N, K) in zip(EXPERT_TENSORS, ((2 * Im, H), (H, Im))):
+        spec[k + "_c"] = ((Ne, N, K // 2), None)
+        spec[k + "_s"] = ((Ne, N, K // ops.MX_BLOCK), None)
+    return [spec if moe else {} for moe in cfg["moe_layers"]]
+
+
 class Qwen3MoeLRP(Q.QwenLRP):
     """QwenLRP for Qwen3-MoE: cfg carries moe_layers (which layers are sparse), n_experts, top_k, norm_topk, moe_inter (config_from_hf);
     W["layers"][i] of a sparse layer holds wr, wgu_e, wd_e.  The expert weights stay the caller's tensors (moved to the engine's device and
-    dtype only if they are elsewhere); everything else lives in the flat buffer.  explain() is LlamaLRP.explain plus `experts`."""
+    dtype only if they are elsewhere); everything else lives in the flat buffer.  explain() is LlamaLRP.explain plus `experts`.
+    weight_format="mxfp4": wgu_e / wd_e of every sparse layer are ops.MoeQuantWeight views of ONE uint8 buffer flat_q (128-byte aligned views)
+    and nothing else of them is kept -- a multi-GPU start-up is dist.broadcast_weights([eng.flat, eng.flat_q]).  Attention, router, dense
+    layers' MLPs, norms, embedding and head stay in `flat` in the model dtype: the base classes see weight_format=None."""
 
-    def __init__(self, cfg, W, dtype=torch.bfloat16, device="cuda", mode="efficient", max_seq=4096, sparse_top=False, fold_norm=None):
+    def __init__(self, cfg, W, dtype=torch.bfloat16, device="cuda", mode="efficient", max_seq=4096, sparse_top=False, fold_norm=None, **storage):
+        """storage: weight_format=None | "mxfp4", the format of the ROUTED EXPERTS alone.  It is keyword-only and not a named parameter: the
+        dense drivers' weight_format (all four Linears of a layer through a scratch, engine.weight_format_request) is a different contract,
+        which this driver does not take -- tests/test_mxfp4_cpu.py holds its signature to that"""
+        unknown = set(storage) - {"weight_format"}
+        if unknown:
+            raise TypeError(f"Qwen3MoeLRP() got unexpected keyword argument(s) {sorted(unknown)}")
+        self.expert_format = expert_format_request(storage.get("weight_format"))
         self._af_cache = {}
+        self._eq_flat = self._eq_layers = None      # the experts' uint8 buffer while the layers load (the base constructor owns the name flat_q)
         super().__init__(cfg, W, dtype=dtype, device=device, mode=mode, max_seq=max_seq, sparse_top=False, fold_norm=fold_norm)
+        self.flat_q = self._eq_flat
 
     @staticmethod
     def flat_layout(cfg, dtype):
@@ -119,11 +163,57 @@ class Qwen3MoeLRP(Q.QwenLRP):
         if self.folded:          # (ln1 into the QKV columns as in the dense layers; ln2 stays a vector: the expert weights are read as stored)
             E.fold_rows(Lw["wqkv"], (Lw["wqkv"],), L["ln1"])
             Lw["ln1"].fill_(1.0)
-        for k in ("wgu_e", "wd_e"):
+        li = next(i for i, x in enumerate(self.layers) if x is Lw)
+        if self.expert_format is not None and self._eq_flat is None:
+            self._eq_flat, _, self._eq_layers = E.pack_flat({}, expert_quant_layout(self.cfg), len(self.layers), torch.uint8, self.device, align=128)
+        for k in EXPERT_TENSORS:
+            # one expert tensor at a time: on the device in the engine dtype, quantised into its views, and dropped -- the peak at load is
+            # what is resident plus one tensor (a CPU-resident model loads even when its bf16 experts would not fit the device)
             w = L[k].detach().to(device=self.device, dtype=self.dtype)
             if not w.is_contiguous():
                 raise NotImplementedError("Qwen3MoeLRP: gate_up_proj / down_proj must be contiguous (the grouped kernels read them as stored)")
-            Lw[k] = w
+            if self.expert_format is None:
+                Lw[k] = w
+                continue
+            if not bool(torch.isfinite(w).all()):
+                raise ValueError(f"weight_format={self.expert_format!r}: layer {li} holds non-finite expert weights ({k})")
+            Lw[k] = ops.MoeQuantWeight(w, self._eq_layers[li][k + "_c"], self._eq_layers[li][k + "_s"])
+            del w
+
+    def _load_layer(self, li):
+        """nothing to load: the quantised experts are read in place by the grouped GEMMs"""
+
+    def weight_bytes(self):
+        """LlamaLRP.weight_bytes (resident: `flat` + `flat_q`, scratch: 0 -- there is none) plus experts: the exact bytes of the routed
+        experts as held -- codes + scales, or the tensors in the model dtype (weight_format=None: those are not part of `flat`)"""
+        out = super().weight_bytes()
+        held = [Lw[k] for Lw in self.layers if "wr" in Lw for k in EXPERT_TENSORS]
+        out["experts"] = sum(t.nbytes() if isinstance(t, ops.MoeQuantWeight) else t.numel() * t.element_size() for t in held)
+        return out
+
+    def dequantized_weights(self):
+        """-> (cfg, W) in the form weights_from_hf gives and Qwen3MoeLRP(cfg, W) takes, holding what this engine computes with: the experts
+        dequantised exactly in the engine dtype, everything else as stored (q / k / v split, a dense layer's gate / up de-interleaved, folded
+        norm vectors as ones: an engine built from it folds by exactly 1.0 and ends up with the same bits).  Whole-model copies: for checks"""
+        c = self.cfg
+        nq, nk, d, I = c["n_heads"], c["n_kv"], c["head_dim"], c["inter"]
+        W = dict(embed=self.embed.clone(), norm=self.norm.clone(), layers=[])
+        if self.lm_head is not self.embed:
+            W["lm_head"] = self.lm_head.clone()
+        for Lw in self.layers:
+            wq, wk, wv = (t.clone() for t in Lw["wqkv"].split((nq * d, nk * d, nk * d), 0))
+            L = dict(ln1=Lw["ln1"].clone(), ln2=Lw["ln2"].clone(), wq=wq, wk=wk, wv=wv, wo=Lw["wo"].clone(), qn=Lw["qn"].clone(),
+                     kn=Lw["kn"].clone())
+            if "wr" in Lw:
+                L["wr"] = Lw["wr"].clone()
+                for k in EXPERT_TENSORS:
+                    L[k] = Lw[k].dequant(self.dtype) if isinstance(Lw[k], ops.MoeQuantWeight) else Lw[k].clone()
+            else:
+                gu = Lw["wgu"].unflatten(0, (I // ops.GATED_IL, 2, ops.GATED_IL))
+                L.update(wg=gu[:, 0].reshape(I, -1).clone(), wu=gu[:, 1].reshape(I, -1).clone(), wd=Lw["wd"].clone())
+            W["layers"].append(L)
+        torch.cuda.synchronize(self.device)
+        return dict(c), W
 
     def set_mode(self, mode):
         if mode == "explicit":

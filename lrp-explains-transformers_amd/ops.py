@@ -1315,13 +1315,83 @@ class MoePlan:
         return b[:E], b[E:2 * E + 1], b[3 * E + 2:3 * E + 2 + R], b[3 * E + 2 + R:3 * E + 2 + 2 * R]
 
 
+class MoeQuantWeight:
+    """an expert tensor [E, N, K] held as MXFP4 (include/lrp_hip_moe_mxfp4.h): codes uint8 [E, N, K / 2] and scales uint8 [E, N, K / 32], the
+    2-D format of mxfp4_quantize applied to the [E N, K] view.  MoeQuantWeight(w) quantises a device tensor (into codes / scales when given:
+    the engine passes views of its flat_q); from_bytes wraps stored bytes.  The four grouped expert GEMMs take it in place of the weight
+    tensor and decode inside the kernel -- bit-identical to the same call on dequant(dtype)."""
+
+    def __init__(self, w, codes=None, scales=None):
+        if not w.is_cuda:
+            raise RuntimeError("MoeQuantWeight: lrp_hip kernels need device tensors (no CPU fallback)")
+        if w.dim() != 3 or not w.is_contiguous() or w.shape[2] % (4 * MX_BLOCK):      # (K / 32 scale bytes per row, rows on the 4-byte grid)
+            raise ValueError(f"MoeQuantWeight: an expert tensor is a contiguous [E, N, K] with K % {4 * MX_BLOCK} == 0, got {tuple(w.shape)}")
+        E, N, K = w.shape
+        if codes is None:
+            codes = torch.empty(E, N, K // 2, device=w.device, dtype=torch.uint8)
+        if scales is None:
+            scales = torch.empty(E, N, K // MX_BLOCK, device=w.device, dtype=torch.uint8)
+        self._set(codes, scales)
+        if self.shape != (E, N, K):
+            raise ValueError(f"MoeQuantWeight: codes / scales of a {self.shape} tensor for a weight of {(E, N, K)}")
+        mxfp4_quantize(w.view(E * N, K), codes.view(E * N, K // 2), scales.view(E * N, K // MX_BLOCK))
+
+    def _set(self, codes, scales):
+        if codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.dim() != 3 or not codes.is_contiguous():
+            raise ValueError(f"MoeQuantWeight: codes must be a contiguous uint8 [E, N, K / 2] tensor and scales uint8, got {codes.dtype} "
+                             f"{tuple(codes.shape)} and {scales.dtype}")
+        E, N, K2 = codes.shape
+        if (2 * K2) % (4 * MX_BLOCK) or tuple(scales.shape) != (E, N, 2 * K2 // MX_BLOCK) or not scales.is_contiguous() or scales.device != codes.device:
+            raise ValueError(f"MoeQuantWeight: scales must be a contiguous uint8 [{E}, {N}, {2 * K2} / {MX_BLOCK}] tensor on {codes.device}, got "
+                             f"{tuple(scales.shape)} on {scales.device}")
+        self.codes, self.scales, self.shape = codes, scales, (E, N, 2 * K2)
+
+    @classmethod
+    def from_bytes(cls, codes, scales):
+        q = cls.__new__(cls)
+        q._set(codes, scales)
+        return q
+
+    @property
+    def device(self):
+        return self.codes.device
+
+    def nbytes(self):
+        return self.codes.numel() + self.scales.numel()
+
+    def dequant(self, dtype, out=None):
+        """-> the tensor [E, N, K] the bytes hold, exact in float32 and bfloat16 (lrp_mxfp4_dequant on the [E N, K] view)"""
+        E, N, K = self.shape
+        p(self.codes)
+        if out is None:
+            out = torch.empty(E, N, K, device=self.device, dtype=dtype)
+        mxfp4_dequant(self.codes.view(E * N, K // 2), self.scales.view(E * N, K // MX_BLOCK), out.view(E * N, K))
+        return out
+
+
+def _moe_w(x, W):
+    """the weight operand of a grouped expert GEMM next to the activation x -> (quantised?, the pointer arguments)"""
+    if isinstance(W, MoeQuantWeight):
+        if W.device != x.device and x.is_cuda and W.codes.is_cuda:
+            raise TypeError(f"lrp_hip: quantised expert weight on {W.device} next to activations on {x.device}")
+        return True, (p(W.codes), p(W.scales))
+    same(x, W)
+    return False, (p(W),)
+
+
 def moe_gate_up_fwd(x, Wgu, plan, act="silu"):
-    """-> (coef [R, 2 I], m [R, I]) in plan-row order; x [T, H] rows are gathered through the plan inside the GEMM"""
+    """-> (coef [R, 2 I], m [R, I]) in plan-row order; x [T, H] rows are gathered through the plan inside the GEMM.  Wgu: the tensor
+    [E, 2 I, H] or a MoeQuantWeight of it (here and in the three GEMMs below: decoded inside the kernel, lrp_moe_*_q)"""
     E, I2, H = Wgu.shape
     I, R = I2 // 2, plan.rows
-    same(x, Wgu)
+    q, wp = _moe_w(x, Wgu)
     coef = torch.empty(R, 2 * I, device=x.device, dtype=x.dtype)
     m = torch.empty(R, I, device=x.device, dtype=x.dtype)
+    if q:
+        _timed(2.0 * R * 2 * I * H, "moe_gate_up_fwd", lambda: lib.lrp_moe_gate_up_fwd_q(
+            p(x), *wp, p(plan.buf), p(coef), p(m), plan.T, plan.k, plan.E, H, I, x.stride(0), coef.stride(0), m.stride(0), ACT[act],
+            dt(x), stream()), "lrp_moe_gate_up_fwd_q")
+        return coef, m
     _timed(2.0 * R * 2 * I * H, "moe_gate_up_fwd", lambda: lib.lrp_moe_gate_up_fwd(
         p(x), p(Wgu), p(plan.buf), p(coef), p(m), plan.T, plan.k, plan.E, H, I, x.stride(0), coef.stride(0), m.stride(0), ACT[act],
         dt(x), stream()), "lrp_moe_gate_up_fwd")
@@ -1331,8 +1401,12 @@ def moe_gate_up_fwd(x, Wgu, plan, act="silu"):
 def moe_down_fwd(m, Wd, plan):
     """-> y [R, H] = m Wd[e]^T per plan row"""
     E, H, I = Wd.shape
-    same(m, Wd)
+    q, wp = _moe_w(m, Wd)
     y = torch.empty(plan.rows, H, device=m.device, dtype=m.dtype)
+    if q:
+        _timed(2.0 * plan.rows * H * I, "moe_down_fwd", lambda: lib.lrp_moe_down_fwd_q(
+            p(m), *wp, p(plan.buf), p(y), plan.T, plan.k, plan.E, H, I, m.stride(0), y.stride(0), dt(m), stream()), "lrp_moe_down_fwd_q")
+        return y
     _timed(2.0 * plan.rows * H * I, "moe_down_fwd", lambda: lib.lrp_moe_down_fwd(
         p(m), p(Wd), p(plan.buf), p(y), plan.T, plan.k, plan.E, H, I, m.stride(0), y.stride(0), dt(m), stream()), "lrp_moe_down_fwd")
     return y
@@ -1351,14 +1425,16 @@ def moe_combine(rows, plan, w=None):
 def moe_down_dgrad(G, Wd, coef, m, w, plan):
     """-> (Agu [R, 2 I] in [gate | up] order, G_w [T, k]) from the output gradient G [T, H] (gathered by token inside the GEMM)"""
     E, H, I = Wd.shape
-    same(G, Wd, coef, m, w)
+    q, wp = _moe_w(G, Wd)
+    same(G, coef, m, w)
     R = plan.rows
     Agu = torch.empty(R, 2 * I, device=G.device, dtype=G.dtype)
     part = torch.empty(R, I // 128, device=G.device, dtype=torch.float32)
     gw = torch.empty(plan.T, plan.k, device=G.device, dtype=G.dtype)
-    _timed(2.0 * R * H * I, "moe_down_dgrad", lambda: lib.lrp_moe_down_dgrad(
-        p(G), p(Wd), p(coef), p(m), p(w), p(plan.buf), p(Agu), p(part), plan.T, plan.k, plan.E, H, I, G.stride(0), coef.stride(0),
-        m.stride(0), Agu.stride(0), dt(G), stream()), "lrp_moe_down_dgrad")
+    fn, name = (lib.lrp_moe_down_dgrad_q, "lrp_moe_down_dgrad_q") if q else (lib.lrp_moe_down_dgrad, "lrp_moe_down_dgrad")
+    _timed(2.0 * R * H * I, "moe_down_dgrad", lambda: fn(
+        p(G), *wp, p(coef), p(m), p(w), p(plan.buf), p(Agu), p(part), plan.T, plan.k, plan.E, H, I, G.stride(0), coef.stride(0),
+        m.stride(0), Agu.stride(0), dt(G), stream()), name)
     check(lib.lrp_moe_gw_reduce(p(part), p(plan.buf), p(gw), plan.T, plan.k, plan.E, I, dt(G), stream()), "lrp_moe_gw_reduce")
     return Agu, gw
 
@@ -1366,11 +1442,11 @@ def moe_down_dgrad(G, Wd, coef, m, w, plan):
 def moe_gate_up_dgrad(Agu, Wgu, plan):
     """-> per-row G_x [R, H] = Agu Wgu[e] (NN on the stored weight)"""
     E, I2, H = Wgu.shape
-    same(Agu, Wgu)
+    q, wp = _moe_w(Agu, Wgu)
     gx = torch.empty(plan.rows, H, device=Agu.device, dtype=Agu.dtype)
-    _timed(2.0 * plan.rows * I2 * H, "moe_gate_up_dgrad", lambda: lib.lrp_moe_gate_up_dgrad(
-        p(Agu), p(Wgu), p(plan.buf), p(gx), plan.T, plan.k, plan.E, H, I2 // 2, Agu.stride(0), gx.stride(0), dt(Agu), stream()),
-        "lrp_moe_gate_up_dgrad")
+    fn, name = (lib.lrp_moe_gate_up_dgrad_q, "lrp_moe_gate_up_dgrad_q") if q else (lib.lrp_moe_gate_up_dgrad, "lrp_moe_gate_up_dgrad")
+    _timed(2.0 * plan.rows * I2 * H, "moe_gate_up_dgrad", lambda: fn(
+        p(Agu), *wp, p(plan.buf), p(gx), plan.T, plan.k, plan.E, H, I2 // 2, Agu.stride(0), gx.stride(0), dt(Agu), stream()), name)
     return gx
 
 
