@@ -330,7 +330,6 @@ LRP_DEVICE bool xcd_group_decode(int L, int ngroups, int per_group, int& group, 
     (void)rounds;
     return group < ngroups;
 }
-inline int xcd_group_grid(int ngroups, int per_group) { return ((ngroups + 7) / 8) * 8 * per_group; }
 
 // =================================================================================================
 // backward dQ: row side = queries (registers); column side = keys (K, V row-major + K^T in LDS)
@@ -1096,11 +1095,26 @@ __global__ void gqa_reduce_rope_kernel(const T* in, T* out, int64_t rows, int se
     }
 }
 
-template <typename K> void set_lds(K kern, size_t bytes) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// ---- one launch expression per kernel family.  mid: the 8-wave kernels take B (their 1-D grid decode needs it) between window and q_begin
+template <auto Kern, typename T, typename... Mid>
+void launch_fwd(const AttnCall& c, dim3 grid, int threads, size_t lds, Mid... mid) {
+    lrp_launch_lds<Kern>(grid, dim3(threads), lds, lds, c.st, (const T*)c.q, (const T*)c.k, (const T*)c.v_t, (T*)c.o, c.lse_out, c.S, c.Hq, c.Hkv,
+                         c.ldq, c.ldk, c.ldt, c.ldo, c.scale, c.causal, c.window, mid..., c.q_begin, c.row_lo, c.row_hi);
+}
+template <auto Kern, typename T, typename... Mid>
+void launch_dq(const AttnCall& c, dim3 grid, int threads, size_t lds, Mid... mid) {
+    lrp_launch_lds<Kern>(grid, dim3(threads), lds, lds, c.st, (const T*)c.q, (const T*)c.k, (const T*)c.v, (const T*)c.k_t, (const T*)c.gho, c.lse,
+                         c.D, (T*)c.dq, c.S, c.Hq, c.Hkv, c.ldq, c.ldk, c.ldv, c.ldt, c.ldg, c.lddq, c.scale, c.eps_mask, c.eps_qk, c.causal,
+                         c.window, mid..., c.q_begin, c.row_lo, c.row_hi);
+}
+template <auto Kern, typename T, typename... Mid>
+void launch_dkv(const AttnCall& c, dim3 grid, int threads, size_t lds, Mid... mid) {
+    lrp_launch_lds<Kern>(grid, dim3(threads), lds, lds, c.st, (const T*)c.q, (const T*)c.k, (const T*)c.v, (const T*)c.q_t, (const T*)c.gho,
+                         (const T*)c.gho_t, c.lse, c.D, (T*)c.dk, (T*)c.dv, c.S, c.Hq, c.Hkv, c.ldq, c.ldk, c.ldv, c.ldt, c.ldg, c.lddk, c.lddv,
+                         c.scale, c.eps_mask, c.eps_qk, c.causal, c.window, mid..., c.q_begin, c.row_lo, c.row_hi);
+}
 
 }  // namespace
 
@@ -1108,55 +1122,48 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 static inline bool use_attn32(int dtype, int d) { return dtype == LRP_BF16 && (d == 64 || d == 96 || d == 128 || d == 256); }
 extern "C" int lrp_attn_needs_transposed(int dtype, int d) { return use_attn32(dtype, d) ? 0 : 1; }
 
+// head dims with an instantiation in this file: fp32 16 ... 256; bf16 32 ALONE -- use_attn32() sent 64, 96, 128 and 256 to attention32.hip
+// before this point and a 16-wide bf16 row is below the 64 bytes a fragment read needs
 #define ATT_DISPATCH_D(T, d, ...)                                   \
     if ((size_t)d * sizeof(T) < 64) return LRP_ESHAPE;              \
+    if (sizeof(T) == 2 && d != 32) return LRP_ESHAPE;               \
     switch (d) {                                                    \
-        case 16: if constexpr (sizeof(T) == 4) { constexpr int DD = 16; __VA_ARGS__ } break;   /* fp32 only: the line above refused bf16 */ \
+        case 16: if constexpr (sizeof(T) == 4) { constexpr int DD = 16; __VA_ARGS__ } break;   \
         case 32: { constexpr int DD = 32; __VA_ARGS__ } break;      \
-        case 64: { constexpr int DD = 64; __VA_ARGS__ } break;      \
-        case 128: { constexpr int DD = 128; __VA_ARGS__ } break;    \
-        case 256: { constexpr int DD = 256; __VA_ARGS__ } break;    \
+        case 64: if constexpr (sizeof(T) == 4) { constexpr int DD = 64; __VA_ARGS__ } break;   \
+        case 128: if constexpr (sizeof(T) == 4) { constexpr int DD = 128; __VA_ARGS__ } break; \
+        case 256: if constexpr (sizeof(T) == 4) { constexpr int DD = 256; __VA_ARGS__ } break; \
         default: return LRP_ESHAPE;                                 \
     }
 
-template <typename T>
-static int attn_fwd_t(const void* q, const void* k, const void* vt, void* o, float* lse, int B, int S, int Hq, int Hkv,
-                      int d, int64_t ldq, int64_t ldk, int64_t ldt, int64_t ldo, float scale, int causal, int window,
-                      int q_begin, const int* row_lo, const int* row_hi, hipStream_t st) {
+// the 8-wave (_v2) kernels: transposed operands padded to whole column tiles, rows of >= 64 bytes, d <= 128; everything else on the 4-wave kernels
+template <typename T> static bool attn_8wave(const AttnCall& c) {
     constexpr int SZ = sizeof(T), CT = 128 / SZ;
-    if ((ldt % CT) == 0 && ((size_t)d * SZ >= 64) && d <= 128) {
-        ATT_DISPATCH_D(T, d, {
+    return (c.ldt % CT) == 0 && ((size_t)c.d * SZ >= 64) && c.d <= 128;
+}
+
+template <typename T>
+static int attn_fwd_t(const AttnCall& c) {
+    constexpr int SZ = sizeof(T), CT = 128 / SZ;
+    if (attn_8wave<T>(c)) {
+        ATT_DISPATCH_D(T, c.d, {
             if constexpr (DD <= 128) {
                 const size_t lds = 2 * (2 * (size_t)128 * DD);
-                const int rep = Hq / Hkv;
+                const int rep = c.Hq / c.Hkv;
                 // 256-query workgroups (two 16-row sub-tiles per wave: every K/V fragment read feeds two
                 // MFMAs) once that still leaves >= 2 workgroups per CU, else 128-query workgroups
-                if ((int64_t)B * Hq * ((S + 255) / 256) >= 512) {
-                    auto kern = attn_fwd_v2_kernel<T, DD, 2>;
-                    set_lds(kern, lds);
-                    dim3 grid(xcd_group_grid(B * Hkv, rep * ((S + 255) / 256)));
-                    hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, (const T*)q, (const T*)k, (const T*)vt, (T*)o, lse, S, Hq,
-                                       Hkv, ldq, ldk, ldt, ldo, scale, causal, window, B, q_begin, row_lo, row_hi);
-                } else {
-                    auto kern = attn_fwd_v2_kernel<T, DD, 1>;
-                    set_lds(kern, lds);
-                    dim3 grid(xcd_group_grid(B * Hkv, rep * ((S + 127) / 128)));
-                    hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, (const T*)q, (const T*)k, (const T*)vt, (T*)o, lse, S, Hq,
-                                       Hkv, ldq, ldk, ldt, ldo, scale, causal, window, B, q_begin, row_lo, row_hi);
-                }
+                if ((int64_t)c.B * c.Hq * ((c.S + 255) / 256) >= 512)
+                    launch_fwd<attn_fwd_v2_kernel<T, DD, 2>, T>(c, dim3(xcd_group_grid(c.B * c.Hkv, rep * ((c.S + 255) / 256))), 512, lds, c.B);
+                else
+                    launch_fwd<attn_fwd_v2_kernel<T, DD, 1>, T>(c, dim3(xcd_group_grid(c.B * c.Hkv, rep * ((c.S + 127) / 128))), 512, lds, c.B);
             }
         })
         return lrp_check_launch();
     }
-    ATT_DISPATCH_D(T, d, {
+    ATT_DISPATCH_D(T, c.d, {
         constexpr int QSUB = (DD >= 256) ? 1 : 2;
-        const size_t lds = (size_t)CT * DD * SZ + (size_t)DD * 128;
-        auto kern = attn_fwd_kernel<T, DD, QSUB>;
-        set_lds(kern, lds);
-        const int BQ = 64 * QSUB;
-        dim3 grid((S + BQ - 1) / BQ, Hq, B);
-        hipLaunchKernelGGL(kern, grid, dim3(ANT), lds, st, (const T*)q, (const T*)k, (const T*)vt, (T*)o, lse, S, Hq, Hkv,
-                           ldq, ldk, ldt, ldo, scale, causal, window, q_begin, row_lo, row_hi);
+        constexpr int BQ = 64 * QSUB;
+        launch_fwd<attn_fwd_kernel<T, DD, QSUB>, T>(c, dim3((c.S + BQ - 1) / BQ, c.Hq, c.B), ANT, (size_t)CT * DD * SZ + (size_t)DD * 128);
     })
     return lrp_check_launch();
 }
@@ -1178,49 +1185,41 @@ extern "C" int lrp_attn_fwd(const void* q, const void* k, const void* v, const v
     if (rc) return rc;
     if (B == 0 || S == 0) return LRP_OK;
     const int epc = dtype == LRP_F32 ? 4 : 8;
-    hipStream_t st = (hipStream_t)stream;
-    if (use_attn32(dtype, d)) {
+    const bool a32 = use_attn32(dtype, d);
+    if (a32) {
         if (!v) return LRP_EINVAL;
         if (!al16(q) || !al16(k) || !al16(v) || !al16(o) || (ldq % epc) || (ldk % epc) || (ldv % epc) || (ldo % 4)) return LRP_EALIGN;
-        if (d == 256) return lrp_attn32_fwd_d256(q, k, v, o, lse, B, S, Hq, Hkv, ldq, ldk, ldv, ldo, scale, causal, window, q_begin, row_lo, row_hi, st);
-        return lrp_attn32_fwd(q, k, v, o, lse, B, S, Hq, Hkv, d, ldq, ldk, ldv, ldo, scale, causal, window, q_begin, row_lo, row_hi, st);
+    } else {
+        if (!v_t) return LRP_EINVAL;
+        if (!al16(q) || !al16(k) || !al16(v_t) || !al16(o) || (ldq % epc) || (ldk % epc) || (ldt % epc) || (ldo % 4) || ldt < S) return LRP_EALIGN;
     }
-    if (!v_t) return LRP_EINVAL;
-    if (!al16(q) || !al16(k) || !al16(v_t) || !al16(o) || (ldq % epc) || (ldk % epc) || (ldt % epc) || (ldo % 4) || ldt < S) return LRP_EALIGN;
-    if (dtype == LRP_F32) return attn_fwd_t<float>(q, k, v_t, o, lse, B, S, Hq, Hkv, d, ldq, ldk, ldt, ldo, scale, causal, window, q_begin, row_lo, row_hi, st);
-    return attn_fwd_t<bf16_t>(q, k, v_t, o, lse, B, S, Hq, Hkv, d, ldq, ldk, ldt, ldo, scale, causal, window, q_begin, row_lo, row_hi, st);
+    AttnCall c = {};
+    c.q = q; c.k = k; c.v = v; c.v_t = v_t; c.o = o; c.lse_out = lse;
+    c.B = B; c.S = S; c.Hq = Hq; c.Hkv = Hkv; c.d = d;
+    c.ldq = ldq; c.ldk = ldk; c.ldv = ldv; c.ldt = ldt; c.ldo = ldo;
+    c.scale = scale; c.causal = causal; c.window = window; c.q_begin = q_begin;
+    c.row_lo = row_lo; c.row_hi = row_hi; c.st = (hipStream_t)stream;
+    if (a32) return lrp_attn32_fwd(c);
+    return dtype == LRP_F32 ? attn_fwd_t<float>(c) : attn_fwd_t<bf16_t>(c);
 }
 
 template <typename T>
-static int attn_dq_t(const void* q, const void* k, const void* v, const void* kt, const void* gho, const float* lse,
-                     const float* D, void* dq, int B, int S, int Hq, int Hkv, int d, int64_t ldq, int64_t ldk, int64_t ldv,
-                     int64_t ldt, int64_t ldg, int64_t lddq, float scale, float eps_mask, float eps_qk, int causal, int window,
-                     int q_begin, const int* row_lo, const int* row_hi, hipStream_t st) {
+static int attn_dq_t(const AttnCall& c) {
     constexpr int SZ = sizeof(T), CT = 128 / SZ;
-    if ((ldt % CT) == 0 && ((size_t)d * SZ >= 64) && d <= 128) {
-        ATT_DISPATCH_D(T, d, {
+    if (attn_8wave<T>(c)) {
+        ATT_DISPATCH_D(T, c.d, {
             if constexpr (DD <= 128) {
                 const size_t lds = 2 * (3 * (size_t)128 * DD);
-                dim3 grid(xcd_group_grid(B * Hkv, (Hq / Hkv) * ((S + 127) / 128)));
-                auto launch = [&](auto kern) {
-                    set_lds(kern, lds);
-                    hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, (const T*)q, (const T*)k, (const T*)v, (const T*)kt,
-                                       (const T*)gho, lse, D, (T*)dq, S, Hq, Hkv, ldq, ldk, ldv, ldt, ldg, lddq, scale, eps_mask,
-                                       eps_qk, causal, window, B, q_begin, row_lo, row_hi);
-                };
-                if (eps_mask != 0.f || eps_qk != 0.f) launch(attn_bwd_dq_v2_kernel<T, DD, true>);
-                else launch(attn_bwd_dq_v2_kernel<T, DD, false>);
+                dim3 grid(xcd_group_grid(c.B * c.Hkv, (c.Hq / c.Hkv) * ((c.S + 127) / 128)));
+                lrp_with_bool(c.eps_mask != 0.f || c.eps_qk != 0.f, [&](auto ex) {
+                    launch_dq<attn_bwd_dq_v2_kernel<T, DD, decltype(ex)::value>, T>(c, grid, 512, lds, c.B);
+                });
             }
         })
         return lrp_check_launch();
     }
-    ATT_DISPATCH_D(T, d, {
-        const size_t lds = 2 * (size_t)CT * DD * SZ + (size_t)DD * 128;
-        auto kern = attn_bwd_dq_kernel<T, DD>;
-        set_lds(kern, lds);
-        dim3 grid((S + 63) / 64, Hq, B);
-        hipLaunchKernelGGL(kern, grid, dim3(ANT), lds, st, (const T*)q, (const T*)k, (const T*)v, (const T*)kt, (const T*)gho,
-                           lse, D, (T*)dq, S, Hq, Hkv, ldq, ldk, ldv, ldt, ldg, lddq, scale, eps_mask, eps_qk, causal, window, q_begin, row_lo, row_hi);
+    ATT_DISPATCH_D(T, c.d, {
+        launch_dq<attn_bwd_dq_kernel<T, DD>, T>(c, dim3((c.S + 63) / 64, c.Hq, c.B), ANT, 2 * (size_t)CT * DD * SZ + (size_t)DD * 128);
     })
     return lrp_check_launch();
 }
@@ -1237,15 +1236,20 @@ extern "C" int lrp_attn_bwd_dq(const void* q, const void* k, const void* v, cons
     const int epc = dtype == LRP_F32 ? 4 : 8;
     if (!al16(q) || !al16(k) || !al16(v) || !al16(Gho) || !al16(dq) || (ldq % epc) || (ldk % epc) ||
         (ldv % epc) || (ldgho % epc) || (lddq % 4)) return LRP_EALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    if (use_attn32(dtype, d) && d == 256)
-        return lrp_attn32_dq_d256(q, k, v, Gho, lse, D, dq, B, S, Hq, Hkv, ldq, ldk, ldv, ldgho, lddq, scale, eps_mask, eps_qk, causal, window, q_begin, row_lo, row_hi, st);
-    if (use_attn32(dtype, d))
-        return lrp_attn32_dq(q, k, v, Gho, lse, D, dq, B, S, Hq, Hkv, d, ldq, ldk, ldv, ldgho, lddq, scale, eps_mask, eps_qk, causal, window, q_begin, row_lo, row_hi, st);
-    if (!k_t) return LRP_EINVAL;
-    if (!al16(k_t) || (ldt % epc) || ldt < S) return LRP_EALIGN;
-    if (dtype == LRP_F32) return attn_dq_t<float>(q, k, v, k_t, Gho, lse, D, dq, B, S, Hq, Hkv, d, ldq, ldk, ldv, ldt, ldgho, lddq, scale, eps_mask, eps_qk, causal, window, q_begin, row_lo, row_hi, st);
-    return attn_dq_t<bf16_t>(q, k, v, k_t, Gho, lse, D, dq, B, S, Hq, Hkv, d, ldq, ldk, ldv, ldt, ldgho, lddq, scale, eps_mask, eps_qk, causal, window, q_begin, row_lo, row_hi, st);
+    const bool a32 = use_attn32(dtype, d);
+    if (!a32) {
+        if (!k_t) return LRP_EINVAL;
+        if (!al16(k_t) || (ldt % epc) || ldt < S) return LRP_EALIGN;
+    }
+    AttnCall c = {};
+    c.q = q; c.k = k; c.v = v; c.gho = Gho; c.lse = lse; c.D = D;
+    c.B = B; c.S = S; c.Hq = Hq; c.Hkv = Hkv; c.d = d;
+    c.ldq = ldq; c.ldk = ldk; c.ldv = ldv; c.ldg = ldgho; c.ldt = ldt;
+    c.scale = scale; c.eps_mask = eps_mask; c.eps_qk = eps_qk; c.causal = causal; c.window = window; c.q_begin = q_begin;
+    c.row_lo = row_lo; c.row_hi = row_hi; c.st = (hipStream_t)stream;
+    c.dq = dq; c.lddq = lddq; c.k_t = k_t;
+    if (a32) return lrp_attn32_dq(c);
+    return dtype == LRP_F32 ? attn_dq_t<float>(c) : attn_dq_t<bf16_t>(c);
 }
 
 // dQ with the statistic D_i = sum_d Gho_i o_i formed in the kernel's prologue (lxt.efficient placement: no stabiliser on P.V or the scores, so
@@ -1266,41 +1270,33 @@ extern "C" int lrp_attn_bwd_dq_d(const void* q, const void* k, const void* v, co
     if (B == 0 || S == 0) return LRP_OK;
     if (!al16(q) || !al16(k) || !al16(v) || !al16(Gho) || !al16(o) || !al16(dq) || (ldq % 8) || (ldk % 8) || (ldv % 8) || (ldgho % 8) ||
         (ldo % 8) || (lddq % 4)) return LRP_EALIGN;
-    return lrp_attn32_dq(q, k, v, Gho, lse, nullptr, dq, B, S, Hq, Hkv, d, ldq, ldk, ldv, ldgho, lddq, scale, 0.f, 0.f, causal, window, 0,
-                         row_lo, row_hi, (hipStream_t)stream, o, ldo, D, cos_t, sin_t);
+    AttnCall c = {};
+    c.q = q; c.k = k; c.v = v; c.gho = Gho; c.lse = lse; c.D = nullptr;
+    c.B = B; c.S = S; c.Hq = Hq; c.Hkv = Hkv; c.d = d;
+    c.ldq = ldq; c.ldk = ldk; c.ldv = ldv; c.ldg = ldgho;
+    c.scale = scale; c.causal = causal; c.window = window;
+    c.row_lo = row_lo; c.row_hi = row_hi; c.st = (hipStream_t)stream;
+    c.dq = dq; c.lddq = lddq; c.ofw = o; c.ldo = ldo; c.Dout = D; c.cos_t = cos_t; c.sin_t = sin_t;
+    return lrp_attn32_dq(c);
 }
 
 template <typename T>
-static int attn_dkv_t(const void* q, const void* k, const void* v, const void* qt, const void* gho, const void* ghot,
-                      const float* lse, const float* D, void* dk, void* dv, int B, int S, int Hq, int Hkv, int d, int64_t ldq,
-                      int64_t ldk, int64_t ldv, int64_t ldt, int64_t ldg, int64_t lddk, int64_t lddv, float scale,
-                      float eps_mask, float eps_qk, int causal, int window, int q_begin, const int* row_lo, const int* row_hi, hipStream_t st) {
+static int attn_dkv_t(const AttnCall& c) {
     constexpr int SZ = sizeof(T), CT = 128 / SZ;
-    if ((ldt % CT) == 0 && ((size_t)d * SZ >= 64) && d <= 128 && S >= 1) {
-        ATT_DISPATCH_D(T, d, {
+    if (attn_8wave<T>(c) && c.S >= 1) {
+        ATT_DISPATCH_D(T, c.d, {
             if constexpr (DD <= 128) {
                 const size_t lds = 2 * (4 * (size_t)128 * DD + 512);
-                dim3 grid(xcd_group_grid(B * Hq, (S + 127) / 128));
-                auto launch = [&](auto kern) {
-                    set_lds(kern, lds);
-                    hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, (const T*)q, (const T*)k, (const T*)v, (const T*)qt,
-                                       (const T*)gho, (const T*)ghot, lse, D, (T*)dk, (T*)dv, S, Hq, Hkv, ldq, ldk, ldv, ldt,
-                                       ldg, lddk, lddv, scale, eps_mask, eps_qk, causal, window, B, q_begin, row_lo, row_hi);
-                };
-                if (eps_mask != 0.f || eps_qk != 0.f) launch(attn_bwd_dkv_v2_kernel<T, DD, true>);
-                else launch(attn_bwd_dkv_v2_kernel<T, DD, false>);
+                dim3 grid(xcd_group_grid(c.B * c.Hq, (c.S + 127) / 128));
+                lrp_with_bool(c.eps_mask != 0.f || c.eps_qk != 0.f, [&](auto ex) {
+                    launch_dkv<attn_bwd_dkv_v2_kernel<T, DD, decltype(ex)::value>, T>(c, grid, 512, lds, c.B);
+                });
             }
         })
         return lrp_check_launch();
     }
-    ATT_DISPATCH_D(T, d, {
-        const size_t lds = 2 * (size_t)CT * DD * SZ + 2 * (size_t)DD * 128;
-        auto kern = attn_bwd_dkv_kernel<T, DD>;
-        set_lds(kern, lds);
-        dim3 grid((S + 63) / 64, Hq, B);
-        hipLaunchKernelGGL(kern, grid, dim3(ANT), lds, st, (const T*)q, (const T*)k, (const T*)v, (const T*)qt, (const T*)gho,
-                           (const T*)ghot, lse, D, (T*)dk, (T*)dv, S, Hq, Hkv, ldq, ldk, ldv, ldt, ldg, lddk, lddv, scale,
-                           eps_mask, eps_qk, causal, window, q_begin, row_lo, row_hi);
+    ATT_DISPATCH_D(T, c.d, {
+        launch_dkv<attn_bwd_dkv_kernel<T, DD>, T>(c, dim3((c.S + 63) / 64, c.Hq, c.B), ANT, 2 * (size_t)CT * DD * SZ + 2 * (size_t)DD * 128);
     })
     return lrp_check_launch();
 }
@@ -1318,15 +1314,20 @@ extern "C" int lrp_attn_bwd_dkv(const void* q, const void* k, const void* v, con
     const int epc = dtype == LRP_F32 ? 4 : 8;
     if (!al16(q) || !al16(k) || !al16(v) || !al16(Gho) || !al16(dk_h) || !al16(dv_h) ||
         (ldq % epc) || (ldk % epc) || (ldv % epc) || (ldgho % epc) || (lddk % 4) || (lddv % 4)) return LRP_EALIGN;
-    hipStream_t st = (hipStream_t)stream;
-    if (use_attn32(dtype, d) && d == 256)
-        return lrp_attn32_dkv_d256(q, k, v, Gho, lse, D, dk_h, dv_h, B, S, Hq, Hkv, ldq, ldk, ldv, ldgho, lddk, lddv, scale, eps_mask, eps_qk, causal, window, q_begin, row_lo, row_hi, st);
-    if (use_attn32(dtype, d))
-        return lrp_attn32_dkv(q, k, v, Gho, lse, D, dk_h, dv_h, B, S, Hq, Hkv, d, ldq, ldk, ldv, ldgho, lddk, lddv, scale, eps_mask, eps_qk, causal, window, q_begin, row_lo, row_hi, st);
-    if (!q_t || !Gho_t) return LRP_EINVAL;
-    if (!al16(q_t) || !al16(Gho_t) || (ldt % epc) || ldt < S) return LRP_EALIGN;
-    if (dtype == LRP_F32) return attn_dkv_t<float>(q, k, v, q_t, Gho, Gho_t, lse, D, dk_h, dv_h, B, S, Hq, Hkv, d, ldq, ldk, ldv, ldt, ldgho, lddk, lddv, scale, eps_mask, eps_qk, causal, window, q_begin, row_lo, row_hi, st);
-    return attn_dkv_t<bf16_t>(q, k, v, q_t, Gho, Gho_t, lse, D, dk_h, dv_h, B, S, Hq, Hkv, d, ldq, ldk, ldv, ldt, ldgho, lddk, lddv, scale, eps_mask, eps_qk, causal, window, q_begin, row_lo, row_hi, st);
+    const bool a32 = use_attn32(dtype, d);
+    if (!a32) {
+        if (!q_t || !Gho_t) return LRP_EINVAL;
+        if (!al16(q_t) || !al16(Gho_t) || (ldt % epc) || ldt < S) return LRP_EALIGN;
+    }
+    AttnCall c = {};
+    c.q = q; c.k = k; c.v = v; c.gho = Gho; c.lse = lse; c.D = D;
+    c.B = B; c.S = S; c.Hq = Hq; c.Hkv = Hkv; c.d = d;
+    c.ldq = ldq; c.ldk = ldk; c.ldv = ldv; c.ldg = ldgho; c.ldt = ldt;
+    c.scale = scale; c.eps_mask = eps_mask; c.eps_qk = eps_qk; c.causal = causal; c.window = window; c.q_begin = q_begin;
+    c.row_lo = row_lo; c.row_hi = row_hi; c.st = (hipStream_t)stream;
+    c.dk = dk_h; c.dv = dv_h; c.lddk = lddk; c.lddv = lddv; c.q_t = q_t; c.gho_t = Gho_t;
+    if (a32) return lrp_attn32_dkv(c);
+    return dtype == LRP_F32 ? attn_dkv_t<float>(c) : attn_dkv_t<bf16_t>(c);
 }
 
 extern "C" int lrp_transpose_heads(const void* x, void* xt, int B, int S, int H, int d, int64_t ldx, int64_t ldt,

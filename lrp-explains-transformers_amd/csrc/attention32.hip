@@ -45,7 +45,6 @@ LRP_DEVICE bool xcd_group_decode(int L, int ngroups, int per_group, int& group, 
     group = xcd + 8 * (i / per_group);
     return group < ngroups;
 }
-inline int xcd_group_grid(int ngroups, int per_group) { return ((ngroups + 7) / 8) * 8 * per_group; }
 // the same grid walked ITEM-major within a XCD: all groups' item 0 first, then item 1, ... -- for the dK / dV kernel, whose items (key blocks of a
 // head) differ 8 : 1 in work (causal) and whose 128-KiB workgroups run ONE per CU: with the group-major order the last head's heaviest key
 // block starts when the other CUs are already draining (list-scheduling simulation of 16 heads x 8 key blocks on a XCD's 32 CUs: makespan 88 tile
@@ -1593,77 +1592,33 @@ __global__ __launch_bounds__(NW2 * 64, 1) void dkv256_kernel(
 }  // namespace d256
 
 constexpr size_t A32_LDS_MAX = 160 * 1024;       // gfx950: 160 KiB per workgroup (the dK / dV kernels' interval table grows with S: S <= ~60000 with row intervals)
-template <typename K> void set_lds(K kern, size_t bytes) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+
+// ---- one launch expression per kernel family; nw = waves per workgroup, 32 row-side rows each -------------------------------------------
+template <auto Kern>
+static void launch_fwd(const AttnCall& c, int nw, size_t lds) {
+    dim3 grid(xcd_group_grid(c.B * c.Hkv, (c.Hq / c.Hkv) * ((c.S + nw * 32 - 1) / (nw * 32))));
+    lrp_launch_lds<Kern>(grid, dim3(nw * 64), lds, lds, c.st, (const bf16_t*)c.q, (const bf16_t*)c.k, (const bf16_t*)c.v, (bf16_t*)c.o, c.lse_out,
+                         c.S, c.Hq, c.Hkv, c.ldq, c.ldk, c.ldv, c.ldo, c.scale, c.causal, c.window, c.B, c.q_begin, c.row_lo, c.row_hi);
+}
+// tail: what dq_kernel takes after dq256_kernel's list (the D-forming form's operands)
+template <auto Kern, typename... Tail>
+static void launch_dq(const AttnCall& c, int nw, size_t lds, Tail... tail) {
+    dim3 grid(xcd_group_grid(c.B * c.Hkv, (c.Hq / c.Hkv) * ((c.S + nw * 32 - 1) / (nw * 32))));
+    lrp_launch_lds<Kern>(grid, dim3(nw * 64), lds, lds, c.st, (const bf16_t*)c.q, (const bf16_t*)c.k, (const bf16_t*)c.v, (const bf16_t*)c.gho,
+                         c.lse, c.D, (bf16_t*)c.dq, c.S, c.Hq, c.Hkv, c.ldq, c.ldk, c.ldv, c.ldg, c.lddq, c.scale, c.eps_mask, c.eps_qk,
+                         c.causal, c.window, c.B, c.q_begin, c.row_lo, c.row_hi, tail...);
+}
+template <auto Kern>
+static void launch_dkv(const AttnCall& c, int nw, size_t lds) {
+    dim3 grid(xcd_group_grid(c.B * c.Hq, (c.S + nw * 32 - 1) / (nw * 32)));
+    lrp_launch_lds<Kern>(grid, dim3(nw * 64), lds, A32_LDS_MAX, c.st, (const bf16_t*)c.q, (const bf16_t*)c.k, (const bf16_t*)c.v,
+                         (const bf16_t*)c.gho, c.lse, c.D, (bf16_t*)c.dk, (bf16_t*)c.dv, c.S, c.Hq, c.Hkv, c.ldq, c.ldk, c.ldv, c.ldg, c.lddk,
+                         c.lddv, c.scale, c.eps_mask, c.eps_qk, c.causal, c.window, c.B, c.q_begin, c.row_lo, c.row_hi);
 }
 
 }  // namespace attn32
 
-// ---- entry points used by the dispatchers of attention.hip (bf16, d == 256) ------------------------------------------
-int lrp_attn32_fwd_d256(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq, int Hkv, int64_t ldq,
-                        int64_t ldk, int64_t ldv, int64_t ldo, float scale, int causal, int window, int q_begin, const int* row_lo,
-                        const int* row_hi, hipStream_t st) {
-    using namespace attn32;
-    using namespace attn32::d256;
-    const size_t lds = 2 * (2 * (size_t)TILE2);
-    auto kern = fwd256_kernel;
-    LRP_SET_MAX_LDS(kern, lds);
-    dim3 grid(xcd_group_grid(B * Hkv, (Hq / Hkv) * ((S + NW2 * 32 - 1) / (NW2 * 32))));
-    hipLaunchKernelGGL(kern, grid, dim3(NW2 * 64), lds, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, S, Hq,
-                       Hkv, ldq, ldk, ldv, ldo, scale, causal, window, B, q_begin, row_lo, row_hi);
-    return lrp_check_launch();
-}
-
-int lrp_attn32_dq_d256(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dq, int B,
-                       int S, int Hq, int Hkv, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddq, float scale,
-                       float eps_mask, float eps_qk, int causal, int window, int q_begin, const int* row_lo, const int* row_hi,
-                       hipStream_t st) {
-    using namespace attn32;
-    using namespace attn32::d256;
-    const size_t lds = 2 * (2 * (size_t)TILE2);
-    dim3 grid(xcd_group_grid(B * Hkv, (Hq / Hkv) * ((S + NW2 * 32 - 1) / (NW2 * 32))));
-    if (eps_mask != 0.f || eps_qk != 0.f) {
-        auto kern = dq256_kernel<true>;
-        LRP_SET_MAX_LDS(kern, lds);
-        hipLaunchKernelGGL(kern, grid, dim3(NW2 * 64), lds, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)gho,
-                           lse, D_, (bf16_t*)dq, S, Hq, Hkv, ldq, ldk, ldv, ldg, lddq, scale, eps_mask, eps_qk, causal, window, B,
-                           q_begin, row_lo, row_hi);
-    } else {
-        auto kern = dq256_kernel<false>;
-        LRP_SET_MAX_LDS(kern, lds);
-        hipLaunchKernelGGL(kern, grid, dim3(NW2 * 64), lds, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)gho,
-                           lse, D_, (bf16_t*)dq, S, Hq, Hkv, ldq, ldk, ldv, ldg, lddq, scale, eps_mask, eps_qk, causal, window, B,
-                           q_begin, row_lo, row_hi);
-    }
-    return lrp_check_launch();
-}
-
-int lrp_attn32_dkv_d256(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dk,
-                        void* dv, int B, int S, int Hq, int Hkv, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddk,
-                        int64_t lddv, float scale, float eps_mask, float eps_qk, int causal, int window, int q_begin,
-                        const int* row_lo, const int* row_hi, hipStream_t st) {
-    using namespace attn32;
-    using namespace attn32::d256;
-    const size_t lds = 2 * (2 * (size_t)TILE2 + 512) + (size_t)NW2 * 32 * KP2 + (row_lo ? (size_t)((S + 31) / 32) * 16 : 0);   // + the interval table
-    if (lds > A32_LDS_MAX) return LRP_ESHAPE;
-    dim3 grid(xcd_group_grid(B * Hq, (S + NW2 * 32 - 1) / (NW2 * 32)));
-    if (eps_mask != 0.f || eps_qk != 0.f) {
-        auto kern = dkv256_kernel<true>;
-        LRP_SET_MAX_LDS(kern, A32_LDS_MAX);
-        hipLaunchKernelGGL(kern, grid, dim3(NW2 * 64), lds, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)gho,
-                           lse, D_, (bf16_t*)dk, (bf16_t*)dv, S, Hq, Hkv, ldq, ldk, ldv, ldg, lddk, lddv, scale, eps_mask, eps_qk,
-                           causal, window, B, q_begin, row_lo, row_hi);
-    } else {
-        auto kern = dkv256_kernel<false>;
-        LRP_SET_MAX_LDS(kern, A32_LDS_MAX);
-        hipLaunchKernelGGL(kern, grid, dim3(NW2 * 64), lds, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)gho,
-                           lse, D_, (bf16_t*)dk, (bf16_t*)dv, S, Hq, Hkv, ldq, ldk, ldv, ldg, lddk, lddv, scale, eps_mask, eps_qk,
-                           causal, window, B, q_begin, row_lo, row_hi);
-    }
-    return lrp_check_launch();
-}
-
-// ---- entry points used by the dispatchers of attention.hip (bf16, d in {64, 96, 128}) ----------------------------------
+// ---- entry points used by the dispatchers of attention.hip (bf16, d in {64, 96, 128, 256}) -----------------------------------------------
 #define A32_FOR_DH(d, ...)                                     \
     switch (d) {                                               \
         case 64: { constexpr int DH = 64; __VA_ARGS__ } break; \
@@ -1672,65 +1627,37 @@ int lrp_attn32_dkv_d256(const void* q, const void* k, const void* v, const void*
         default: return LRP_ESHAPE;                            \
     }
 
-int lrp_attn32_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq, int Hkv, int d, int64_t ldq,
-                   int64_t ldk, int64_t ldv, int64_t ldo, float scale, int causal, int window, int q_begin, const int* row_lo,
-                   const int* row_hi, hipStream_t st) {
+int lrp_attn32_fwd(const AttnCall& c) {
     using namespace attn32;
-    const size_t lds = 2 * (2 * (size_t)TILE);
-    dim3 grid(xcd_group_grid(B * Hkv, (Hq / Hkv) * ((S + NWQ * 32 - 1) / (NWQ * 32))));
-    A32_FOR_DH(d, {
-        auto kern = fwd_kernel<DH>;
-        LRP_SET_MAX_LDS(kern, lds);
-        hipLaunchKernelGGL(kern, grid, dim3(NWQ * 64), lds, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse, S, Hq,
-                           Hkv, ldq, ldk, ldv, ldo, scale, causal, window, B, q_begin, row_lo, row_hi);
+    if (c.d == 256) launch_fwd<d256::fwd256_kernel>(c, d256::NW2, 2 * (2 * (size_t)d256::TILE2));
+    else A32_FOR_DH(c.d, { launch_fwd<fwd_kernel<DH>>(c, NWQ, 2 * (2 * (size_t)TILE)); })
+    return lrp_check_launch();
+}
+
+int lrp_attn32_dq(const AttnCall& c) {
+    using namespace attn32;
+    const bool expl = c.eps_mask != 0.f || c.eps_qk != 0.f;
+    if (c.d == 256)
+        lrp_with_bool(expl, [&](auto ex) { launch_dq<d256::dq256_kernel<decltype(ex)::value>>(c, d256::NW2, 2 * (2 * (size_t)d256::TILE2)); });
+    else A32_FOR_DH(c.d, {
+        lrp_with_bool(expl, [&](auto ex) {
+            launch_dq<dq_kernel<decltype(ex)::value, DH>>(c, NWQ, 2 * (2 * (size_t)TILE), (const bf16_t*)c.ofw, c.ldo, c.Dout, c.cos_t, c.sin_t);
+        });
     })
     return lrp_check_launch();
 }
 
-// o != NULL: D is COMPUTED from (gho, o) and written to Dout (then D_ is not read)
-int lrp_attn32_dq(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dq, int B,
-                  int S, int Hq, int Hkv, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddq, float scale,
-                  float eps_mask, float eps_qk, int causal, int window, int q_begin, const int* row_lo, const int* row_hi,
-                  hipStream_t st, const void* o, int64_t ldo, float* Dout, const float* cos_t, const float* sin_t) {
+int lrp_attn32_dkv(const AttnCall& c) {
     using namespace attn32;
-    const size_t lds = 2 * (2 * (size_t)TILE);
-    dim3 grid(xcd_group_grid(B * Hkv, (Hq / Hkv) * ((S + NWQ * 32 - 1) / (NWQ * 32))));
-    const bool expl = eps_mask != 0.f || eps_qk != 0.f;
-#define A32_LAUNCH_DQ(EX)                                                                                                                  \
-    {                                                                                                                                       \
-        auto kern = dq_kernel<EX, DH>;                                                                                                      \
-        LRP_SET_MAX_LDS(kern, lds);                                                                                                         \
-        hipLaunchKernelGGL(kern, grid, dim3(NWQ * 64), lds, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)gho, \
-                           lse, D_, (bf16_t*)dq, S, Hq, Hkv, ldq, ldk, ldv, ldg, lddq, scale, eps_mask, eps_qk, causal, window, B,         \
-                           q_begin, row_lo, row_hi, (const bf16_t*)o, ldo, Dout, cos_t, sin_t);                                            \
-    }
-    A32_FOR_DH(d, { if (expl) A32_LAUNCH_DQ(true) else A32_LAUNCH_DQ(false) })
-#undef A32_LAUNCH_DQ
-    return lrp_check_launch();
-}
-
-int lrp_attn32_dkv(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dk,
-                   void* dv, int B, int S, int Hq, int Hkv, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddk,
-                   int64_t lddv, float scale, float eps_mask, float eps_qk, int causal, int window, int q_begin,
-                   const int* row_lo, const int* row_hi, hipStream_t st) {
-    using namespace attn32;
-    const size_t lds = 2 * (2 * (size_t)TILE + 512) + (size_t)NW * 32 * KP + (row_lo ? (size_t)((S + 31) / 32) * 16 : 0);   // + the interval table
+    const bool wide = c.d == 256, expl = c.eps_mask != 0.f || c.eps_qk != 0.f, iv = c.row_lo != nullptr;
+    const size_t lds = (wide ? 2 * (2 * (size_t)d256::TILE2 + 512) + (size_t)d256::NW2 * 32 * d256::KP2 : 2 * (2 * (size_t)TILE + 512) + (size_t)NW * 32 * KP) +
+                       (iv ? (size_t)((c.S + 31) / 32) * 16 : 0);   // + the interval table
     if (lds > A32_LDS_MAX) return LRP_ESHAPE;
-    dim3 grid(xcd_group_grid(B * Hq, (S + 255) / 256));
-    const bool expl = eps_mask != 0.f || eps_qk != 0.f;
-#define A32_LAUNCH_DKV(EX, IVF)                                                                                                        \
-    {                                                                                                                                   \
-        auto kern = dkv_kernel<EX, DH, IVF>;                                                                                            \
-        LRP_SET_MAX_LDS(kern, A32_LDS_MAX);                                                                                             \
-        hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)gho,   \
-                           lse, D_, (bf16_t*)dk, (bf16_t*)dv, S, Hq, Hkv, ldq, ldk, ldv, ldg, lddk, lddv, scale, eps_mask, eps_qk,     \
-                           causal, window, B, q_begin, row_lo, row_hi);                                                                \
-    }
-    const bool iv = row_lo != nullptr;
-    A32_FOR_DH(d, {
-        if (expl) { if (iv) A32_LAUNCH_DKV(true, true) else A32_LAUNCH_DKV(true, false) }
-        else { if (iv) A32_LAUNCH_DKV(false, true) else A32_LAUNCH_DKV(false, false) }
+    if (wide) lrp_with_bool(expl, [&](auto ex) { launch_dkv<d256::dkv256_kernel<decltype(ex)::value>>(c, d256::NW2, lds); });
+    else A32_FOR_DH(c.d, {
+        lrp_with_bool(expl, [&](auto ex) {
+            lrp_with_bool(iv, [&](auto ivf) { launch_dkv<dkv_kernel<decltype(ex)::value, DH, decltype(ivf)::value>>(c, NW, lds); });
+        });
     })
-#undef A32_LAUNCH_DKV
     return lrp_check_launch();
 }

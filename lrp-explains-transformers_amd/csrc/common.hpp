@@ -35,6 +35,20 @@ static inline void lrp_set_max_lds_once(std::atomic<uint64_t>& done, const void*
         lrp_set_max_lds_once(lds_done_, reinterpret_cast<const void*>(kern), (bytes));     \
     } while (0)
 
+// launch Kern with up to max_lds bytes of dynamic LDS opted in.  The template parameter is the kernel ITSELF, not its type: kernels that differ
+// only in their template flags share one signature, and the once-flag of LRP_SET_MAX_LDS below must be one per kernel
+template <auto Kern, typename... Args>
+static inline void lrp_launch_lds(dim3 grid, dim3 block, size_t lds, size_t max_lds, hipStream_t st, Args... args) {
+    LRP_SET_MAX_LDS(Kern, max_lds);
+    hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+}
+// a runtime flag as a template argument: f(std::true_type{}) or f(std::false_type{})
+#include <type_traits>
+template <typename F> static inline void lrp_with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
 // compute units of the current device (one query per device and process)
 static inline int lrp_num_cus() {
     static std::atomic<int> cached[64];
@@ -252,31 +266,35 @@ LRP_DEVICE int xcd_remap(int bid, int nwg) {
     return base + loc;
 }
 
-// ---- entry points of attention32.hip, called by the dispatchers of attention.hip: bf16 on the 32x32x16 MFMA kernels, no head-transposed
-// operands; d in {64, 96, 128}, and the _d256 forms.  lrp_attn32_dq with o != NULL computes D from (gho, o) and writes it to Dout.
-int lrp_attn32_fwd(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq, int Hkv, int d, int64_t ldq,
-                   int64_t ldk, int64_t ldv, int64_t ldo, float scale, int causal, int window, int q_begin, const int* row_lo,
-                   const int* row_hi, hipStream_t st);
-int lrp_attn32_dq(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dq, int B,
-                  int S, int Hq, int Hkv, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddq, float scale,
-                  float eps_mask, float eps_qk, int causal, int window, int q_begin, const int* row_lo, const int* row_hi,
-                  hipStream_t st, const void* o = nullptr, int64_t ldo = 0, float* Dout = nullptr, const float* cos_t = nullptr,
-                  const float* sin_t = nullptr);
-int lrp_attn32_dkv(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dk,
-                   void* dv, int B, int S, int Hq, int Hkv, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddk,
-                   int64_t lddv, float scale, float eps_mask, float eps_qk, int causal, int window, int q_begin,
-                   const int* row_lo, const int* row_hi, hipStream_t st);
-int lrp_attn32_fwd_d256(const void* q, const void* k, const void* v, void* o, float* lse, int B, int S, int Hq, int Hkv, int64_t ldq,
-                        int64_t ldk, int64_t ldv, int64_t ldo, float scale, int causal, int window, int q_begin, const int* row_lo,
-                        const int* row_hi, hipStream_t st);
-int lrp_attn32_dq_d256(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dq, int B,
-                       int S, int Hq, int Hkv, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddq, float scale,
-                       float eps_mask, float eps_qk, int causal, int window, int q_begin, const int* row_lo, const int* row_hi,
-                       hipStream_t st);
-int lrp_attn32_dkv_d256(const void* q, const void* k, const void* v, const void* gho, const float* lse, const float* D_, void* dk,
-                        void* dv, int B, int S, int Hq, int Hkv, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, int64_t lddk,
-                        int64_t lddv, float scale, float eps_mask, float eps_qk, int causal, int window, int q_begin,
-                        const int* row_lo, const int* row_hi, hipStream_t st);
+// ---- one attention call (forward, dQ or dK / dV) as everything below the extern "C" entries of attention.hip sees it.  An entry fills it
+// once, after its checks; a field an operation does not use stays null / zero.
+struct AttnCall {
+    const void *q, *k, *v, *gho;         // token-major operands [B * S, H * d] (gho: the backward kernels' incoming relevance / gradient of o)
+    const float* lse;                    // [B, Hq, S] softmax statistic (read by the backward kernels) ...
+    const float* D;                      // ... and D_i = sum_d gho_i o_i
+    int B, S, Hq, Hkv, d;
+    int64_t ldq, ldk, ldv, ldg, ldt;     // row pitches in elements; ldt: the head-transposed operands' ([B, H, d, ldt], attention.hip's kernels only)
+    float scale, eps_mask, eps_qk;
+    int causal, window, q_begin;
+    const int *row_lo, *row_hi;          // optional per-query-row key interval [lo, hi)
+    hipStream_t st;
+    // forward
+    void* o;  float* lse_out;  int64_t ldo;  const void* v_t;
+    // dQ; with ofw != NULL D is COMPUTED from (gho, ofw) and written to Dout (then D is not read), and cos_t / sin_t undo RoPE on dq
+    void* dq;  int64_t lddq;  const void* k_t;
+    const void* ofw;  float* Dout;  const float *cos_t, *sin_t;      // (ofw's pitch is ldo)
+    // dK / dV (per query head)
+    void *dk, *dv;  int64_t lddk, lddv;  const void *q_t, *gho_t;
+};
+
+// entry points of attention32.hip, called by the dispatchers of attention.hip: bf16 on the 32x32x16 MFMA kernels, no head-transposed operands,
+// d in {64, 96, 128, 256} (which kernel serves which d is decided there)
+int lrp_attn32_fwd(const AttnCall& c);
+int lrp_attn32_dq(const AttnCall& c);
+int lrp_attn32_dkv(const AttnCall& c);
+
+// 1-D grid of the XCD-aware decodes of the attention kernels (xcd_group_decode): ngroups sharing groups padded to whole rounds of 8 XCDs
+static inline int xcd_group_grid(int ngroups, int per_group) { return ((ngroups + 7) / 8) * 8 * per_group; }
 
 // ---- the ping-pong GEMM of gemm_pp.hip as the dispatchers of gemm.hip see it.
 // What an epilogue form reads and writes beside A, B, C and bias (EPI 1 .. 6 and the row scale; the forms are described above gemm_pp_kernel)

@@ -168,13 +168,19 @@ def _check(name, x, ref, bar, norm=None, rows=None):
         assert bool((eb <= 4 * bar * rb).all()), (name, worst)
 
 
-def _attn_pipeline(ops, views, B, S, Hq, Hkv, d, dtype, causal, window, Go, q_begin=0, row_iv=None, fwd_from=None):
+def _attn_pipeline(ops, views, B, S, Hq, Hkv, d, dtype, causal, window, Go, q_begin=0, row_iv=None, fwd_from=None, t_pitch=None):
     """forward, prep, dQ, dK / dV (+ the D-forming dQ kernel where it serves the call) on strided operands with NaN-filled, over-wide outputs;
-    fwd_from = (o, lse): the backward is fed these instead of this call's forward"""
+    fwd_from = (o, lse): the backward is fed these instead of this call's forward; t_pitch: row pitch of the head-transposed operands
+    (default: ops.transpose_heads' own, S padded to 64)"""
     q, k, v = views
     scale = d ** -0.5
     R = {}
-    v_t = ops.transpose_heads(v, B, S, Hkv, d)
+
+    def tr(x, H):
+        out = None if t_pitch is None else torch.zeros(B, H, d, t_pitch, dtype=dtype, device="cuda")
+        return ops.transpose_heads(x, B, S, H, d, out=out)
+
+    v_t = tr(v, Hkv)
     R["o"], R["o_spare"] = _nan_buf(B * S, Hq * d, 64, dtype)
     R["lse"] = torch.full((B, Hq, S), float("nan"), device="cuda")
     ops.attn_fwd(q, k, v, v_t, R["o"], R["lse"], B, S, Hq, Hkv, d, scale, causal, window, q_begin=q_begin, row_iv=row_iv)
@@ -183,7 +189,7 @@ def _attn_pipeline(ops, views, B, S, Hq, Hkv, d, dtype, causal, window, Go, q_be
     o, lse = fwd_from if fwd_from is not None else (R["o"], R["lse"])
     R["Gho"], R["D"] = torch.full_like(Go, float("nan")), torch.full((B, Hq, S), float("nan"), device="cuda")
     ops.attn_bwd_prep(Go, o, R["Gho"], R["D"], B, S, Hq, d, 0.0, 0.5)
-    k_t, q_t, Gho_t = ops.transpose_heads(k, B, S, Hkv, d), ops.transpose_heads(q, B, S, Hq, d), ops.transpose_heads(R["Gho"], B, S, Hq, d)
+    k_t, q_t, Gho_t = tr(k, Hkv), tr(q, Hq), tr(R["Gho"], Hq)
     R["dq"], R["dq_spare"] = _nan_buf(B * S, Hq * d, 64, dtype)
     ops.attn_bwd_dq(q, k, v, k_t, R["Gho"], lse, R["D"], R["dq"], B, S, Hq, Hkv, d, scale, 0.0, 0.0, causal, window, q_begin=q_begin, row_iv=row_iv)
     R["dk_h"], R["dk_spare"] = _nan_buf(B * S, Hq * d, 8, dtype)
@@ -266,6 +272,31 @@ def test_attention_block_edges(ops, B, S, Hq, Hkv, d, causal, window, dtype):
         R0 = _attn_pipeline(ops, views, B, S, Hq, Hkv, d, dtype, causal, 0, Go)
         for key in ("o", "lse", "dq", "dk_h", "dv_h") + (("dq2", "D2") if "dq2" in R else ()):
             assert torch.equal(R[key], R0[key]), f"{key}: window >= S differs from no window"
+
+
+@pytest.mark.parametrize("S,d,t_pitch,dtype", [(100, 64, 100, torch.float32), (100, 32, 104, torch.bfloat16)])
+def test_attention_narrow_transposed_pitch(ops, S, d, t_pitch, dtype):
+    """head-transposed operands whose pitch is S rounded up to 16 bytes only -- off the 128-byte column-tile grid, which include/lrp_hip.h
+    allows: the 8-wave kernels read whole column tiles, so these calls run on the 4-wave kernels (ops.transpose_heads always pads to 64, which
+    leaves them fp32 d = 256 alone from Python).  fwd o / lse, dQ, dK, dV against the fp64 reference with test_attention's bars."""
+    B, Hq, Hkv, causal = 1, 4, 2, True
+    size = torch.empty(0, dtype=dtype).element_size()
+    assert t_pitch >= S and (t_pitch * size) % 16 == 0 and (t_pitch * size) % 128 != 0 and (t_pitch - S) * size < 16
+    tol = 3e-5 if dtype == torch.float32 else 3e-2
+    scale = d ** -0.5
+    views, (q4, k4, v4) = _qkv_slices(B, S, Hq, Hkv, d, dtype)
+    Go = rnd(B * S, Hq * d, dtype=dtype, seed=4)
+    R = _attn_pipeline(ops, views, B, S, Hq, Hkv, d, dtype, causal, 0, Go, t_pitch=t_pitch)
+    s, p, o_ref, vis, rep = _attn_ref(f64(q4), f64(k4), f64(v4), scale, causal, 0)
+    lse_ref = torch.logsumexp((s * scale).masked_fill(~vis, float("-inf")), -1)
+    print(f"[narrow transposed pitch {t_pitch}: S {S} d {d} {dtype}]")
+    _spares_untouched(R)
+    _check("o", R["o"], o_ref, tol)
+    assert torch.isfinite(R["lse"]).all() and nmax(R["lse"], lse_ref) < (1e-5 if dtype == torch.float32 else 1e-2)
+    dQ, dK, dV, _ = _ref_bwd(f64(q4), f64(k4), f64(v4), _h4(R["Gho"], B, S, Hq, d), p, vis, scale)
+    _check("dq", R["dq"], dQ, 3 * tol)
+    _check("dk", R["dk"], dK, 3 * tol)
+    _check("dv", R["dv"], dV, 3 * tol)
 
 
 # ------------------------------------------------------------------------------------------------- C. q_begin

@@ -1000,7 +1000,9 @@ def _tm(x):      # [B,H,S,d] -> token-major [B*S, H*d]
     (1, 130, 2, 2, 64, False, 0), (1, 200, 2, 1, 64, True, 48), (1, 300, 8, 2, 128, True, 0),
     (1, 150, 2, 1, 256, True, 0), (1, 150, 2, 1, 256, True, 64), (1, 300, 6, 2, 96, True, 0), (2, 260, 3, 3, 96, False, 0), (1, 400, 2, 1, 96, True, 90),
     (2, 520, 8, 2, 64, True, 0), (1, 333, 4, 4, 64, False, 0),
-    (1, 500, 4, 2, 128, True, 100), (1, 260, 4, 2, 128, False, 0), (2, 700, 8, 2, 128, True, 0), (1, 257, 4, 4, 128, True, 0)])
+    (1, 500, 4, 2, 128, True, 100), (1, 260, 4, 2, 128, False, 0), (2, 700, 8, 2, 128, True, 0), (1, 257, 4, 4, 128, True, 0),
+    # B Hq ceil(S / 256) >= 512: the 8-wave forward's 256-query workgroups (fp32, and bf16 at d = 32); S = 257: one row in the second block
+    (4, 130, 128, 32, 32, True, 0), (8, 257, 32, 8, 16, True, 0)])
 @pytest.mark.parametrize("mode", ["efficient", "explicit"])
 def test_attention(ops, dtype, B, S, Hq, Hkv, d, causal, window, mode):
     if dtype == torch.bfloat16 and d < 32:
@@ -1122,11 +1124,14 @@ def _intervals(kind, B, S):
 
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("kind", ["left_pad", "right_pad", "packed", "image_block", "blocks_full", "random"])
-@pytest.mark.parametrize("B,S,Hq,Hkv,d,window", [(2, 150, 4, 2, 64, 0), (2, 200, 2, 1, 128, 0), (1, 140, 2, 1, 256, 0), (2, 160, 2, 2, 64, 40), (2, 210, 2, 1, 96, 0),
-                                                 (2, 330, 4, 2, 128, 0), (2, 300, 2, 1, 128, 70)])
-def test_attention_row_intervals(ops, dtype, kind, B, S, Hq, Hkv, d, window):
+@pytest.mark.parametrize("B,S,Hq,Hkv,d,window,mode", [pytest.param(*c, id="-".join(str(x) for x in c[:6]) + ("-explicit" if c[6] == "explicit" else "")) for c in [
+    (2, 150, 4, 2, 64, 0, "efficient"), (2, 200, 2, 1, 128, 0, "efficient"), (1, 140, 2, 1, 256, 0, "efficient"), (2, 160, 2, 2, 64, 40, "efficient"),
+    (2, 210, 2, 1, 96, 0, "efficient"), (2, 330, 4, 2, 128, 0, "efficient"), (2, 300, 2, 1, 128, 70, "efficient"),
+    (2, 200, 2, 1, 128, 0, "explicit")]])          # explicit stabilisers WITH intervals: the (EXPL, IV) form of the bf16 dK / dV kernel
+def test_attention_row_intervals(ops, dtype, kind, B, S, Hq, Hkv, d, window, mode):
     """per-row key intervals (padding / packed sequences / bidirectional blocks) against an fp64 eager attention with
     the same boolean mask; rows with an empty interval must come out as exact zeros and stay NaN-free"""
+    E = dict(pv=1e-6, mask=1e-8, qk=1e-8) if mode == "explicit" else dict(pv=0.0, mask=0.0, qk=0.0)      # test_attention's
     if kind in ("image_block", "blocks_full", "random") and window:
         pytest.skip("bidirectional blocks are used with global layers")
     if dtype == torch.float32 and d == 96:
@@ -1161,19 +1166,20 @@ def test_attention_row_intervals(ops, dtype, kind, B, S, Hq, Hkv, d, window):
 
     Go = rnd(B * S, Hq * d, dtype=dtype, seed=4)
     Gho, D = torch.empty_like(Go), torch.empty(B, Hq, S, device="cuda")
-    ops.attn_bwd_prep(Go, o, Gho, D, B, S, Hq, d, 0.0, 0.5)
+    ops.attn_bwd_prep(Go, o, Gho, D, B, S, Hq, d, E["pv"], 0.5)
     Gh = f64(Gho).reshape(B, S, Hq, d).permute(0, 2, 1, 3)
     dP = Gh @ vx.transpose(-1, -2)
     dS3 = pr * (dP - (dP * pr).sum(-1, keepdim=True))
-    Ghs = torch.where(vis, dS3 * scale * 0.5, torch.zeros_like(s))
+    f = 0.5 if mode == "efficient" else (s * scale) / (s * scale + E["mask"]) * s / (2 * s + E["qk"])
+    Ghs = torch.where(vis, dS3 * scale * f, torch.zeros_like(s))
     dQ = Ghs @ kx
     dK = (Ghs.transpose(-1, -2) @ qd).reshape(B, Hkv, rep, S, d).sum(2)
     dV = (pr.transpose(-1, -2) @ Gh).reshape(B, Hkv, rep, S, d).sum(2)
     k_t, q_t, Gho_t = ops.transpose_heads(kt, B, S, Hkv, d), ops.transpose_heads(qt, B, S, Hq, d), ops.transpose_heads(Gho, B, S, Hq, d)
     dq = torch.empty_like(qt)
-    ops.attn_bwd_dq(qt, kt, vt, k_t, Gho, lse, D, dq, B, S, Hq, Hkv, d, scale, 0.0, 0.0, causal, window, row_iv=row_iv)
+    ops.attn_bwd_dq(qt, kt, vt, k_t, Gho, lse, D, dq, B, S, Hq, Hkv, d, scale, E["mask"], E["qk"], causal, window, row_iv=row_iv)
     dk_h, dv_h = torch.empty_like(qt), torch.empty_like(qt)
-    ops.attn_bwd_dkv(qt, kt, vt, q_t, Gho, Gho_t, lse, D, dk_h, dv_h, B, S, Hq, Hkv, d, scale, 0.0, 0.0, causal, window, row_iv=row_iv)
+    ops.attn_bwd_dkv(qt, kt, vt, q_t, Gho, Gho_t, lse, D, dk_h, dv_h, B, S, Hq, Hkv, d, scale, E["mask"], E["qk"], causal, window, row_iv=row_iv)
     dk, dv = torch.empty_like(kt), torch.empty_like(vt)
     ops.gqa_reduce(dk_h, dk, B * S, Hkv, rep, d)
     ops.gqa_reduce(dv_h, dv, B * S, Hkv, rep, d)
