@@ -250,24 +250,29 @@ def fused_layer_fwd(h, rstd1, qkv, qkr, W, cos, sin, B, S, meta, alloc, row_iv=N
     return st
 
 
-def fused_layer_bwd(G, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm=None, heads=None, attn_map=None):
+def fused_layer_bwd(G, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm=None, heads=None, attn_map=None, weights=None):
     """efficient placement: G at the layer's output -> G at its input in 7 GEMMs, rules / norms in their epilogues, D and RoPE's backward in the
     attention backward.  st: what the forward left, plus rstd1; alloc("half", 1, M, ...) returns fp32 rows already set to 1/2 (no fill per layer).
     A q / k / v bias (Qwen2) changes nothing here: it receives relevance and passes none on, G_h is the same GEMM.  qk_norm = (wq, wk) (Qwen3;
     st then holds rstd_q, rstd_k): the dQ kernel leaves the gradient of the ROTATED q, and one site kernel builds the whole Aqkv operand -- RoPE
     transposed, the head norms' row-constant scale, the GQA group sums -- in place of gqa_reduce_rope + gqa_reduce.
     heads: a HeadSink (explain(heads=...)) that reads the per-head relevance off the buffers while they are live; None: nothing is launched.
-    attn_map: an AttnMapSink (explain(attn_map=...)), the token-to-token maps off the same buffers; None: nothing is launched."""
+    attn_map: an AttnMapSink (explain(attn_map=...)), the token-to-token maps off the same buffers; None: nothing is launched.
+    weights: a WeightSink (explain(weights=...)), the per-weight relevance W (*) G^T X of the four Linears off the same buffers (st["m"] must
+    then be the layer's own: keep_m); the norms are folded on this path, so the Linears behind them read the un-normed stream with rs = rstd."""
     nq, nk, d = meta[:3]
     M, H, I, dt = B * S, G.shape[1], W["wd"].shape[1], G.dtype
     pt = fused_layout(H, I, nq, nk, d, dt)
     new = lambda tag, cols, pitch=None: alloc(tag, M, cols, (pitch or cols) - cols, dt)      # noqa: E731
     Agu = ops.gemm_gated_bwd_coef(G, W["wd"], st["gu"], new("Agu", 2 * I, pt["Agu"]))
+    if weights is not None:
+        weights("down", G, st["m"], W["wd"])
+        weights("gate_up", Agu, st["h1"], W["wgu"], rs=st["rstd2"])
     Gs1 = ops.gemm_nn_rs_res(Agu, W["wgu"], st["rstd2"], G, new("Gs1", H))
-    return fused_attn_bwd(Gs1, st, W, cos, sin, B, S, meta, alloc, row_iv, qk_norm, heads, attn_map)
+    return fused_attn_bwd(Gs1, st, W, cos, sin, B, S, meta, alloc, row_iv, qk_norm, heads, attn_map, weights)
 
 
-def fused_attn_bwd(Gs1, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm=None, heads=None, attn_map=None):
+def fused_attn_bwd(Gs1, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm=None, heads=None, attn_map=None, weights=None):
     """the attention half of fused_layer_bwd (the MoE driver runs it on its own): Gs1, the gradient at h1 -> G at the layer's input; everything
     from the o projection's dgrad on.  Arguments as fused_layer_bwd's"""
     nq, nk, d, _, _, scale = meta
@@ -280,6 +285,8 @@ def fused_attn_bwd(Gs1, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm
     Aqkv, dk_h, dv_h = new("Aqkv", nqkv, pt["Aqkv"]), new("dk_h", nq * d), new("dv_h", nq * d)
     if heads is not None:
         heads("out", st["o"], Gho, scale=2.0)          # (Gho = 1/2 G_o out of the dgrad's epilogue)
+    if weights is not None:
+        weights("o", Gs1, st["o"], W["wo"])
     if attn_map is not None:
         attn_map(q, k, v, Gho, st["lse"], 2.0, row_iv)
     if qk_norm is not None:
@@ -290,6 +297,8 @@ def fused_attn_bwd(Gs1, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm
             heads("k", k, dk_h, nq // nk)
             heads("v", v, dv_h, nq // nk)
         ops.qkv_bwd_pack(dq, dk_h, dv_h, qk_norm[0], qk_norm[1], st["rstd_q"], st["rstd_k"], cos, sin, Aqkv, S, nq, nk, d)
+        if weights is not None:
+            weights("qkv", Aqkv, st["h"], W["wqkv"], rs=st["rstd1"])
         return ops.gemm_nn_rs_res(Aqkv, W["wqkv"], st["rstd1"], Gs1, new("Gh", H))
     ops.attn_bwd_dq_d(q, k, v, Gho, st["o"], st["lse"], D, Aqkv[:, : nq * d], B, S, nq, nk, d, scale, row_iv=row_iv, rope=(cos, sin))
     ops.attn_bwd_dkv(q, k, v, None, Gho, None, st["lse"], D, dk_h, dv_h, B, S, nq, nk, d, scale, 0.0, 0.0, row_iv=row_iv)
@@ -299,6 +308,8 @@ def fused_attn_bwd(Gs1, st, W, cos, sin, B, S, meta, alloc, row_iv=None, qk_norm
         heads("v", v, dv_h, nq // nk)
     ops.gqa_reduce_rope(dk_h, Aqkv[:, nq * d: nqk], M, S, nk, nq // nk, d, cos, sin)
     ops.gqa_reduce(dv_h, Aqkv[:, nqk:], M, nk, nq // nk, d)
+    if weights is not None:
+        weights("qkv", Aqkv, st["h"], W["wqkv"], rs=st["rstd1"])
     return ops.gemm_nn_rs_res(Aqkv, W["wqkv"], st["rstd1"], Gs1, new("Gh", H))
 
 
@@ -604,6 +615,93 @@ class AttnMapSink:
             lo, hi_live = row_iv[0].reshape(M), torch.index_select(row_iv[1].reshape(M), 0, last, out=hi_live)
         hi = ar.get("am_hi", (M,), torch.int32, zero=True).index_copy_(0, last, hi_live)
         self(q, k, v, Gho, lse, gscale, (lo, hi))
+
+
+WEIGHTS = ("qkv", "o", "gate_up", "down")
+
+
+def weight_shapes(cfg):
+    """{name: (N, K)} of the four decoder Linears in HF row order (qkv = q | k | v rows, gate_up = gate rows then up rows)"""
+    H, I, nq, nk, d = cfg["hidden"], cfg["inter"], cfg["n_heads"], cfg["n_kv"], cfg["head_dim"]
+    return dict(qkv=((nq + 2 * nk) * d, H), o=(H, nq * d), gate_up=(2 * I, H), down=(H, I))
+
+
+def weight_request(weights, weight_layers, weights_out, cfg, nL, dtype, mode="efficient", graph=False):
+    """explain(weights=..., weight_layers=..., weights_out=...) -> (names, layers): the requested per-weight relevance matrices in WEIGHTS
+    order and the ascending layer indices (default: every layer); weights=None -> ((), ()).  Raises ValueError before a kernel of the model
+    runs: an unknown name, a non-iterable, layer indices that are not ascending integers in [0, nL) (negative indices are not wrapped),
+    weight_layers / weights_out without weights, the explicit placement (the reference's explicit rules define no weight gradient),
+    graph=True (the outputs of a dataset-level accumulation are the caller's, not a graph's static buffers), a bf16 Linear whose sizes are
+    off lrp_wgrad_rel's grid of 8, or a weights_out that is not a previous call's R_W for the same names and layers"""
+    if weights is None:
+        if weight_layers is not None or weights_out is not None:
+            raise ValueError("weight_layers / weights_out need weights=...")
+        return (), ()
+    try:
+        names = (weights,) if isinstance(weights, str) else tuple(weights)
+    except TypeError:
+        raise ValueError(f"weights must be an iterable of names from {WEIGHTS}, got {weights!r}") from None
+    bad = [n for n in names if n not in WEIGHTS]
+    if bad:
+        raise ValueError(f"weights: unknown matrix name(s) {bad}; choose from {WEIGHTS}")
+    names = tuple(n for n in WEIGHTS if n in names)
+    if weight_layers is None:
+        layers = tuple(range(nL))
+    else:
+        try:
+            layers = tuple(operator.index(l) for l in weight_layers)
+        except TypeError:
+            raise ValueError(f"weight_layers must be an iterable of layer indices, got {weight_layers!r}") from None
+        if any(not 0 <= l < nL for l in layers) or any(a >= b for a, b in zip(layers, layers[1:])):
+            raise ValueError(f"weight_layers must be ascending layer indices in [0, {nL}), got {list(layers)}")
+    if not names or not layers:
+        if weights_out is not None:
+            raise ValueError("weights_out without a matrix or a layer to accumulate")
+        return (), ()
+    if mode != "efficient":
+        raise ValueError(f"weights: the per-weight relevance is defined for the efficient placement only, not mode={mode!r}")
+    if graph:
+        raise ValueError("weights: graph=True is not supported (R_W is allocated, or accumulated into the caller's tensors, per call)")
+    shapes = weight_shapes(cfg)
+    if dtype == torch.bfloat16:
+        for n in names:
+            if shapes[n][0] % 8 or shapes[n][1] % 8:
+                raise ValueError(f"weights: the bf16 kernel needs both sizes of {n!r} {shapes[n]} to be multiples of 8")
+    if weights_out is not None:
+        if not isinstance(weights_out, dict) or set(weights_out) != set(names):
+            raise ValueError(f"weights_out must be a previous call's R_W with exactly the matrices {list(names)}")
+        for n in names:
+            t = weights_out[n]
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (len(layers), *shapes[n]) or not t.is_contiguous():
+                raise ValueError(f"weights_out[{n!r}] must be a contiguous float32 [{len(layers)}, {shapes[n][0]}, {shapes[n][1]}] tensor")
+    return names, layers
+
+
+class WeightSink:
+    """the per-weight relevance of one explanation: out[name] [len(layers), N, K] fp32 in HF row order, one ops.wgrad_rel per requested
+    matrix and layer on the buffers the backward has just left (the fused-layer functions and LlamaLRP.backward call it; a layer or a name
+    that was not requested launches nothing).  prev: a previous call's R_W -- this call's values are ADDED to it in place (every matrix of
+    every layer is visited exactly once per explanation, with all tokens of all prompts in one contraction)"""
+
+    def __init__(self, req, cfg, device, prev=None):
+        names, self.layers = req
+        shapes = weight_shapes(cfg)
+        self.slot, self.accumulate, self.li = {l: i for i, l in enumerate(self.layers)}, prev is not None, None
+        if prev is not None and any(t.device != torch.empty(0, device=device).device for t in prev.values()):          # ("cuda" -> "cuda:N")
+            raise ValueError(f"weights_out must live on {device}")
+        self.out = {n: torch.empty(len(self.layers), *shapes[n], device=device, dtype=torch.float32) for n in names} if prev is None else prev
+        self.row_map = ops.gate_up_row_map(cfg["inter"], device) if "gate_up" in names else None      # (wgu is stored gate / up interleaved)
+
+    def layer(self, li):
+        """-> the sink positioned at layer li, or None when nothing of that layer was requested"""
+        self.li = li
+        return self if li in self.slot else None
+
+    def __call__(self, name, G, X, W, rs=None):
+        """G: the gradient at the Linear's output, X: its input (with rs = the 1 / rms of a norm in front of it when X is un-normed)"""
+        if name in self.out:
+            ops.wgrad_rel(G, X, W, out=self.out[name][self.slot[self.li]], rs=rs, row_map=self.row_map if name == "gate_up" else None,
+                          accumulate=self.accumulate, check_map=False)
 
 
 class GraphCache:
@@ -994,9 +1092,10 @@ class LlamaLRP:
         return Gh_last, Gs_last, A_last, rel_last
 
     # ---------------------------------------------------------------------------------------------
-    def backward(self, fw, emb, idx, B, S, layer_relevance=False, seed=None, latent=frozenset(), heads=None, attn_map=None):
+    def backward(self, fw, emb, idx, B, S, layer_relevance=False, seed=None, latent=frozenset(), heads=None, attn_map=None, weights=None):
         """-> (G at the embedding, layer_R rows or None, dict of the token-summed latent read-outs: R_resid [L+1, B, H] / R_mlp [L, B, I]);
-        heads: a HeadSink that collects the per-head read-outs layer by layer, or None; attn_map: an AttnMapSink, likewise"""
+        heads: a HeadSink that collects the per-head read-outs layer by layer, or None; attn_map: an AttnMapSink, likewise; weights: a
+        WeightSink, likewise (the forward then ran with keep_m when "down" is asked for)"""
         c, E = self.cfg, self.eps
         H, I, d, nq, nk = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"]
         M, rep = B * S, nq // nk
@@ -1025,6 +1124,15 @@ class LlamaLRP:
         half = ar.f32("half", M).fill_(0.5) if fuse_prep else None              # (fused_layer_bwd reads it too)
         fuse_rope = fuse_prep and ops.ROPE_BWD_FUSION and E["rope"] == 0.0 and E["lin"] == 0.0 and d in (64, 128) and S <= self.max_seq
 
+        def normed(x, rstd, ln, tag):
+            """(X, rs) of a Linear behind an RMSNorm for the WeightSink: folded norm weights are ones, so the un-normed stream with rs = rstd
+            IS the Linear's input; otherwise the normed rows are formed once more (the forward keeps them in a scratch buffer only)"""
+            if self.folded:
+                return x, rstd
+            y = ar.new(tag, *x.shape)
+            ops.add_rmsnorm_fwd(x, None, ln, c["rms_eps"], y=y, rstd=ar.f32(tag + "_rstd", x.shape[0]))
+            return y, None
+
         for li in range(len(self.layers) - 1, -1, -1):
             Lw, st = self.layers[li], fw["stash"][li]
             self._load_layer(li)
@@ -1041,8 +1149,9 @@ class LlamaLRP:
                     ops.colsum_dot(st["m"], Gm, B, S, out=lat["R_mlp"][li])
             hs = None if heads is None else heads.layer(li)
             am = None if attn_map is None else attn_map.layer(li)
+            ws = None if weights is None else weights.layer(li)
             if full and not st.get("top", False):          # (Adn = Gs: eps = 0)
-                Gs = Adn = fused_layer_bwd(Gs, st, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv, self._qk_norm(Lw), hs, am)
+                Gs = Adn = fused_layer_bwd(Gs, st, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv, self._qk_norm(Lw), hs, am, ws)
                 layer_R = layer_R + [ops.readout(st["h"], Gs, out=ar.f32(("rel", li), M))] if layer_relevance else None
                 if "resid" in latent:
                     ops.colsum_dot(st["h"], Gs, B, S, out=lat["R_resid"][li])
@@ -1056,6 +1165,11 @@ class LlamaLRP:
                 ops.rmsnorm_bwd_add2(Gs_last, Gx2, Lw["ln2"], st["rstd2_l"], st["h1_l"], st["a_l"], Gs1_l, Aa_l, None, 0.0,
                                      E["add"], E["lin"])
                 Gof_l = self._lin_bwd(Aa_l, Lw["wo"], ar.new("Gof_l", B, nq * d))
+                if ws is not None:          # one row per prompt: every other token's contribution to these three matrices is exactly 0
+                    ws("down", A_last, st["m_l"], Lw["wd"])
+                    x2w, rs2 = normed(st["h1_l"], st["rstd2_l"], Lw["ln2"], "x2w_l")
+                    ws("gate_up", Agu, x2w, Lw["wgu"], rs=rs2)
+                    ws("o", Aa_l, st["o_l"], Lw["wo"])
                 Gho, D, Gs1 = top_attn_operands(ar, Gof_l, st["o_l"], Gs1_l, last, S, nq, d, E["pv"])
                 if hs is not None:
                     hs.last("out", st["o_l"], Gof_l)
@@ -1067,6 +1181,10 @@ class LlamaLRP:
                     Agu = ops.gemm_gated_bwd_coef(Adn, Lw["wd"], gu, ar.wide("Agu", M, 2 * I))
                 else:
                     Agu = ops.gemm_gated_bwd(Adn, Lw["wd"], gu, ar.wide("Agu", M, 2 * I), self.eps_g, E["lin"], self.act)
+                if ws is not None:
+                    ws("down", Adn, st["m"], Lw["wd"])
+                    x2w, rs2 = normed(st["h1"], st["rstd2"], Lw["ln2"], "x2w")
+                    ws("gate_up", Agu, x2w, Lw["wgu"], rs=rs2)
                 Gs1 = ar.new("Gs1", M, H)
                 if nfb and ops.norm_fusion_part("bwd_gu"):               # K1n: Gs1 = rstd2 (.) (Agu W'gu) + Gs in the dgrad GEMM's epilogue
                     Aa = ops.gemm_nn_rs_res(Agu, Lw["wgu"], st["rstd2"], Gs, Gs1)
@@ -1078,6 +1196,8 @@ class LlamaLRP:
                     else:
                         Aa = ar.new("Aa", M, H)
                         ops.rmsnorm_bwd_add2(Gs, Gx2, Lw["ln2"], st["rstd2"], st["h1"], st["a"], Gs1, Aa, None, 0.0, E["add"], E["lin"])
+                if ws is not None:
+                    ws("o", Aa, st["o"], Lw["wo"])
                 # ---- attention
                 Gho = ar.new("Gho", M, nq * d)
                 D = ar.f32("D", B, nq, S)
@@ -1142,6 +1262,9 @@ class LlamaLRP:
             if hs is not None:
                 hs("k", k, dk_h, rep)
                 hs("v", v, dv_h, rep)
+            if ws is not None:
+                xw, rs1 = normed(st["h"], st["rstd1"], Lw["ln1"], "xw")
+                ws("qkv", Aqkv, xw, Lw["wqkv"], rs=rs1)
             rel = ar.f32(("rel", li), M) if layer_relevance else None
             if nfb and ops.norm_fusion_part("bwd_qkv"):
                 # K1n: Gs = rstd1 (.) (Aqkv W'qkv) + Gs1 -- the input norm's identity rule and the residual add in the qkv dgrad's epilogue.  The
@@ -1177,12 +1300,13 @@ class LlamaLRP:
 
     # ---------------------------------------------------------------------------------------------
     def _run(self, input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, latent=frozenset(), heads=frozenset(), attn_map=(False, ()),
-             **opts):
+             weights=((), ()), weights_out=None, **opts):
         """forward + backward + read-out on the current stream: library launches only, no host synchronisation (capturable); opts: further
         keywords of a subclass's forward / backward (Qwen3MoeLRP: experts)"""
         if emb is None:
             emb = self.embed.index_select(0, input_ids.reshape(-1))
-        fw = self.forward(emb, B, S, row_iv, keep_m="mlp" in latent, **opts)
+        wsink = WeightSink(weights, self.cfg, self.device, weights_out) if weights[0] else None
+        fw = self.forward(emb, B, S, row_iv, keep_m="mlp" in latent or "down" in weights[0], **opts)
         if idx is None:
             # (a dense seed explains no single logit; idx / logit then report the arg-max for convenience)
             idx, _ = ops.argmax_rows(fw["logits"])
@@ -1194,6 +1318,8 @@ class LlamaLRP:
         if attn_map[0] or attn_map[1]:
             c = self.cfg
             am = AttnMapSink(attn_map, len(self.layers), B, S, c["n_heads"], c["n_kv"], c["head_dim"], self.meta[-1], self.device)
+        if wsink is not None:
+            opts = dict(opts, weights=wsink)
         G, layer_R, lat = self.backward(fw, emb, idx, B, S, layer_relevance or "trace" in latent, seed=seed, latent=latent, heads=hs, attn_map=am, **opts)
         out = explanation(emb, G, idx, fw["logits"], B, S, return_G)
         if layer_relevance:
@@ -1218,11 +1344,13 @@ class LlamaLRP:
                 out["R_attn"] = am.total
             if am.per_head is not None:
                 out["R_attn_heads"], out["attn_map_heads"] = am.per_head, list(am.pairs)
+        if wsink is not None:
+            out["R_W"], out["weight_layers"] = wsink.out, list(wsink.layers)
         return out
 
     @torch.no_grad()
     def explain(self, input_ids=None, inputs_embeds=None, target=None, layer_relevance=False, return_G=False, lengths=None,
-                seed=None, graph=False, latent=None, heads=None, attn_map=None):
+                seed=None, graph=False, latent=None, heads=None, attn_map=None, weights=None, weight_layers=None, weights_out=None):
         """input_ids [B,S] (or inputs_embeds [B,S,H]); target: None (arg-max of the last position) or
         int tensor [B].  Returns dict(idx [B], logit [B], R_tok [B,S] fp32, and optionally
         layer_R [L+1, B] (sum_h h (*) G_h at every residual-stream boundary) and G_emb [B,S,H]).
@@ -1249,7 +1377,15 @@ class LlamaLRP:
         section 12.2) R[i, j] = P[i, j] (G_o[i] . v[j]), `attn_weights * attn_weights.grad` of eager attention: how much relevance query
         position i draws from source position j.  "sum": R_attn [L, B, S, S] fp32 over all query heads; pairs: R_attn_heads [n, B, S, S] in
         request order and attn_map_heads, the pairs.  A row sums to R_head_out (1/2 of it is the uniform-rule share of P in P V); masked and pad
-        (i, j) are exactly 0; efficient placement only; nothing else changes with it."""
+        (i, j) are exactly 0; efficient placement only; nothing else changes with it.
+        weights (optional): names from {"qkv", "o", "gate_up", "down"} -- the per-weight relevance `weight * weight.grad` of those decoder
+        Linears: R_W[name] fp32 [len(weight_layers), N, K], summed over every token of every prompt of the call, rows in
+        HF order (qkv = q_proj | k_proj | v_proj rows, gate_up = gate_proj rows then up_proj rows), and weight_layers, the layer list.
+        weight_layers: ascending layer indices (default: all -- at the 8B shape all four matrices of 32 layers are ~28 GB of fp32).
+        weights_out: a previous call's R_W; this call's values are added to it in place and it is returned (dataset-level accumulation).
+        Efficient placement only, no graph=True; nothing else changes with it."""
+        wr = weight_request(weights, weight_layers, weights_out, self.cfg, len(getattr(self, "layers", ())), self.dtype,
+                            getattr(self, "mode", "efficient"), graph)
         am = attn_map_request(attn_map, len(getattr(self, "layers", ())), self.cfg.get("n_heads", 0), self.cfg.get("head_dim"), self.dtype,
                               getattr(self, "mode", "efficient"))
         hd = head_request(heads, self.cfg.get("head_dim"), self.dtype)
@@ -1259,7 +1395,7 @@ class LlamaLRP:
         if inputs_embeds is None:
             input_ids = input_ids.to(self.device)
         if not graph:
-            return self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, lat, hd, am)
+            return self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, lat, hd, am, wr, weights_out)
         if emb is not None or lengths is not None or seed is not None or return_G:
             raise ValueError("graph=True takes input_ids only (no inputs_embeds / lengths / seed / return_G)")
         return self._graphs((B, S, idx is not None, bool(layer_relevance), self.mode, tuple(sorted(lat)), tuple(sorted(hd)), am),

@@ -398,14 +398,17 @@ class Qwen3MoeLRP(Q.QwenLRP):
 
     @torch.no_grad()
     def explain(self, input_ids=None, inputs_embeds=None, target=None, layer_relevance=False, return_G=False, lengths=None, seed=None,
-                graph=False, latent=None, heads=None, attn_map=None, experts=False):
+                graph=False, latent=None, heads=None, attn_map=None, experts=False, weights=None):
         """LlamaLRP.explain for Qwen3-MoE (same arguments and outputs), with
         experts=True: two more outputs -- R_expert [L, B, E] fp32, the relevance of every expert of every layer per prompt (`routing_weights *
         routing_weights.grad` scattered by expert, summed over the prompt's tokens; rows of dense layers are exactly 0, pad tokens contribute
         exactly 0), expert_index [L, B, S, k] int64, the experts each token was routed to (-1 on dense layers), and R_block [L, B] fp32 =
         sum_{t, j} out (*) G at the sparse block's output (0 on dense layers), read off the block's own output and the gradient that reaches
         it: sum_e R_expert[l, b] = 1/2 R_block[l, b].  Every other output is bitwise what it is without the keyword.
-        Not served: latent="mlp" (a sparse layer has no single MLP) and graph=True -- both raise ValueError."""
+        Not served: latent="mlp" (a sparse layer has no single MLP), graph=True and weights= (the per-weight relevance of LlamaLRP / QwenLRP:
+        the routed experts' matrices need a grouped form of the kernel) -- all raise ValueError."""
+        if weights is not None:
+            raise ValueError("Qwen3MoeLRP: weights= (per-weight relevance) is not supported for a model with routed experts")
         names = (latent,) if isinstance(latent, str) else tuple(latent or ())
         if "mlp" in names:
             raise ValueError('Qwen3MoeLRP: latent="mlp" is not defined for a model with sparse layers (no single MLP per layer); '

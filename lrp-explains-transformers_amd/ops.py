@@ -932,6 +932,61 @@ def attn_relmap(q, k, v, g, lse, B, S, Hq, Hkv, d, scale, heads=None, gscale=1.0
     return out
 
 
+_ROW_MAPS = {}           # (I, device) -> gate_up_row_map
+
+
+def gate_up_row_map(I, device):
+    """int32 [2 I]: the HF row (gate_proj rows, then up_proj rows) of every STORED row of a fused gate/up weight -- the inverse of
+    interleave_gate_up's placement; one tensor per (I, device)"""
+    if I % GATED_IL:
+        raise ValueError(f"intermediate size {I} is not a multiple of {GATED_IL}")
+    key = (I, torch.device(device))
+    m = _ROW_MAPS.get(key)
+    if m is None:
+        s = torch.arange(2 * I, dtype=torch.int64)
+        hf = ((s // GATED_IL) % 2) * I + (s // (2 * GATED_IL)) * GATED_IL + s % GATED_IL
+        m = _ROW_MAPS[key] = hf.to(device=device, dtype=torch.int32).contiguous()
+    return m
+
+
+def wgrad_rel_ok(M, N, K, ldg, ldx, ldw, ldo, dtype):
+    """lrp_wgrad_rel serves this problem (sizes, row pitches in elements, torch dtype)"""
+    return dtype in _DT and lib.lrp_wgrad_rel_ok(M, N, K, ldg, ldx, ldw, ldo, _DT[dtype]) == 1
+
+
+def wgrad_rel(G, X, W, out=None, rs=None, row_map=None, accumulate=False, check_map=True):
+    """out[r(n), k] (+)= W[n, k] sum_t G[t, n] rs[t] X[t, k]  ([N, K] fp32): the per-weight relevance `weight * weight.grad` of the Linear
+    y = x W^T with output gradient G [M, N] and input X [M, K] (token-major, unit column stride, any row pitch), W [N, K] as stored (any row
+    pitch); rs [M] fp32: the 1 / rms of the norm in front of the Linear when X is the un-normed stream; row_map [N] int32: the row of out
+    that weight row n lands in (a permutation of [0, N): gate_up_row_map); accumulate: add to out (which then must be given) instead of
+    overwriting it; check_map: read the map back and refuse one that is no permutation (one host sync; the kernel stores through it -- the engine
+    turns it off for gate_up_row_map's own maps).  bf16: N and K multiples of 8, rs folded into G (one extra bf16 rounding); fp32: any size.  No atomics: bitwise repeatable."""
+    if G.dim() != 2 or X.dim() != 2 or W.dim() != 2:
+        raise ValueError(f"wgrad_rel: G {tuple(G.shape)}, X {tuple(X.shape)}, W {tuple(W.shape)} must be matrices")
+    (M, N), K = G.shape, X.shape[1]
+    if X.shape[0] != M or tuple(W.shape) != (N, K) or G.stride(1) != 1 or X.stride(1) != 1 or W.stride(1) != 1:
+        raise ValueError(f"wgrad_rel: G {tuple(G.shape)} / X {tuple(X.shape)} / W {tuple(W.shape)} must be [M, N] / [M, K] / [N, K] with contiguous rows")
+    pg, px, pw = p(G), p(X), p(W)                 # (device tensors only: raises before anything is allocated)
+    same(G, X, W)
+    if out is None:
+        if accumulate:
+            raise ValueError("wgrad_rel: accumulate=True needs the out tensor to add to")
+        out = torch.empty(N, K, device=G.device, dtype=torch.float32)
+    f32(out, rs)
+    if tuple(out.shape) != (N, K) or out.stride(1) != 1 or out.device != G.device:
+        raise ValueError(f"wgrad_rel: out must be a [{N}, {K}] float32 tensor with contiguous rows on {G.device}, got {tuple(out.shape)} on {out.device}")
+    if rs is not None and (tuple(rs.shape) != (M,) or not rs.is_contiguous() or rs.device != G.device):
+        raise ValueError(f"wgrad_rel: rs must be a contiguous [{M}] tensor on {G.device}")
+    if row_map is not None:
+        if row_map.dtype != torch.int32 or tuple(row_map.shape) != (N,) or not row_map.is_contiguous() or row_map.device != G.device:
+            raise ValueError(f"wgrad_rel: row_map must be a contiguous int32 [{N}] tensor on {G.device}")
+        if check_map and not torch.equal(torch.sort(row_map.long()).values, torch.arange(N, device=row_map.device)):
+            raise ValueError(f"wgrad_rel: row_map is not a permutation of [0, {N})")
+    check(lib.lrp_wgrad_rel(pg, px, pw, p(out), p(rs), p(row_map), M, N, K, G.stride(0), X.stride(0), W.stride(0), out.stride(0),
+                            int(bool(accumulate)), dt(G), stream()), "lrp_wgrad_rel")
+    return out
+
+
 def argmax_rows(logits):
     B, V = logits.shape
     idx = torch.empty(B, device=logits.device, dtype=torch.int32)
