@@ -1299,13 +1299,17 @@ class LlamaLRP:
         return Gs, layer_R, lat
 
     # ---------------------------------------------------------------------------------------------
+    def _weight_sink(self, req, prev):
+        """the sink that collects R_W for a weight_request (a subclass with other matrices returns its own)"""
+        return WeightSink(req, self.cfg, self.device, prev)
+
     def _run(self, input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, latent=frozenset(), heads=frozenset(), attn_map=(False, ()),
              weights=((), ()), weights_out=None, **opts):
         """forward + backward + read-out on the current stream: library launches only, no host synchronisation (capturable); opts: further
         keywords of a subclass's forward / backward (Qwen3MoeLRP: experts)"""
         if emb is None:
             emb = self.embed.index_select(0, input_ids.reshape(-1))
-        wsink = WeightSink(weights, self.cfg, self.device, weights_out) if weights[0] else None
+        wsink = self._weight_sink(weights, weights_out) if weights[0] else None
         fw = self.forward(emb, B, S, row_iv, keep_m="mlp" in latent or "down" in weights[0], **opts)
         if idx is None:
             # (a dense seed explains no single logit; idx / logit then report the arg-max for convenience)

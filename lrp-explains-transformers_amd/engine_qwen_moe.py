@@ -13,7 +13,11 @@ explain(experts=True) adds R_expert [L, B, E] (ops.moe_expert_relevance: `routin
 summed over a prompt's tokens; = 1/2 of the block-output relevance when summed over the experts) and expert_index [L, B, S, k].
 weight_format="mxfp4": the routed experts -- almost all of the parameters -- are resident ONLY as MXFP4 codes + scales (views of the uint8
 buffer flat_q) and the four grouped GEMMs decode them in their staging loads (ops.MoeQuantWeight): no scratch copy, no
-dequant launch, forward / backward below unchanged."""
+dequant launch, forward / backward below unchanged.
+explain(moe_weights=...) adds R_W, the per-weight relevance `weight * weight.grad` of the attention Linears, the router and the routed
+experts' gate_up_proj / down_proj (moe_weight_request, MoeWeightSink; ops.moe_wgrad_rel)."""
+import operator
+
 import torch
 
 from . import engine as E
@@ -123,6 +127,115 @@ def expert_quant_layout(cfg):
         spec[k + "_c"] = ((Ne, N, K // 2), None)
         spec[k + "_s"] = ((Ne, N, K // ops.MX_BLOCK), None)
     return [spec if moe else {} for moe in cfg["moe_layers"]]
+
+
+MOE_WEIGHTS = ("qkv", "o", "router", "gate_up", "down")
+MOE_WEIGHTS_SPARSE = ("router", "gate_up", "down")          # one row per requested SPARSE layer; qkv / o: one per requested layer
+
+
+def moe_weight_shapes(cfg):
+    """{name: shape of one layer's matrix}: qkv / o in HF row order (q | k | v rows), router = gate.weight [E, H], gate_up =
+    experts.gate_up_proj [E, 2 I, H] ([gate | up] rows), down = experts.down_proj [E, H, I]"""
+    H, Im, Ne, nq, nk, d = cfg["hidden"], cfg["moe_inter"], cfg["n_experts"], cfg["n_heads"], cfg["n_kv"], cfg["head_dim"]
+    return dict(qkv=((nq + 2 * nk) * d, H), o=(H, nq * d), router=(Ne, H), gate_up=(Ne, 2 * Im, H), down=(Ne, H, Im))
+
+
+def moe_weight_request(moe_weights, weight_layers, weights_out, cfg, dtype, mode="efficient", graph=False):
+    """explain(moe_weights=..., weight_layers=..., weights_out=...) -> (names, layers, moe): the requested matrices in MOE_WEIGHTS order, the
+    ascending layer indices (default: every layer) and the sparse ones among them; moe_weights=None -> ((), (), ()).  Raises ValueError before
+    a kernel of the model runs: an unknown name, a non-iterable, layer indices that are not ascending integers in [0, L) (negative indices
+    are not wrapped), weight_layers / weights_out without names, a placement other than the efficient one, graph=True, router / gate_up /
+    down when no requested layer is sparse, a bf16 qkv / o / router matrix off lrp_wgrad_rel's grid of 8 (the expert tensors are on it:
+    config_from_hf), or a weights_out that is not a previous call's R_W for the same names and layers"""
+    nL = len(cfg["moe_layers"])
+    if moe_weights is None:
+        if weight_layers is not None or weights_out is not None:
+            raise ValueError("weight_layers / weights_out need moe_weights=...")
+        return (), (), ()
+    try:
+        names = (moe_weights,) if isinstance(moe_weights, str) else tuple(moe_weights)
+    except TypeError:
+        raise ValueError(f"moe_weights must be an iterable of names from {MOE_WEIGHTS}, got {moe_weights!r}") from None
+    bad = [n for n in names if n not in MOE_WEIGHTS]
+    if bad:
+        raise ValueError(f"moe_weights: unknown matrix name(s) {bad}; choose from {MOE_WEIGHTS}")
+    names = tuple(n for n in MOE_WEIGHTS if n in names)
+    if weight_layers is None:
+        layers = tuple(range(nL))
+    else:
+        try:
+            layers = tuple(operator.index(l) for l in weight_layers)
+        except TypeError:
+            raise ValueError(f"weight_layers must be an iterable of layer indices, got {weight_layers!r}") from None
+        if any(not 0 <= l < nL for l in layers) or any(a >= b for a, b in zip(layers, layers[1:])):
+            raise ValueError(f"weight_layers must be ascending layer indices in [0, {nL}), got {list(layers)}")
+    if not names or not layers:
+        if weights_out is not None:
+            raise ValueError("weights_out without a matrix or a layer to accumulate")
+        return (), (), ()
+    if mode != "efficient":
+        raise ValueError(f"moe_weights: the per-weight relevance is defined for the efficient placement only, not mode={mode!r}")
+    if graph:
+        raise ValueError("moe_weights: graph=True is not supported (R_W is allocated, or accumulated into the caller's tensors, per call)")
+    moe = tuple(l for l in layers if cfg["moe_layers"][l])
+    sparse = [n for n in names if n in MOE_WEIGHTS_SPARSE]
+    if sparse and not moe:
+        raise ValueError(f"moe_weights: {sparse} belong to sparse layers and none of the requested layers {list(layers)} is sparse")
+    shapes = moe_weight_shapes(cfg)
+    if dtype == torch.bfloat16:
+        for n in names:
+            if len(shapes[n]) == 2 and (shapes[n][0] % 8 or shapes[n][1] % 8):
+                raise ValueError(f"moe_weights: the bf16 kernel needs both sizes of {n!r} {shapes[n]} to be multiples of 8")
+    if weights_out is not None:
+        if not isinstance(weights_out, dict) or set(weights_out) != set(names):
+            raise ValueError(f"weights_out must be a previous call's R_W with exactly the matrices {list(names)}")
+        for n in names:
+            t, want = weights_out[n], (len(moe) if n in MOE_WEIGHTS_SPARSE else len(layers), *shapes[n])
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != want or not t.is_contiguous():
+                raise ValueError(f"weights_out[{n!r}] must be a contiguous float32 {list(want)} tensor")
+    return names, layers, moe
+
+
+class MoeWeightSink:
+    """the per-weight relevance of one Qwen3-MoE explanation, built like engine.WeightSink: out[name] fp32, qkv / o [len(layers), N, K] and
+    router / gate_up / down [len(moe), E, ...] in HF order, one launch per requested matrix and layer on the buffers the backward has just
+    left -- ops.wgrad_rel for the dense matrices (called as a WeightSink: engine.fused_attn_bwd takes it in that place), ops.moe_wgrad_rel
+    for the expert tensors.  A layer or a name that was not requested launches nothing.  prev: a previous call's R_W -- this call's values
+    are ADDED to it in place.  Operands:
+        qkv      G = Aqkv (the gradient at the fused QKV Linear's output), X = the normed input rows (folded ln1: h with rs = rstd1)
+        o        G = Gs1 (the gradient at h1; no stabiliser on the residual add), X = o (the attention's output)
+        router   G = Glogits (moe_router_bwd), X = x2 = rstd2 (.) ln2 (.) h1
+        gate_up  G = Agu in plan rows (moe_down_dgrad), X = x2 gathered by token
+        down     G = Gs (the gradient at the layer's output) gathered by token, scaled by 1/2 w; X = m in plan rows"""
+
+    def __init__(self, req, cfg, device, prev=None):
+        names, self.layers, self.moe = req
+        shapes = moe_weight_shapes(cfg)
+        self.slot, self.mslot = {l: i for i, l in enumerate(self.layers)}, {l: i for i, l in enumerate(self.moe)}
+        self.accumulate, self.li = prev is not None, None
+        if prev is not None and any(t.device != torch.empty(0, device=device).device for t in prev.values()):          # ("cuda" -> "cuda:N")
+            raise ValueError(f"weights_out must live on {device}")
+        rows = lambda n: len(self.moe) if n in MOE_WEIGHTS_SPARSE else len(self.layers)      # noqa: E731
+        self.out = {n: torch.empty(rows(n), *shapes[n], device=device, dtype=torch.float32) for n in names} if prev is None else prev
+
+    def layer(self, li):
+        """-> the sink positioned at layer li, or None when nothing of that layer was requested"""
+        self.li = li
+        return self if li in self.slot else None
+
+    def wants(self, *names):
+        return any(n in self.out for n in names)
+
+    def __call__(self, name, G, X, W, rs=None):
+        """a dense matrix: G the gradient at the Linear's output, X its input (with rs = 1 / rms when X is un-normed)"""
+        if name in self.out:
+            slot = self.mslot[self.li] if name in MOE_WEIGHTS_SPARSE else self.slot[self.li]
+            ops.wgrad_rel(G, X, W, out=self.out[name][slot], rs=rs, accumulate=self.accumulate)
+
+    def experts(self, name, G, X, W, plan, w=None):
+        """an expert tensor of the sparse layer the sink is positioned at (ops.moe_wgrad_rel's operands)"""
+        if name in self.out:
+            ops.moe_wgrad_rel(G, X, W, plan, name, w=w, out=self.out[name][self.mslot[self.li]], accumulate=self.accumulate)
 
 
 class Qwen3MoeLRP(Q.QwenLRP):
@@ -311,9 +424,13 @@ class Qwen3MoeLRP(Q.QwenLRP):
                     **E.head_fwd(ar, h_prev, branch, False, last, self.norm, self.lm_head, eps))
 
     # ---------------------------------------------------------------------------------------------
-    def backward(self, fw, emb, idx, B, S, layer_relevance=False, seed=None, latent=frozenset(), heads=None, attn_map=None, experts=False):
+    def _weight_sink(self, req, prev):
+        return MoeWeightSink(req, self.cfg, self.device, prev)
+
+    def backward(self, fw, emb, idx, B, S, layer_relevance=False, seed=None, latent=frozenset(), heads=None, attn_map=None, experts=False,
+                 weights=None):
         """-> (G at the embedding, layer_R rows or None, dict of the extra read-outs: R_resid [L+1, B, H]; experts: R_expert [L, B, E],
-        expert_index [L, B, S, k] and R_block [L, B])"""
+        expert_index [L, B, S, k] and R_block [L, B]); weights: a MoeWeightSink that collects R_W layer by layer, or None"""
         c, ar, dev, dt = self.cfg, self._arena, self.device, self.dtype
         H, I, d, nq, nk, Ne, k = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"], c["n_experts"], c["top_k"]
         M, rep, nqk, nqkv, scale = B * S, nq // nk, (nq + nk) * d, (nq + 2 * nk) * d, d ** -0.5
@@ -335,6 +452,7 @@ class Qwen3MoeLRP(Q.QwenLRP):
             Lw, st = self.layers[li], fw["stash"][li]
             hs = None if heads is None else heads.layer(li)
             am = None if attn_map is None else attn_map.layer(li)
+            ws = None if weights is None else weights.layer(li)
             # ---- MLP half: Gs at the layer's output -> Gs1 at h1 (the norm's identity rule, rstd held constant, and the residual)
             Gs1 = ar.new("Gs1", M, H)
             if st["moe"]:
@@ -346,6 +464,13 @@ class Qwen3MoeLRP(Q.QwenLRP):
                 Gx_e = ops.moe_combine(ops.moe_gate_up_dgrad(Agu, Lw["wgu_e"], st["plan"]), st["plan"])
                 Gl = ops.moe_router_bwd(st["logits"], st["lse_r"], st["idx"], st["w"], gw, c["norm_topk"], out=ar.new("Glogits", M, Ne))
                 Gx_r = self._lin_bwd(Gl, Lw["wr"], ar.new("Gx2", M, H))
+                if ws is not None:
+                    ws.experts("down", Gs, st["m"], Lw["wd_e"], st["plan"], st["w"])
+                    if ws.wants("gate_up", "router"):          # x2 once more: the forward keeps it in a scratch buffer only (the row-scale kernel)
+                        x2 = ar.new("x2w", M, H)
+                        ops.rmsnorm_bwd_add2(None, st["h1"], Lw["ln2"], st["rstd2"], None, None, x2, None)
+                        ws.experts("gate_up", Agu, x2, Lw["wgu_e"], st["plan"])
+                        ws("router", Gl, x2, Lw["wr"])
                 Gs1e = ar.new("Gs1e", M, H)
                 ops.rmsnorm_bwd_add2(Gs, Gx_e, Lw["ln2"], st["rstd2"], None, None, Gs1e, None)
                 ops.rmsnorm_bwd_add2(Gs1e, Gx_r, Lw["ln2"], st["rstd2"], None, None, Gs1, None)
@@ -359,7 +484,7 @@ class Qwen3MoeLRP(Q.QwenLRP):
             # ---- attention half: Gs1 -> Gs at the layer's input
             qkn = self._qk_norm(Lw)
             if fa:
-                Gs = E.fused_attn_bwd(Gs1, st, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv, qkn, hs, am)
+                Gs = E.fused_attn_bwd(Gs1, st, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv, qkn, hs, am, ws)
             else:
                 qkv, qkr = st["qkv"], st["qkr"]
                 q, kk, v = qkr[:, : nq * d], qkr[:, nq * d:], qkv[:, nqk:]
@@ -387,6 +512,14 @@ class Qwen3MoeLRP(Q.QwenLRP):
                 Gqk = ops.rope_bwd(dqk, None, None, ar.new("Gqkn", M, nqk), self.cos, self.sin, S, nq + nk, d, 0.0, 0.0)
                 ops.head_rmsnorm_bwd(Gqk[:, : nq * d], qkn[0], st["rstd_q"], Aqkv[:, : nq * d], nq, d)
                 ops.head_rmsnorm_bwd(Gqk[:, nq * d:], qkn[1], st["rstd_k"], Aqkv[:, nq * d: nqk], nk, d)
+                if ws is not None:
+                    ws("o", Gs1, st["o"], Lw["wo"])
+                    if self.folded:          # folded ln1 is ones: the un-normed stream with rs = rstd1 IS the Linear's input
+                        ws("qkv", Aqkv, st["h"], Lw["wqkv"], rs=st["rstd1"])
+                    elif ws.wants("qkv"):    # the normed rows once more (the forward keeps them in a scratch buffer only)
+                        xw = ar.new("xw", M, H)
+                        ops.add_rmsnorm_fwd(st["h"], None, Lw["ln1"], c["rms_eps"], y=xw, rstd=ar.f32("xw_rstd", M))
+                        ws("qkv", Aqkv, xw, Lw["wqkv"])
                 Gx = self._lin_bwd(Aqkv, Lw["wqkv"], ar.new("Gx", M, H))
                 Gs = ar.new(("Gs", li & 1), M, H)
                 ops.rmsnorm_bwd_add2(Gs1, Gx, Lw["ln1"], st["rstd1"], None, None, Gs, None)
@@ -398,17 +531,30 @@ class Qwen3MoeLRP(Q.QwenLRP):
 
     @torch.no_grad()
     def explain(self, input_ids=None, inputs_embeds=None, target=None, layer_relevance=False, return_G=False, lengths=None, seed=None,
-                graph=False, latent=None, heads=None, attn_map=None, experts=False, weights=None):
+                graph=False, latent=None, heads=None, attn_map=None, experts=False, weights=None, moe_weights=None, weight_layers=None,
+                weights_out=None):
         """LlamaLRP.explain for Qwen3-MoE (same arguments and outputs), with
         experts=True: two more outputs -- R_expert [L, B, E] fp32, the relevance of every expert of every layer per prompt (`routing_weights *
         routing_weights.grad` scattered by expert, summed over the prompt's tokens; rows of dense layers are exactly 0, pad tokens contribute
         exactly 0), expert_index [L, B, S, k] int64, the experts each token was routed to (-1 on dense layers), and R_block [L, B] fp32 =
         sum_{t, j} out (*) G at the sparse block's output (0 on dense layers), read off the block's own output and the gradient that reaches
         it: sum_e R_expert[l, b] = 1/2 R_block[l, b].  Every other output is bitwise what it is without the keyword.
-        Not served: latent="mlp" (a sparse layer has no single MLP), graph=True and weights= (the per-weight relevance of LlamaLRP / QwenLRP:
-        the routed experts' matrices need a grouped form of the kernel) -- all raise ValueError."""
+        moe_weights (optional): names from {"qkv", "o", "router", "gate_up", "down"} -- the per-weight relevance `weight * weight.grad`
+        (DESIGN.md section 17), R_W[name], all fp32 and summed over every token of every prompt of the call: qkv [len(weight_layers),
+        (nq + 2 nk) d, H] (q_proj | k_proj | v_proj rows) and o [len(weight_layers), H, nq d] of every requested layer; router [len(moe), E, H]
+        (mlp.gate.weight), gate_up [len(moe), E, 2 I, H] (experts.gate_up_proj, [gate | up] rows) and down [len(moe), E, H, I]
+        (experts.down_proj) of the SPARSE layers among them; weight_layers, the requested layers, and weight_layers_moe, the sparse ones (the
+        rows of the last three).  An expert that received no token is exactly 0; per expert, gate_up and down each sum to R_expert summed
+        over the prompts.  weight_layers: ascending layer indices (default: all -- one 30B-A3B layer's gate_up + down are 604 M elements =
+        2.42 GB of fp32, 48 layers ~116 GB: ask for the layers you need).  weights_out: a previous call's R_W; this call's values are added to
+        it in place and it is returned (dataset-level accumulation).  weight_format="mxfp4" serves it from the codes (no dequantised copy).
+        Efficient placement only, no graph=True; moe_weights=None launches nothing and every other output is bitwise what it is without it.
+        Not part of it: the MLP matrices of dense (mlp_only_layers) layers, the monkey_patch drop-in, expert-parallel multi-GPU.
+        Not served: latent="mlp" (a sparse layer has no single MLP), graph=True and weights= (LlamaLRP / QwenLRP's keyword: its names, shapes
+        and layer lists are not this model's -- use moe_weights=) -- all raise ValueError."""
         if weights is not None:
-            raise ValueError("Qwen3MoeLRP: weights= (per-weight relevance) is not supported for a model with routed experts")
+            raise ValueError("Qwen3MoeLRP: weights= (per-weight relevance) is not supported for a model with routed experts; use moe_weights=")
+        wr = moe_weight_request(moe_weights, weight_layers, weights_out, self.cfg, self.dtype, getattr(self, "mode", "efficient"), graph)
         names = (latent,) if isinstance(latent, str) else tuple(latent or ())
         if "mlp" in names:
             raise ValueError('Qwen3MoeLRP: latent="mlp" is not defined for a model with sparse layers (no single MLP per layer); '
@@ -422,7 +568,10 @@ class Qwen3MoeLRP(Q.QwenLRP):
                                                   self.device, seed)
         if inputs_embeds is None:
             input_ids = input_ids.to(self.device)
-        return self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, lat, hd, am, experts=bool(experts))
+        out = self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, lat, hd, am, wr, weights_out, experts=bool(experts))
+        if wr[0]:
+            out["weight_layers_moe"] = list(wr[2])
+        return out
 
     @classmethod
     def from_hf(cls, model, **kw):

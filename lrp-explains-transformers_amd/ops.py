@@ -1505,6 +1505,51 @@ def moe_gate_up_dgrad(Agu, Wgu, plan):
     return gx
 
 
+MOE_WGRAD_MODES = {"gate_up": 0, "down": 1}          # (LRP_MOE_WGRAD_GATE_UP / _DOWN)
+
+
+def moe_wgrad_rel(G, X, W, plan, mode, w=None, out=None, accumulate=False):
+    """out[e][n, k] (+)= W[e][n, k] sum_{p in e} s(p) G[gp(p), n] X[xp(p), k]  ([E, N, K] fp32, contiguous): the per-weight relevance
+    `weight * weight.grad` of an expert tensor W [E, N, K] -- the tensor or a MoeQuantWeight of it (decoded in the kernel's epilogue,
+    lrp_moe_wgrad_rel_q: bit-identical to the call on dequant(dtype)) -- over the plan rows p of every expert (include/lrp_hip_moe_wgrad.h).
+    mode "gate_up": G [R, N] in plan rows (moe_down_dgrad's Agu), X [T, K] gathered by token (the experts' input); mode "down": G [T, N]
+    gathered by token (the gradient at the block's output) and scaled by 1/2 w[t, slot], X [R, K] in plan rows (the stored m), w [T, k] the
+    routing weights.  accumulate: add to out (which then must be given); an expert without rows is written as exact zeros, or left untouched
+    when accumulating.  bf16: N and K multiples of 8; quantised: K a multiple of 128.  One launch, no atomics: bitwise repeatable."""
+    if mode not in MOE_WGRAD_MODES:
+        raise ValueError(f"moe_wgrad_rel: mode must be one of {tuple(MOE_WGRAD_MODES)}, got {mode!r}")
+    if not isinstance(plan, MoePlan):
+        raise TypeError("moe_wgrad_rel: plan must be a MoePlan")
+    if G.dim() != 2 or X.dim() != 2 or len(W.shape) != 3:
+        raise ValueError(f"moe_wgrad_rel: G {tuple(G.shape)} / X {tuple(X.shape)} must be matrices and W {tuple(W.shape)} an [E, N, K] tensor")
+    E, N, K = (int(v) for v in W.shape)
+    gr, xr = (plan.rows, plan.T) if mode == "gate_up" else (plan.T, plan.rows)
+    if E != plan.E or tuple(G.shape) != (gr, N) or tuple(X.shape) != (xr, K) or G.stride(1) != 1 or X.stride(1) != 1:
+        raise ValueError(f"moe_wgrad_rel[{mode}]: G {tuple(G.shape)} / X {tuple(X.shape)} must be [{gr}, {N}] / [{xr}, {K}] with contiguous rows "
+                         f"for W {(E, N, K)} and a plan of {plan.T} tokens x {plan.k} slots over {plan.E} experts")
+    pg, px = p(G), p(X)                 # (device tensors only: raises before anything is allocated)
+    same(G, X)
+    q, wp = _moe_w(G, W)
+    if not q and not W.is_contiguous():
+        raise ValueError("moe_wgrad_rel: W must be contiguous (the kernel reads the expert tensor as stored)")
+    if mode == "down":
+        if w is None or tuple(w.shape) != (plan.T, plan.k) or not w.is_contiguous():
+            raise ValueError(f"moe_wgrad_rel[down]: w must be the contiguous routing weights [{plan.T}, {plan.k}]")
+        same(G, w)
+    if out is None:
+        if accumulate:
+            raise ValueError("moe_wgrad_rel: accumulate=True needs the out tensor to add to")
+        out = torch.empty(E, N, K, device=G.device, dtype=torch.float32)
+    f32(out)
+    if tuple(out.shape) != (E, N, K) or not out.is_contiguous() or out.device != G.device or plan.buf.device != G.device:
+        raise ValueError(f"moe_wgrad_rel: out must be a contiguous [{E}, {N}, {K}] float32 tensor on {G.device} (got {tuple(out.shape)} on "
+                         f"{out.device}) and the plan must live there too")
+    fn, name = (lib.lrp_moe_wgrad_rel_q, "lrp_moe_wgrad_rel_q") if q else (lib.lrp_moe_wgrad_rel, "lrp_moe_wgrad_rel")
+    check(fn(pg, px, *wp, p(w) if mode == "down" else None, p(plan.buf), p(out), plan.T, plan.k, E, N, K, G.stride(0), X.stride(0),
+             MOE_WGRAD_MODES[mode], int(bool(accumulate)), dt(G), stream()), name)
+    return out
+
+
 # ------------------------------------------------------------------------------------------- MoE router (csrc/moe_router.hip)
 ROUTER_EMAX, ROUTER_KMAX = 1024, 16
 
