@@ -20,6 +20,10 @@
 // of 16.  The token sum runs in fp64 (G rs X is formed exactly, the sum carries 2^-53 per step) and W acc is rounded ONCE to fp32, so the
 // parity path's own error is one fp32 rounding whatever M is.
 // Both kernels: one launch, no workspace, no atomics; a result element is formed by one thread in token order -- bitwise repeatable.
+//
+// lrp_wgrad (PLAIN = true of both kernels): the plain weight.grad of the same Linear, out[n, k] = sum_t G[t, n] X[t, k], in the operands' dtype.
+// The token loops are the ones above (one body, two epilogues); the plain epilogue reads nothing: bf16 rounds the fp32 accumulator once
+// (round-to-nearest-even) and stores one 8-byte bf16x4 per 16 x 16 tile and lane, fp32 rounds the fp64 sum once.
 #include "common.hpp"
 
 namespace {
@@ -43,9 +47,9 @@ LRP_DEVICE bf16x8 wg_frag_tr(const char* img, uint32_t off0, uint32_t off1) {
     return __builtin_bit_cast(bf16x8, v);
 }
 
-template <bool RS>
+template <bool RS, bool PLAIN>
 __global__ __launch_bounds__(256) void wgrad_rel_bf16_kernel(const bf16_t* __restrict__ G, const bf16_t* __restrict__ X,
-                                                             const bf16_t* __restrict__ W, float* __restrict__ out,
+                                                             const bf16_t* __restrict__ W, void* __restrict__ outp,
                                                              const float* __restrict__ rs, const int* __restrict__ rmap, int M, int N, int K,
                                                              int64_t ldg, int64_t ldx, int64_t ldw, int64_t ldo, int accumulate) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -114,7 +118,27 @@ __global__ __launch_bounds__(256) void wgrad_rel_bf16_kernel(const bf16_t* __res
                 for (int jg = 0; jg < 4; ++jg) acc[jx][jg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fx[jx], fg[jg], acc[jx][jg], 0, 0, 0);
         }
     }
+    if constexpr (PLAIN) {
+        // ---- plain epilogue: out[n, k .. k + 3] = bf16(acc), one rounding, nothing read
+        bf16_t* out = static_cast<bf16_t*>(outp);
+#pragma unroll
+        for (int jg = 0; jg < 4; ++jg) {
+            const int n = n0 + 64 * wn + 16 * jg + i16;
+            if (n >= N) continue;
+#pragma unroll
+            for (int jx = 0; jx < 4; ++jx) {
+                const int k = k0 + 64 * wk + 16 * jx + 4 * hi;
+                if (k >= K) continue;                                  // (K is a multiple of 8: k < K means k + 3 < K)
+                bf16x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = (bf16_t)acc[jx][jg][e];
+                *reinterpret_cast<bf16x4*>(out + (int64_t)n * ldo + k) = v;
+            }
+        }
+        return;
+    }
     // ---- epilogue: out[r(n), k .. k + 3] (+)= W[n, k .. k + 3] acc
+    float* out = static_cast<float*>(outp);
 #pragma unroll
     for (int jg = 0; jg < 4; ++jg) {
         const int n = n0 + 64 * wn + 16 * jg + i16;
@@ -141,6 +165,7 @@ __global__ __launch_bounds__(256) void wgrad_rel_bf16_kernel(const bf16_t* __res
 
 constexpr int WF_TILE = 64, WF_TT = 16;
 
+template <bool PLAIN>
 __global__ __launch_bounds__(256) void wgrad_rel_f32_kernel(const float* __restrict__ G, const float* __restrict__ X, const float* __restrict__ W,
                                                             float* __restrict__ out, const float* __restrict__ rs, const int* __restrict__ rmap,
                                                             int M, int N, int K, int64_t ldg, int64_t ldx, int64_t ldw, int64_t ldo,
@@ -186,8 +211,12 @@ __global__ __launch_bounds__(256) void wgrad_rel_f32_kernel(const float* __restr
         for (int b = 0; b < 4; ++b) {
             const int k = k0 + tx * 4 + b;
             if (k >= K) continue;
-            float v = (float)((double)W[(int64_t)n * ldw + k] * acc[a][b]);
             float* dst = out + orow * ldo + k;
+            if constexpr (PLAIN) {
+                *dst = (float)acc[a][b];
+                continue;
+            }
+            float v = (float)((double)W[(int64_t)n * ldw + k] * acc[a][b]);
             if (accumulate) v += *dst;
             *dst = v;
         }
@@ -219,13 +248,45 @@ extern "C" int lrp_wgrad_rel(const void* G, const void* X, const void* W, float*
     if (dtype == LRP_BF16) {
         const dim3 grid((unsigned)((K + WG_TILE - 1) / WG_TILE), (unsigned)((N + WG_TILE - 1) / WG_TILE));
         lrp_with_bool(rs != nullptr, [&](auto RS) {
-            hipLaunchKernelGGL((wgrad_rel_bf16_kernel<decltype(RS)::value>), grid, dim3(256), WG_LDS, st, (const bf16_t*)G, (const bf16_t*)X,
-                               (const bf16_t*)W, out, rs, rmap, M, N, K, ldg, ldx, ldw, ldo, accumulate);
+            hipLaunchKernelGGL((wgrad_rel_bf16_kernel<decltype(RS)::value, false>), grid, dim3(256), WG_LDS, st, (const bf16_t*)G, (const bf16_t*)X,
+                               (const bf16_t*)W, (void*)out, rs, rmap, M, N, K, ldg, ldx, ldw, ldo, accumulate);
         });
     } else {
         const dim3 grid((unsigned)((K + WF_TILE - 1) / WF_TILE), (unsigned)((N + WF_TILE - 1) / WF_TILE));
-        hipLaunchKernelGGL(wgrad_rel_f32_kernel, grid, dim3(256), 0, st, (const float*)G, (const float*)X, (const float*)W, out, rs, rmap, M, N, K,
+        hipLaunchKernelGGL(wgrad_rel_f32_kernel<false>, grid, dim3(256), 0, st, (const float*)G, (const float*)X, (const float*)W, out, rs, rmap, M, N, K,
                            ldg, ldx, ldw, ldo, accumulate);
+    }
+    return lrp_check_launch();
+}
+
+extern "C" int lrp_wgrad_ok(int M, int N, int K, int64_t ldg, int64_t ldx, int64_t ldo, int dtype) {
+    if (dtype != LRP_F32 && dtype != LRP_BF16) return LRP_EINVAL;
+    if (M < 1 || N < 1 || K < 1 || ldg < N || ldx < K || ldo < K) return LRP_ESHAPE;
+    const int tile = dtype == LRP_BF16 ? WG_TILE : WF_TILE;
+    if (((int64_t)N + tile - 1) / tile > 65535) return LRP_ESHAPE;
+    if (dtype == LRP_BF16) {
+        if (N % 8 || K % 8) return LRP_ESHAPE;                            // 16-byte chunks of G and X rows: inside or outside as a whole
+        if (ldg % 8 || ldx % 8 || ldo % 4) return LRP_EALIGN;             // out: one 8-byte bf16x4 store per lane
+    }
+    return 1;
+}
+
+extern "C" int lrp_wgrad(const void* G, const void* X, void* out, int M, int N, int K, int64_t ldg, int64_t ldx, int64_t ldo, int dtype,
+                         void* stream) {
+    if (!G || !X || !out) return LRP_EINVAL;
+    const int ok = lrp_wgrad_ok(M, N, K, ldg, ldx, ldo, dtype);
+    if (ok != 1) return ok;
+    if (dtype == LRP_BF16 ? (((uintptr_t)G | (uintptr_t)X) % 16 || (uintptr_t)out % 8) : (((uintptr_t)G | (uintptr_t)X | (uintptr_t)out) % 4))
+        return LRP_EALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == LRP_BF16) {
+        const dim3 grid((unsigned)((K + WG_TILE - 1) / WG_TILE), (unsigned)((N + WG_TILE - 1) / WG_TILE));
+        hipLaunchKernelGGL((wgrad_rel_bf16_kernel<false, true>), grid, dim3(256), WG_LDS, st, (const bf16_t*)G, (const bf16_t*)X,
+                           (const bf16_t*)nullptr, out, (const float*)nullptr, (const int*)nullptr, M, N, K, ldg, ldx, (int64_t)0, ldo, 0);
+    } else {
+        const dim3 grid((unsigned)((K + WF_TILE - 1) / WF_TILE), (unsigned)((N + WF_TILE - 1) / WF_TILE));
+        hipLaunchKernelGGL(wgrad_rel_f32_kernel<true>, grid, dim3(256), 0, st, (const float*)G, (const float*)X, (const float*)nullptr,
+                           (float*)out, (const float*)nullptr, (const int*)nullptr, M, N, K, ldg, ldx, (int64_t)0, ldo, 0);
     }
     return lrp_check_launch();
 }

@@ -8,42 +8,65 @@ from torch.autograd import Function
 from .. import ops
 
 
+def _param_grad(v, ref):
+    """an fp32 column sum as the gradient of the parameter `ref`: its dtype (lrp_cast) and its shape"""
+    return (v if v.dtype == ref.dtype else ops.cast(v, ref.dtype)).view(ref.shape)
+
+
 class RMSNormFn(Function):
     """K2: y = w' * x * rsqrt(mean(x^2)+eps) ; backward = identity rule (rsqrt detached):
-    G_x = G_y * w' * rstd.   ref: lxt/efficient/patches.py:111-123, lxt/efficient/models/gemma3.py:11-12"""
+    G_x = G_y * w' * rstd.   ref: lxt/efficient/patches.py:111-123, lxt/efficient/models/gemma3.py:11-12
+    A trainable weight (w' = w or 1 + w) gets its plain gradient sum_t G_y x rstd (ops.colsum_affine); x is kept for it, and only then."""
 
     @staticmethod
     def forward(ctx, x, weight, eps, w_offset):
         shp = x.shape
         x2 = x.reshape(-1, shp[-1]).contiguous()
         y, rstd = ops.add_rmsnorm_fwd(x2, None, weight, eps, w_offset)
-        ctx.save_for_backward(weight, rstd)
+        if ctx.needs_input_grad[1]:
+            ctx.save_for_backward(weight, rstd, x2)
+        else:
+            ctx.save_for_backward(weight, rstd)
         ctx.w_offset = w_offset
         return y.view(shp)
 
     @staticmethod
     def backward(ctx, gy):
-        weight, rstd = ctx.saved_tensors
+        weight, rstd, *x2 = ctx.saved_tensors
         shp = gy.shape
         g2 = gy.reshape(-1, shp[-1]).contiguous()
         gx = torch.empty_like(g2)
         ops.rmsnorm_bwd_add2(None, g2, weight, rstd, None, None, gx, None, None, ctx.w_offset, 0.0, 0.0)
-        return gx.view(shp), None, None, None
+        gw = _param_grad(ops.colsum_affine(g2, x2[0], None, rstd)[0], weight) if x2 else None
+        return gx.view(shp), gw, None, None
 
 
 class LayerNormFn(Function):
-    """K7: LayerNorm with std detached.  ref: lxt/efficient/patches.py:126-142"""
+    """K7: LayerNorm with std detached.  ref: lxt/efficient/patches.py:126-142
+    Trainable weight / bias get their plain gradients sum_t G_y (x - mean) rstd and sum_t G_y (ops.colsum_affine); x and the mean are kept
+    for the weight's, and only then."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, eps):
-        y, _, rstd = ops.layernorm_fwd(x, weight, bias, eps)
-        ctx.save_for_backward(weight, rstd)
+        y, mean, rstd = ops.layernorm_fwd(x, weight, bias, eps)
+        if ctx.needs_input_grad[1]:
+            ctx.save_for_backward(weight, rstd, x.reshape(-1, x.shape[-1]).contiguous(), mean)
+        else:
+            ctx.save_for_backward(weight, rstd)
+        ctx.bias = bias if bias is not None and ctx.needs_input_grad[2] else None         # (shape and dtype of its gradient)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        weight, rstd = ctx.saved_tensors
-        return ops.layernorm_bwd(gy, None, weight, rstd, 0.0), None, None, None
+        weight, rstd, *xm = ctx.saved_tensors
+        gx = ops.layernorm_bwd(gy, None, weight, rstd, 0.0)
+        gw = gb = None
+        if xm or ctx.bias is not None:
+            g2 = gy.reshape(-1, gy.shape[-1]).contiguous()
+            dw, db = ops.colsum_affine(g2, *(xm if xm else (None, None)), rstd if xm else None, want_bias=ctx.bias is not None)
+            gw = _param_grad(dw, weight) if xm else None
+            gb = _param_grad(db, ctx.bias) if ctx.bias is not None else None
+        return gx, gw, gb, None
 
 
 class GatedActFn(Function):
@@ -182,30 +205,51 @@ class RopeFn(Function):
         return A.view(B, S, H, d).transpose(1, 2), None, None
 
 
+def _weight_grad(g2, x2):
+    """G^T X of two token-major matrices on lrp_wgrad, in their dtype.  Operands off the 16-byte grid are copied onto it; a bf16 problem whose N
+    or K is no multiple of 8 (a 2-way classifier head) runs the fp32 kernel on cast operands (lrp_cast) and is rounded once."""
+    v = ops.epc(g2)
+    g2, x2 = (t if t.stride(0) % v == 0 and t.data_ptr() % 16 == 0 else t.contiguous() for t in (g2, x2))
+    if g2.dtype == torch.bfloat16 and (g2.shape[1] % 8 or x2.shape[1] % 8 or g2.stride(0) % 8 or x2.stride(0) % 8):
+        return ops.cast(ops.wgrad(ops.cast(g2, torch.float32), ops.cast(x2, torch.float32)), torch.bfloat16)
+    return ops.wgrad(g2, x2)
+
+
 class LinearFn(Function):
     """K1 (efficient form, eps = 0): z = x W^T + b, backward G_x = G_z W -- both from the STORED weight [out, in] (ops.linear_fwd /
     ops.linear_dgrad pick the kernel by row count and dtype; bf16 never makes a W^T copy).  `weight_t` is accepted for callers of the
-    round-2 signature and ignored."""
+    round-2 signature and ignored.
+    Trainable parameters get their plain gradients from the library as well: weight.grad = G_z^T x (ops.wgrad; the 2-D input is kept for it,
+    and only then), bias.grad = sum_t G_z (ops.colsum_affine).  `stored`: the Parameter of a module that keeps its weight [in, out] (HF's
+    Conv1D), `weight` then being a frozen [out, in] copy of it: its gradient x^T G_z is the same kernel with the operands swapped."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, weight_t=None):
+    def forward(ctx, x, weight, bias, weight_t=None, stored=None):
         shp = x.shape
         x2 = x.reshape(-1, shp[-1])
         if x2.stride(-1) != 1:
             x2 = x2.contiguous()
         z = ops.linear_fwd(x2, weight, bias)
-        ctx.save_for_backward(weight)
+        ctx.wgrad = (ctx.needs_input_grad[1], stored is not None and ctx.needs_input_grad[4])
+        if any(ctx.wgrad):
+            ctx.save_for_backward(weight, x2)
+        else:
+            ctx.save_for_backward(weight)
+        ctx.bias = bias if bias is not None and ctx.needs_input_grad[2] else None         # (shape and dtype of its gradient)
         return z.view(*shp[:-1], weight.shape[0])
 
     @staticmethod
     def backward(ctx, gz):
-        (w,) = ctx.saved_tensors
+        w, *x2 = ctx.saved_tensors
         shp = gz.shape
         g2 = gz.reshape(-1, shp[-1])
         if g2.stride(-1) != 1:
             g2 = g2.contiguous()
         gx = ops.linear_dgrad(g2, w)
-        return gx.view(*shp[:-1], w.shape[1]), None, None, None
+        gw = _weight_grad(g2, x2[0]) if ctx.wgrad[0] else None
+        gs = _weight_grad(x2[0], g2) if ctx.wgrad[1] else None
+        gb = _param_grad(ops.colsum_affine(g2, want_bias=True)[1], ctx.bias) if ctx.bias is not None else None
+        return gx.view(*shp[:-1], w.shape[1]), gw, gb, None, gs
 
 
 def _kernel_head_dim(d, dtype):

@@ -73,6 +73,11 @@ def _owned(m):
     return m.__dict__.get("_lrp_owned", False)
 
 
+def _operand(param):
+    """a parameter as a Function's operand: the Parameter itself when it is trainable (autograd must see it), else a detached alias"""
+    return param if param is None or param.requires_grad else param.detach()
+
+
 def _adopting_call(self, *args, **kwargs):
     if not self.__dict__.get("_lrp_adopted", False):
         adopt(self)
@@ -128,44 +133,44 @@ def layer_norm_forward(self, x):
 def linear_forward(self, x):
     """nn.Linear on the MFMA GEMM, forward and dgrad from the stored weight (bf16: no W^T copy; fp32: one cached on the weight).  Not patched by
     the reference (ATen mm there); part of the default maps here so the whole backward runs on liblrp_hip.so.  Only
-    instances of an explained model with frozen weights take this path (see `adopt`); everything else -- foreign
-    modules, CPU probes, trainable weights, dtypes the kernels do not serve -- runs torch's own forward unchanged."""
+    instances of an explained model take this path (see `adopt`); everything else -- foreign modules, CPU probes, dtypes the
+    kernels do not serve -- runs torch's own forward unchanged.  A trainable weight / bias is handed over as the Parameter itself, so
+    autograd sees it and LinearFn returns its plain gradient (lrp_wgrad / lrp_colsum_affine)."""
     w = self.weight
-    if hasattr(self, "original_forward") and (not _owned(self) or w.requires_grad or x.dtype != w.dtype
-                                              or x.dtype not in (torch.float32, torch.bfloat16)):
+    if hasattr(self, "original_forward") and (not _owned(self) or x.dtype != w.dtype or x.dtype not in (torch.float32, torch.bfloat16)):
         return self.original_forward(x)
     _need_cuda(x, "linear_forward")
-    return LinearFn.apply(x, w.detach(), self.bias.detach() if self.bias is not None else None)
+    return LinearFn.apply(x, _operand(w), _operand(self.bias))
 
 
 def conv1d_forward(self, x):
     """HF's Conv1D (GPT-2's c_attn / c_fc / c_proj: y = x W + b with W stored [in, out]) on the MFMA GEMM: the forward
     uses a cached [out, in] copy (ops.weight_t), the dgrad the NN form on that copy (bf16) or the stored weight (fp32).  The reference leaves these
-    on ATen (lxt/efficient/models/gpt2.py:11-32 patches only the MLP forward around them)."""
+    on ATen (lxt/efficient/models/gpt2.py:11-32 patches only the MLP forward around them).  A trainable weight rides along as LinearFn's
+    `stored` operand and gets its gradient in the stored [in, out] layout."""
     w = self.weight
-    if hasattr(self, "original_forward") and (not _owned(self) or w.requires_grad or x.dtype != w.dtype
-                                              or x.dtype not in (torch.float32, torch.bfloat16)):
+    if hasattr(self, "original_forward") and (not _owned(self) or x.dtype != w.dtype or x.dtype not in (torch.float32, torch.bfloat16)):
         return self.original_forward(x)
     _need_cuda(x, "conv1d_forward")
     from .. import ops
     wd = w.detach()
-    return LinearFn.apply(x, ops.weight_t(wd), self.bias.detach() if self.bias is not None else None)     # cached [out, in] copy
+    return LinearFn.apply(x, ops.weight_t(wd), _operand(self.bias), None, w if w.requires_grad else None)     # cached [out, in] copy
 
 
 def conv2d_patch_forward(self, x):
     """nn.Conv2d whose stride equals its kernel (ViT / SigLIP patch embedding) as ONE GEMM over the unfolded patches:
     same arithmetic, un-patched (plain gradient) semantics as in the reference, but forward AND input-gradient run on
     liblrp_hip.so instead of MIOpen (whose backward-data solver search for the 896x896, 14x14/14 SigLIP stem takes
-    minutes on a fresh box).  Any other convolution falls through to the original forward."""
+    minutes on a fresh box).  Any other convolution falls through to the original forward.  Trainable weight / bias: LinearFn's gradients."""
     kh, kw = self.kernel_size
-    if (not _owned(self) or self.weight.requires_grad or x.dim() != 4 or not x.is_cuda or tuple(self.stride) != (kh, kw) or self.groups != 1 or tuple(self.dilation) != (1, 1)
+    if (not _owned(self) or x.dim() != 4 or not x.is_cuda or tuple(self.stride) != (kh, kw) or self.groups != 1 or tuple(self.dilation) != (1, 1)
             or self.padding not in ((0, 0), "valid", 0) or self.padding_mode != "zeros" or x.dtype not in (torch.float32, torch.bfloat16)):
         return self._conv_forward(x, self.weight, self.bias)
     B, C, Hh, Ww = x.shape
     gh, gw = Hh // kh, Ww // kw
     patches = x[:, :, : gh * kh, : gw * kw].reshape(B, C, gh, kh, gw, kw).permute(0, 2, 4, 1, 3, 5).reshape(B * gh * gw, C * kh * kw)
-    w2 = self.weight.detach().reshape(self.out_channels, C * kh * kw)
-    y = LinearFn.apply(patches, w2, self.bias.detach() if self.bias is not None else None)
+    w2 = _operand(self.weight).reshape(self.out_channels, C * kh * kw)          # (trainable: autograd reshapes the [out, C kh kw] gradient to 4-D)
+    y = LinearFn.apply(patches, w2, _operand(self.bias))
     return y.view(B, gh, gw, self.out_channels).permute(0, 3, 1, 2)
 
 

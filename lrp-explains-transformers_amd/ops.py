@@ -987,6 +987,68 @@ def wgrad_rel(G, X, W, out=None, rs=None, row_map=None, accumulate=False, check_
     return out
 
 
+def wgrad_ok(M, N, K, ldg, ldx, ldo, dtype):
+    """lrp_wgrad serves this problem (sizes, row pitches in elements, torch dtype)"""
+    return dtype in _DT and lib.lrp_wgrad_ok(M, N, K, ldg, ldx, ldo, _DT[dtype]) == 1
+
+
+def wgrad(G, X, out=None):
+    """out[n, k] = sum_t G[t, n] X[t, k]  ([N, K], the operands' dtype): the plain `weight.grad` of the Linear y = x W^T with output gradient
+    G [M, N] and input X [M, K] (token-major, unit column stride, any row pitch).  A weight stored [in, out] (HF's Conv1D): wgrad(X, G).
+    bf16: N and K multiples of 8, wgrad_rel's token loop and ONE round-to-nearest-even of its fp32 accumulator; fp32: any size, fp64 token sum.
+    No atomics: bitwise repeatable."""
+    if G.dim() != 2 or X.dim() != 2:
+        raise ValueError(f"wgrad: G {tuple(G.shape)} and X {tuple(X.shape)} must be matrices")
+    (M, N), K = G.shape, X.shape[1]
+    if X.shape[0] != M or G.stride(1) != 1 or X.stride(1) != 1:
+        raise ValueError(f"wgrad: G {tuple(G.shape)} / X {tuple(X.shape)} must be [M, N] / [M, K] with contiguous rows")
+    pg, px = p(G), p(X)                 # (device tensors only: raises before anything is allocated)
+    same(G, X)
+    dt(G)
+    if out is None:
+        out = torch.empty(N, K, device=G.device, dtype=G.dtype)
+    same(G, out)
+    if tuple(out.shape) != (N, K) or out.stride(1) != 1:
+        raise ValueError(f"wgrad: out must be a [{N}, {K}] tensor with contiguous rows, got {tuple(out.shape)}")
+    check(lib.lrp_wgrad(pg, px, p(out), M, N, K, G.stride(0), X.stride(0), out.stride(0), dt(G), stream()), "lrp_wgrad")
+    return out
+
+
+def colsum_affine(g, x=None, mean=None, rstd=None, want_bias=False, ws=None):
+    """-> (dw, db), fp32 [N] each or None:  dw[j] = sum_t g[t, j] (x[t, j] - mean[t]) rstd[t]  (when x is given),  db[j] = sum_t g[t, j]  (when
+    want_bias) for g, x [M, N] with unit column stride (any row pitch), mean / rstd fp32 [M] or None (0 / 1): the weight gradient of an
+    RMSNorm, a (1 + w) norm or a per-head norm (mean None), the weight and bias gradients of a LayerNorm, the bias gradient of a Linear
+    (x None).  Fixed-order fp32 sums over 64-row chunks, no atomics: bitwise repeatable.
+    ws: the caller's workspace (uint8, at least lrp_colsum_affine_ws bytes); None: the per-stream scratch buffer"""
+    if g.dim() != 2 or g.stride(1) != 1:
+        raise ValueError(f"colsum_affine: g {tuple(g.shape)} must be [M, N] with contiguous rows")
+    M, N = g.shape
+    if x is None and not want_bias:
+        raise ValueError("colsum_affine: nothing to compute (no x and want_bias=False)")
+    if x is None and (mean is not None or rstd is not None):
+        raise ValueError("colsum_affine: mean / rstd without x")
+    if x is not None and (tuple(x.shape) != (M, N) or x.stride(1) != 1):
+        raise ValueError(f"colsum_affine: x {tuple(x.shape)} must have g's shape {tuple(g.shape)} and contiguous rows")
+    pg, px = p(g), p(x)                 # (device tensors only: raises before anything is allocated)
+    same(g, x)
+    f32(mean, rstd)
+    for name, t in (("mean", mean), ("rstd", rstd)):
+        if t is not None and (tuple(t.shape) != (M,) or not t.is_contiguous() or t.device != g.device):
+            raise ValueError(f"colsum_affine: {name} must be a contiguous [{M}] tensor on {g.device}")
+    need = lib.lrp_colsum_affine_ws(M, N)
+    if need < 0:
+        raise ValueError(f"colsum_affine: bad sizes M={M}, N={N}")
+    dw = torch.empty(N, device=g.device, dtype=torch.float32) if x is not None else None
+    db = torch.empty(N, device=g.device, dtype=torch.float32) if want_bias else None
+    if need and ws is None:
+        ws = workspace(need, g)
+    elif need and ws.numel() * ws.element_size() < need:
+        raise ValueError(f"colsum_affine: workspace of {ws.numel() * ws.element_size()} bytes, {need} needed")
+    check(lib.lrp_colsum_affine(pg, px, p(mean), p(rstd), p(dw), p(db), p(ws) if need else None, M, N, g.stride(0),
+                                x.stride(0) if x is not None else 0, dt(g), stream()), "lrp_colsum_affine")
+    return dw, db
+
+
 def argmax_rows(logits):
     B, V = logits.shape
     idx = torch.empty(B, device=logits.device, dtype=torch.int32)
