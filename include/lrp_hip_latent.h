@@ -49,6 +49,17 @@ int lrp_attn_relmap(const void* q, const void* k, const void* v, const void* g, 
                     int Hkv, int d, int h_lo, int h_hi, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, float scale, float gscale,
                     int causal, const int* row_lo, const int* row_hi, int dtype, void* stream);
 
+/* lrp_attn_relmap_d256 (csrc/attnmap.hip): lrp_attn_relmap for LRP_BF16 at d == 256 (Gemma-3's head dim) -- the same arguments in the same
+ * order, the same out[b, i, j], masks, lse convention, error ladder and guarantees (every element written, masked (i, j) selected to exactly
+ * 0, a row with lse = -inf gives 0, dead tiles zero-filled without a load, one launch, no workspace, no atomics, bitwise deterministic and
+ * batch invariant); any other dtype or d -> LRP_ESHAPE (an unknown dtype -> LRP_EINVAL).  Both contractions on the bf16 MFMA, fp32 from the
+ * accumulators to the store.  K and V are staged in two panels of 128 columns (LDS: 34 KB per workgroup in place of 84 KB); the score and
+ * G_P accumulators of the query heads that share the staged kv head live across the two panels, so one staging serves all rep heads of a
+ * group for rep <= 4 (a wider group is walked in chunks of 4 heads); the MFMA steps of a head still run in the order of d. */
+int lrp_attn_relmap_d256(const void* q, const void* k, const void* v, const void* g, const float* lse, float* out, int M, int B, int S, int Hq,
+                         int Hkv, int d, int h_lo, int h_hi, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, float scale, float gscale,
+                         int causal, const int* row_lo, const int* row_hi, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

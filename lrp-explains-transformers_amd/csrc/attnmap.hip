@@ -1,4 +1,4 @@
-// attnmap.hip -- token-to-token attention relevance maps (include/lrp_hip_latent.h: lrp_attn_relmap).
+// attnmap.hip -- token-to-token attention relevance maps (include/lrp_hip_latent.h: lrp_attn_relmap, lrp_attn_relmap_d256).
 //
 // out[b, i, j] = gscale sum_{h_lo <= h < h_hi} P_h[i, j] (g_h[i] . v_{h / rep}[j]),  P_h[i, j] = exp(scale q_h[i] . k_{h / rep}[j] - lse[b, h, i])
 // for the (i, j) the mask lets through (causal, per-row key intervals), exactly 0 elsewhere: `attn_weights * attn_weights.grad` of eager
@@ -51,8 +51,9 @@ LRP_DEVICE bool am_tile_rows(int* s_lo, int* s_hi, const int* __restrict__ row_l
 }
 
 // the tile leaves as runs of AM_T floats along j; so == nullptr: zeros (a dead tile)
+template <int NT = 256>
 LRP_DEVICE void am_store_tile(float* __restrict__ out, const float (*so)[AM_T + 1], int b, int S, int i0, int j0) {
-    for (int e = threadIdx.x; e < AM_T * AM_T; e += 256) {
+    for (int e = threadIdx.x; e < AM_T * AM_T; e += NT) {
         const int r = e / AM_T, c = e - r * AM_T;
         if (i0 + r < S && j0 + c < S) out[((int64_t)b * S + i0 + r) * S + j0 + c] = so ? so[r][c] : 0.f;
     }
@@ -135,6 +136,116 @@ __global__ __launch_bounds__(256) void attn_relmap_bf16_kernel(const bf16_t* __r
         for (int r = 0; r < 4; ++r) so[il][jb * 16 + lg * 4 + r] = tot[jb][r] * gscale;
     __syncthreads();
     am_store_tile(out, so, b, S, i0, j0);
+}
+
+// ---- bf16, d = 256 (Gemma-3): the contraction of the kernel above, with K and V staged in TWO panels of 128 columns.  A full-width pair of
+// tiles (2 x 64 x 264 bf16) plus the output tile is ~84 KB of LDS: one workgroup per CU, one wave per SIMD, nothing to hide the q / g / lse
+// loads behind.  A panel pair is 34 KB, and the output tile reuses it after the last head, so LDS admits four workgroups per CU.  The price
+// is that the fp32 accumulators s and gp of the heads that share the staged panel live across the two panels: RC heads x 4 key blocks x
+// (s, gp) x 4 registers.  A staging serves min(rep, RC) query heads of one kv group: all of them for rep <= 4 (Gemma-3: 2 and 4); a wider
+// group is walked in chunks of RC heads and staged once per chunk.  To keep that register set small the tile is shared by EIGHT waves: wave
+// w owns the 16 query rows (w & 3) * 16.. and the 32 keys (w >> 2) * 32.. (two key blocks, not four), which halves the accumulators per
+// wave; the two waves of a row group read the same q / g fragments (the second read is a cache hit).  The MFMA steps of a head run in the
+// order of d (panel 0: kk 0..3, panel 1: kk 4..7) and the heads are added to the tile in ascending order, so the sums are those of a
+// single-pass kernel.
+constexpr int AM_PD = 128;               // panel width (columns of d)
+constexpr int AM_NT8 = 512;              // threads of the eight-wave workgroup
+
+template <int RC>
+__global__ __launch_bounds__(AM_NT8) void attn_relmap_bf16_d256_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
+                                                                    const bf16_t* __restrict__ v, const bf16_t* __restrict__ g,
+                                                                    const float* __restrict__ lse, float* __restrict__ out, int S, int Hq,
+                                                                    int rep, int h_lo, int h_hi, int64_t ldq, int64_t ldk, int64_t ldv,
+                                                                    int64_t ldg, float scale, float gscale, int causal,
+                                                                    const int* __restrict__ row_lo, const int* __restrict__ row_hi, int T) {
+    constexpr int D = 256;
+    constexpr int P = AM_PD + 8;        // LDS row pitch (elements), as above
+    constexpr int KK = AM_PD / 32;      // MFMA steps of one panel
+    constexpr int TILE = AM_T * P;      // elements of one staged panel
+    static_assert(2 * TILE * sizeof(bf16_t) >= AM_T * (AM_T + 1) * sizeof(float), "the output tile reuses the panels' LDS");
+    __shared__ __attribute__((aligned(16))) bf16_t skv[2 * TILE];
+    __shared__ int s_lo[AM_T], s_hi[AM_T];
+    bf16_t* sk = skv;
+    bf16_t* sv = skv + TILE;
+    float(*so)[AM_T + 1] = reinterpret_cast<float(*)[AM_T + 1]>(skv);
+    const int b = blockIdx.y, ti = blockIdx.x / T, tj = blockIdx.x - ti * T;
+    const int i0 = ti * AM_T, j0 = tj * AM_T;
+    if (!am_tile_rows(s_lo, s_hi, row_lo, row_hi, b, S, i0, j0, causal)) {
+        am_store_tile<AM_NT8>(out, nullptr, b, S, i0, j0);
+        return;
+    }
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, lr = lane & 15, lg = lane >> 4;
+    const int il = (wave & 3) * 16 + lr;                   // this lane's query row inside the tile
+    const int jw = (wave >> 2) * 2;                        // this wave's first key block
+    const int64_t irow = (int64_t)b * S + min(i0 + il, S - 1);
+    const int my_lo = s_lo[il], my_hi = s_hi[il];
+    const float c1 = scale * AM_LOG2E;
+    f32x4 tot[2];
+#pragma unroll
+    for (int jb = 0; jb < 2; ++jb) tot[jb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int h0 = h_lo; h0 < h_hi;) {
+        const int kvh = h0 / rep;
+        const int nh = min(min((kvh + 1) * rep, h_hi) - h0, RC);          // heads of this chunk: one kv head, uniform over the workgroup
+        f32x4 s[RC][2], gp[RC][2];
+#pragma unroll
+        for (int c = 0; c < RC; ++c)
+#pragma unroll
+            for (int jb = 0; jb < 2; ++jb) s[c][jb] = gp[c][jb] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int pn = 0; pn < D / AM_PD; ++pn) {
+            __syncthreads();                               // (every wave is done with the previous panel)
+            for (int e = t; e < AM_T * (AM_PD / 8); e += AM_NT8) {
+                const int r = e / (AM_PD / 8), c = (e - r * (AM_PD / 8)) * 8;
+                const int64_t jrow = (int64_t)b * S + min(j0 + r, S - 1);
+                *reinterpret_cast<bf16x8*>(&sk[r * P + c]) = *reinterpret_cast<const bf16x8*>(k + jrow * ldk + (int64_t)kvh * D + pn * AM_PD + c);
+                *reinterpret_cast<bf16x8*>(&sv[r * P + c]) = *reinterpret_cast<const bf16x8*>(v + jrow * ldv + (int64_t)kvh * D + pn * AM_PD + c);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int c = 0; c < RC; ++c) {
+                if (c < nh) {
+                    bf16x8 qf[KK], gf[KK];
+#pragma unroll
+                    for (int kk = 0; kk < KK; ++kk) {
+                        qf[kk] = *reinterpret_cast<const bf16x8*>(q + irow * ldq + (int64_t)(h0 + c) * D + pn * AM_PD + kk * 32 + lg * 8);
+                        gf[kk] = *reinterpret_cast<const bf16x8*>(g + irow * ldg + (int64_t)(h0 + c) * D + pn * AM_PD + kk * 32 + lg * 8);
+                    }
+#pragma unroll
+                    for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+                        for (int kk = 0; kk < KK; ++kk) {
+                            const int off = ((jw + jb) * 16 + lr) * P + kk * 32 + lg * 8;
+                            s[c][jb] = Mma16<bf16_t>::mma(*reinterpret_cast<const bf16x8*>(&sk[off]), qf[kk], s[c][jb]);
+                            gp[c][jb] = Mma16<bf16_t>::mma(*reinterpret_cast<const bf16x8*>(&sv[off]), gf[kk], gp[c][jb]);
+                        }
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < RC; ++c) {
+            if (c < nh) {
+                const float l = lse[((int64_t)b * Hq + h0 + c) * S + min(i0 + il, S - 1)];
+                const bool row_ok = l > -INFINITY;
+                const float l2 = l * AM_LOG2E;
+#pragma unroll
+                for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int j = j0 + (jw + jb) * 16 + lg * 4 + r;
+                        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[c][jb][r], c1, -l2));
+                        tot[jb][r] += (row_ok && j >= my_lo && j < my_hi) ? p * gp[c][jb][r] : 0.f;
+                    }
+            }
+        }
+        h0 += nh;
+    }
+    __syncthreads();                                       // (every wave is done with the last panel: its LDS becomes the output tile)
+#pragma unroll
+    for (int jb = 0; jb < 2; ++jb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) so[il][(jw + jb) * 16 + lg * 4 + r] = tot[jb][r] * gscale;
+    __syncthreads();
+    am_store_tile<AM_NT8>(out, so, b, S, i0, j0);
 }
 
 // ---- fp32, any d <= 256 that is a multiple of 4 (the parity path): LDS tiles of AM_DK columns of the four operands, a thread owns a 4 x 4
@@ -260,5 +371,33 @@ extern "C" int lrp_attn_relmap(const void* q, const void* k, const void* v, cons
         hipLaunchKernelGGL(attn_relmap_bf16_kernel<128>, grid, dim3(256), 0, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
                            (const bf16_t*)g, lse, out, S, Hq, rep, h_lo, h_hi, ldq, ldk, ldv, ldg, scale, gscale, causal, row_lo, row_hi, (int)T);
     }
+    return lrp_check_launch();
+}
+
+extern "C" int lrp_attn_relmap_d256(const void* q, const void* k, const void* v, const void* g, const float* lse, float* out, int M, int B, int S,
+                                    int Hq, int Hkv, int d, int h_lo, int h_hi, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldg, float scale,
+                                    float gscale, int causal, const int* row_lo, const int* row_hi, int dtype, void* stream) {
+    if (!q || !k || !v || !g || !lse || !out || (dtype != LRP_F32 && dtype != LRP_BF16)) return LRP_EINVAL;
+    if (B < 1 || S < 1 || (int64_t)B * S != (int64_t)M || Hq < 1 || Hkv < 1 || Hq % Hkv != 0 || h_lo < 0 || h_hi > Hq || h_lo >= h_hi ||
+        dtype != LRP_BF16 || d != 256 || ldq < (int64_t)Hq * d || ldg < (int64_t)Hq * d || ldk < (int64_t)Hkv * d || ldv < (int64_t)Hkv * d ||
+        (row_lo == nullptr) != (row_hi == nullptr) || B > 65535)
+        return LRP_ESHAPE;
+    const int64_t T = ((int64_t)S + AM_T - 1) / AM_T;
+    if (T * T > INT_MAX) return LRP_ESHAPE;
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)g) % 16 || ldq % 8 || ldk % 8 || ldv % 8 || ldg % 8 ||
+        ((uintptr_t)out | (uintptr_t)lse | (uintptr_t)row_lo | (uintptr_t)row_hi) % 4)
+        return LRP_EALIGN;
+    const dim3 grid((unsigned)(T * T), (unsigned)B);
+    hipStream_t st = (hipStream_t)stream;
+    const int rep = Hq / Hkv;
+#define LRP_RELMAP_D256(RC)                                                                                                                   \
+    hipLaunchKernelGGL(attn_relmap_bf16_d256_kernel<RC>, grid, dim3(AM_NT8), 0, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,       \
+                       (const bf16_t*)g, lse, out, S, Hq, rep, h_lo, h_hi, ldq, ldk, ldv, ldg, scale, gscale, causal, row_lo, row_hi, (int)T)
+    // the heads one staging serves: a single head (rep 1, or a one-head range) needs no second set of accumulators
+    const int width = min(rep, h_hi - h_lo);
+    if (width == 1) LRP_RELMAP_D256(1);
+    else if (width == 2) LRP_RELMAP_D256(2);
+    else LRP_RELMAP_D256(4);
+#undef LRP_RELMAP_D256
     return lrp_check_launch();
 }

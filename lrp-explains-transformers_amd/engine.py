@@ -595,15 +595,17 @@ class AttnMapSink:
         self.li = li
         return self
 
-    def __call__(self, q, k, v, g, lse, gscale, row_iv=None):
+    def __call__(self, q, k, v, g, lse, gscale, row_iv=None, causal=True):
+        """causal=False: row_iv holds COMPLETE per-row key intervals (Gemma-3 image + text prompts: an image block sees itself in both
+        directions); a sliding window arrives folded into row_iv's lower ends"""
         a = (q, k, v, g, lse, self.B, self.S, self.nq, self.nk, self.d, self.scale)
         if self.total is not None:
-            ops.attn_relmap(*a, gscale=gscale, row_iv=row_iv, out=self.total[self.li])
+            ops.attn_relmap(*a, gscale=gscale, causal=causal, row_iv=row_iv, out=self.total[self.li])
         for n, (l, h) in enumerate(self.pairs):
             if l == self.li:
-                ops.attn_relmap(*a, heads=(h, h + 1), gscale=gscale, row_iv=row_iv, out=self.per_head[n])
+                ops.attn_relmap(*a, heads=(h, h + 1), gscale=gscale, causal=causal, row_iv=row_iv, out=self.per_head[n])
 
-    def top(self, ar, q, k, v, Gho, lse, gscale, last, row_iv=None):
+    def top(self, ar, q, k, v, Gho, lse, gscale, last, row_iv=None, causal=True):
         """the sparse top layer: Gho is dense with one live row per prompt, and lse is written for those rows only -- every other row gets an
         empty key interval, so it is exactly 0 whatever its lse holds.  The interval vectors are arena buffers (ar), as every temporary of
         the backward"""
@@ -614,7 +616,7 @@ class AttnMapSink:
         else:
             lo, hi_live = row_iv[0].reshape(M), torch.index_select(row_iv[1].reshape(M), 0, last, out=hi_live)
         hi = ar.get("am_hi", (M,), torch.int32, zero=True).index_copy_(0, last, hi_live)
-        self(q, k, v, Gho, lse, gscale, (lo, hi))
+        self(q, k, v, Gho, lse, gscale, (lo, hi), causal)
 
 
 WEIGHTS = ("qkv", "o", "gate_up", "down")

@@ -18,8 +18,8 @@ activations live in the same tagged arena as the Llama driver's.
 import torch
 
 from . import ops
-from .engine import (EFFICIENT, Arena, explain_inputs, explanation, fused_layout, head_fwd, pack_flat, put_gate_up, put_rows, rope_tables,
-                     top_attn_operands)
+from .engine import (EFFICIENT, Arena, AttnMapSink, HeadSink, attn_map_request, explain_inputs, explanation, fused_layout, head_fwd,
+                     head_request, latent_request, pack_flat, pitch_pad, put_gate_up, put_rows, rope_tables, top_attn_operands)
 
 _STATIC_ROPE = ("default", "linear")
 
@@ -82,8 +82,45 @@ def weights_from_hf(model):
     return cfg, W
 
 
+def gemma_attn_map_request(attn_map, nL, nq, d, dtype, mode="efficient"):
+    """engine.attn_map_request for the Gemma-3 drivers: the same forms, checks and ValueErrors, and bf16 at d = 256 is served as well
+    (lrp_attn_relmap_d256).  That one case is validated at d = 128, a head dim the shared parser accepts in bf16: every other check of it
+    (names, pairs, the placement) does not look at d"""
+    if dtype == torch.bfloat16 and isinstance(d, int) and d == 256:
+        d = 128
+    return attn_map_request(attn_map, nL, nq, d, dtype, mode)
+
+
+def readout_outputs(out, B, S, layer_R, lat, want_layer_R, want_trace, hs, am, device):
+    """the read-outs of one explanation added to explain()'s dict under LlamaLRP.explain's names (README, DESIGN.md section 12 - 12.2);
+    layer_R: [rel_last [B], per-token rows [M] from the top boundary down to the embedding] or None"""
+    if want_layer_R:
+        rows = [layer_R[0]] + [r.view(B, S).sum(1) for r in layer_R[1:]]
+        out["layer_R"] = torch.stack(rows[::-1], 0)          # [L+1, B], index 0 = embedding
+    if want_trace:
+        nL = len(layer_R) - 1
+        trace = torch.zeros(nL + 1, B, S, device=device, dtype=torch.float32)
+        trace[0] = out["R_tok"]
+        for li in range(1, nL):
+            trace[li] = layer_R[nL - li].view(B, S)
+        trace[nL, :, S - 1] = layer_R[0]
+        out["R_trace"] = trace
+    out.update(lat)
+    if hs is not None:
+        out.update({"R_head_" + n: t for n, t in hs.out.items()})
+        if "out" in hs.out:
+            out["R_head"] = hs.out["out"].sum(-1)
+    if am is not None:
+        if am.total is not None:
+            out["R_attn"] = am.total
+        if am.per_head is not None:
+            out["R_attn_heads"], out["attn_map_heads"] = am.per_head, list(am.pairs)
+    return out
+
+
 class Gemma3LRP:
-    """explain(input_ids) -> dict(idx, logit, R_tok, logits): AttnLRP (lxt.efficient) token relevances of a Gemma-3 text decoder"""
+    """explain(input_ids) -> dict(idx, logit, R_tok, logits): AttnLRP (lxt.efficient) token relevances of a Gemma-3 text decoder; on request
+    the layer, latent, per-head and token-to-token read-outs of LlamaLRP.explain"""
 
     def __init__(self, cfg, W, dtype=torch.bfloat16, device="cuda", max_seq=4096, sparse_top=True):
         if not torch.cuda.is_available():
@@ -147,7 +184,9 @@ class Gemma3LRP:
         return True, self._window(li), row_iv
 
     # ---------------------------------------------------------------------------------------------
-    def forward(self, emb, B, S, row_iv=None):
+    def forward(self, emb, B, S, row_iv=None, keep_h=False, keep_m=False):
+        """keep_h / keep_m: every layer's input h / down-projection input m gets a buffer of its own (the read-outs of the backward need
+        them); otherwise h lives in a two-buffer ping-pong and m in one shared buffer, and neither survives its layer"""
         c = self.cfg
         H, I, d, nq, nk = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"]
         M, dt, dev = B * S, self.dtype, self.device
@@ -158,6 +197,8 @@ class Gemma3LRP:
         h_prev, branch, nxt = emb, None, None
         last = torch.arange(B, device=dev) * S + (S - 1)
         site = ops.sandwich_norm_ok(emb)      # Gemma-3's norms / q-k norm / RoPE fused per site (ops.SITE_FUSION; results bit-identical)
+        h_tag = (lambda li: ("h_keep", li)) if keep_h else (lambda li: ("h", li & 1))
+        m_buf = (lambda li: ar.get(("m_keep", li), (M, I), dt, pad=pitch_pad(I, dt.itemsize))) if keep_m else (lambda li: ar.wide("m", M, I))
         for li, Lw in enumerate(self.layers):
             st = {}
             cos, sin = self.rope[c["layer_types"][li]]
@@ -171,8 +212,9 @@ class Gemma3LRP:
                     h = h_prev
                     ops.add_rmsnorm_fwd(h_prev, None, Lw["ln_in"], eps, 1.0, y=x, rstd=st["rstd1"])
                 else:
-                    h = ar.new(("h", li & 1), M, H)
+                    h = ar.new(h_tag(li), M, H)
                     ops.add_rmsnorm_fwd(h_prev, branch, Lw["ln_in"], eps, 1.0, hsum_out=h, y=x, rstd=st["rstd1"])
+            st["h"] = h
             qkv = ops.linear_fwd(x, Lw["wqkv"], out=ar.new(("qkv", li), M, nqkv))
             # per-head q / k norm straight out of the fused projection output (strided rows), then RoPE with this layer type's table
             st["rstd_q"], st["rstd_k"] = ar.f32(("rstd_q", li), M * nq), ar.f32(("rstd_k", li), M * nk)
@@ -200,7 +242,8 @@ class Gemma3LRP:
                 gu_l, m_l = ops.gemm_gated_fwd(x2_l, Lw["wgu"], ar.new("gu_l", B, 2 * I), ar.new("m_l", B, I), self.act)
                 dn_l = ops.linear_fwd(m_l, Lw["wd"], out=ar.new("dn_l", B, H))
                 pff_l, rstd_pff_l = ops.add_rmsnorm_fwd(dn_l, None, Lw["ln_pff"], eps, 1.0)
-                st.update(top=True, qkv=qkv, qr=qr, kr=kr, lse=lse, o_l=o_l, gu_l=gu_l, rstd_pa_l=rstd_pa_l, rstd2_l=rstd2_l, rstd_pff_l=rstd_pff_l)
+                st.update(top=True, qkv=qkv, qr=qr, kr=kr, lse=lse, o_l=o_l, gu_l=gu_l, m_l=m_l, rstd_pa_l=rstd_pa_l, rstd2_l=rstd2_l,
+                          rstd_pff_l=rstd_pff_l)
                 stash.append(st)
                 h_prev, branch = h1_l, pff_l
                 break
@@ -217,16 +260,16 @@ class Gemma3LRP:
                 ops.add_rmsnorm_fwd(h, pa, Lw["ln_pf"], eps, 1.0, hsum_out=h1, y=x2, rstd=st["rstd2"])
             coef = ops.gated_coef_ok(M, I, H, H, Lw["wgu"].stride(0), H, Lw["wd"].stride(0), self.act, dt)
             if coef:      # gated rules inside the two GEMMs: the backward's coefficients are stashed in gu's place (ops.gemm_gated_fwd_coef)
-                gu, m = ops.gemm_gated_fwd_coef(x2, Lw["wgu"], ar.new(("gu", li), M, 2 * I), ar.wide("m", M, I), self.eps_g, self.eps["lin"], self.act)
+                gu, m = ops.gemm_gated_fwd_coef(x2, Lw["wgu"], ar.new(("gu", li), M, 2 * I), m_buf(li), self.eps_g, self.eps["lin"], self.act)
             else:
-                gu, m = ops.gemm_gated_fwd(x2, Lw["wgu"], ar.new(("gu", li), M, 2 * I), ar.wide("m", M, I), self.act)
+                gu, m = ops.gemm_gated_fwd(x2, Lw["wgu"], ar.new(("gu", li), M, 2 * I), m_buf(li), self.act)
             dn = ops.linear_fwd(m, Lw["wd"], out=ar.new("dn", M, H))
             st["rstd_pff"] = ar.f32(("rstd_pff", li), M)
-            st.update(qkv=qkv, qr=qr, kr=kr, o=o, lse=lse, gu=gu, coef=coef)
+            st.update(qkv=qkv, qr=qr, kr=kr, o=o, lse=lse, gu=gu, coef=coef, m=m)
             stash.append(st)
             if site and li + 1 < len(self.layers):
                 # post-feed-forward norm, residual add and the NEXT layer's input norm in one pass
-                nxt = (ar.new(("h", (li + 1) & 1), M, H), ar.new("x", M, H), ar.f32(("rstd1", li + 1), M))
+                nxt = (ar.new(h_tag(li + 1), M, H), ar.new("x", M, H), ar.f32(("rstd1", li + 1), M))
                 ops.sandwich_norm_fwd(dn, h1, Lw["ln_pff"], self.layers[li + 1]["ln_in"], eps, 1.0, nxt[0], nxt[1], st["rstd_pff"], nxt[2])
                 continue
             nxt = None
@@ -237,19 +280,50 @@ class Gemma3LRP:
         return dict(stash=stash, last=last, row_iv=row_iv, site=site, **head_fwd(ar, h_prev, branch, top, last, self.norm, self.lm_head, eps, 1.0))
 
     # ---------------------------------------------------------------------------------------------
-    def backward(self, fw, idx, B, S):
+    def _map_mask(self, cache, li, row_iv, B, S):
+        """-> (causal, row intervals) of layer li's token-to-token map.  lrp_attn_relmap has no window argument: a sliding layer of a text
+        prompt gets per-row intervals with the window folded in, lo = max(first, i - w + 1), built on the device once per call and window
+        size (cache); image + text prompts hand over complete intervals per layer type and the call is not causal (_attn_mask)"""
+        causal, win, iv = self._attn_mask(li, row_iv)
+        if not win:
+            return causal, iv
+        if win not in cache:
+            i = torch.arange(S, device=self.device, dtype=torch.int32)
+            lo = (i - (win - 1)).clamp_min(0)[None].expand(B, S)
+            if iv is None:
+                cache[win] = (lo.contiguous(), (i + 1)[None].expand(B, S).contiguous())
+            else:
+                cache[win] = (torch.maximum(iv[0], lo).contiguous(), iv[1])
+        return causal, cache[win]
+
+    def backward(self, fw, idx, B, S, layer_relevance=False, latent=frozenset(), heads=None, attn_map=None):
+        """-> G at the embedding; with any read-out asked for -> (G, layer_R rows or None, dict of the token-summed latent read-outs), as
+        LlamaLRP.backward.  layer_relevance / "resid" need forward(keep_h=True), "mlp" forward(keep_m=True); heads: a HeadSink, attn_map: an
+        AttnMapSink (None: nothing is launched)"""
         c, E = self.cfg, self.eps
         H, I, d, nq, nk = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"]
         M, rep = B * S, nq // nk
         nqd, nkd, nqkv = nq * d, nk * d, (nq + 2 * nk) * d
         ar = self._arena
+        nL, dev = len(self.layers), self.device
+        plain = not (layer_relevance or latent or heads is not None or attn_map is not None)
+        lat, layer_R, iv_cache = {}, None, {}
         # LM head (gradient of the explained logit) + final (1 + w) norm on the one explained row of each prompt, scattered into [M, H]
         Gh_last = ops.head_seed(self.lm_head, fw["logits"], idx, self.norm, fw["rstd_f"], ar.new("Gh_last", B, H), 1.0, E["lin"])
         top = bool(fw["stash"]) and fw["stash"][-1].get("top", False)
         Gs = None if top else ar.zeros(("Gs", len(self.layers) & 1), M, H).index_copy_(0, fw["last"], Gh_last)       # gradient w.r.t. h_L = h1 + pff
+        if layer_relevance:          # index L: the head's explained rows (S = 1)
+            layer_R = [ops.readout(fw["hL_last"], Gh_last, out=ar.f32("rel_last", B))]
+        if "resid" in latent:
+            lat["R_resid"] = torch.empty(nL + 1, B, H, device=dev, dtype=torch.float32)
+            ops.colsum_dot(fw["hL_last"], Gh_last, B, 1, out=lat["R_resid"][nL])
+        if "mlp" in latent:
+            lat["R_mlp"] = torch.empty(nL, B, I, device=dev, dtype=torch.float32)
         site, Gdn = fw["site"], None
         for li in range(len(self.layers) - 1, -1, -1):
             Lw, st = self.layers[li], fw["stash"][li]
+            hs = None if heads is None else heads.layer(li)
+            am = None if attn_map is None else attn_map.layer(li)
             cos, sin = self.rope[c["layer_types"][li]]
             causal, win, iv = self._attn_mask(li, fw["row_iv"])
             q_begin = 0
@@ -264,12 +338,18 @@ class Gemma3LRP:
                 ops.rmsnorm_bwd_add2(None, Gs1_l, Lw["ln_pa"], st["rstd_pa_l"], None, None, Ga_l, None, None, 1.0, 0.0, 0.0)
                 Gof_l = ops.linear_dgrad(Ga_l, Lw["wo"], out=ar.new("Gof_l", B, nqd))
                 Gho, D, Gs1 = top_attn_operands(ar, Gof_l, st["o_l"], Gs1_l, fw["last"], S, nq, d, E["pv"])
+                if "mlp" in latent:      # G_m = Gdn Wd, one dgrad the backward otherwise folds into Agu; one row per prompt, the others' neurons are 0
+                    ops.colsum_dot(st["m_l"], ops.linear_dgrad(Gdn_l, Lw["wd"], out=ar.new("Gm_l", B, I)), B, 1, out=lat["R_mlp"][li])
+                if hs is not None:
+                    hs.last("out", st["o_l"], Gof_l)
                 q_begin = S - 1
             else:
                 # ---- post-feed-forward norm, gated MLP, pre-feed-forward norm + residual
                 if Gdn is None:      # (with the site kernels the layer above has produced Gdn together with Gs)
                     Gdn = ar.new("Gdn", M, H)
                     ops.rmsnorm_bwd_add2(None, Gs, Lw["ln_pff"], st["rstd_pff"], None, None, Gdn, None, None, 1.0, 0.0, 0.0)
+                if "mlp" in latent:
+                    ops.colsum_dot(st["m"], ops.linear_dgrad(Gdn, Lw["wd"], out=ar.new("Gm", M, I)), B, S, out=lat["R_mlp"][li])
                 if st["coef"]:
                     Agu = ops.gemm_gated_bwd_coef(Gdn, Lw["wd"], st["gu"], ar.wide("Agu", M, 2 * I))
                 else:
@@ -285,7 +365,15 @@ class Gemma3LRP:
                 Gof = ops.linear_dgrad(Ga, Lw["wo"], out=ar.new("Gof", M, nqd))
                 Gho, D = ar.new("Gho", M, nqd), ar.f32("D", B, nq, S)
                 ops.attn_bwd_prep(Gof, st["o"], Gho, D, B, S, nq, d, E["pv"], 0.5)
+                if hs is not None:
+                    hs("out", st["o"], Gof)
             q, k, v = st["qr"], st["kr"], st["qkv"][:, nqd + nkd:]
+            if am is not None:          # (Gho = 1/2 G_o: attn_bwd_prep's factor)
+                m_causal, m_iv = self._map_mask(iv_cache, li, fw["row_iv"], B, S)
+                if q_begin == 0:
+                    am(q, k, v, Gho, st["lse"], 2.0, m_iv, m_causal)
+                else:
+                    am.top(ar, q, k, v, Gho, st["lse"], 2.0, fw["last"], m_iv, m_causal)
             k_t = q_t = Gho_t = None
             if self.attn_t:
                 k_t = ops.transpose_heads(k, B, S, nk, d)
@@ -297,6 +385,13 @@ class Gemma3LRP:
                             row_iv=iv)
             ops.attn_bwd_dkv(q, k, v, q_t, Gho, Gho_t, st["lse"], D, dk_h, dv_h, B, S, nq, nk, d, c["scale"], E["mask"], E["qk"], causal, win,
                              q_begin=q_begin, row_iv=iv)
+            if hs is not None:          # after the q / k norm and RoPE, k and v per QUERY head (before the group sums): no rotary table needed
+                if q_begin == 0:
+                    hs("q", q, dq)
+                else:          # (the sparse top layer: dq's only live rows)
+                    hs.last("q", q.index_select(0, fw["last"]), dq.index_select(0, fw["last"]))
+                hs("k", k, dk_h, rep)
+                hs("v", v, dv_h, rep)
             Aqkv = ar.new("Aqkv", M, nqkv)
             if site:      # the group sums, RoPE's backward and the q / k norms' scale in one pass over dq / dk_h / dv_h
                 ops.qkv_bwd_pack(dq, dk_h, dv_h, Lw["qn"], Lw["kn"], st["rstd_q"], st["rstd_k"], cos, sin, Aqkv, S, nq, nk, d, 1.0)
@@ -318,21 +413,56 @@ class Gemma3LRP:
             else:
                 Gdn = None
                 ops.rmsnorm_bwd_add2(Gs1, Gx, Lw["ln_in"], st["rstd1"], None, None, Gs, None, None, 1.0, 0.0, 0.0)
-        return Gs
+            # ---- the boundary read-outs: one pass over the stored gradient and the layer's kept input
+            if layer_relevance:
+                layer_R.append(ops.readout(st["h"], Gs, out=ar.f32(("rel", li), M)))
+            if "resid" in latent:
+                ops.colsum_dot(st["h"], Gs, B, S, out=lat["R_resid"][li])
+        return Gs if plain else (Gs, layer_R, lat)
 
     # ---------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def explain(self, input_ids=None, inputs_embeds=None, target=None, return_G=False, lengths=None):
+    def readout_requests(self, latent, heads, attn_map):
+        """-> (latent, heads, attn_map) requests, checked: every ValueError is raised before a kernel of the model runs"""
+        c = self.cfg
+        am = gemma_attn_map_request(attn_map, len(getattr(self, "layers", ())), c.get("n_heads", 0), c.get("head_dim"), self.dtype)
+        return latent_request(latent, c["hidden"], c["inter"], self.dtype), head_request(heads, c.get("head_dim"), self.dtype), am
+
+    def explain_emb(self, emb, B, S, row_iv, idx, return_G=False, layer_relevance=False, lat=frozenset(), hd=frozenset(), am=(False, ())):
+        """forward + backward + read-outs on prepared embeddings and CHECKED requests (readout_requests) -> (explain()'s dict, G at the embedding);
+        with no request the buffers, the launches and every output are those of the plain call"""
+        c = self.cfg
+        want_R = layer_relevance or "trace" in lat
+        fw = self.forward(emb, B, S, row_iv, keep_h=want_R or "resid" in lat, keep_m="mlp" in lat)
+        if idx is None:
+            idx, _ = ops.argmax_rows(fw["logits"])
+        if not (want_R or lat or hd or am[0] or am[1]):
+            G = self.backward(fw, idx, B, S)
+            return explanation(emb, G, idx, fw["logits"], B, S, return_G), G
+        nL = len(self.layers)
+        hs = HeadSink(hd, nL, B, S, c["n_heads"], c["head_dim"], self.device) if hd else None
+        ams = AttnMapSink(am, nL, B, S, c["n_heads"], c["n_kv"], c["head_dim"], c["scale"], self.device) if am[0] or am[1] else None
+        G, layer_R, sums = self.backward(fw, idx, B, S, want_R, lat, hs, ams)
+        out = explanation(emb, G, idx, fw["logits"], B, S, return_G)
+        return readout_outputs(out, B, S, layer_R, sums, layer_relevance, "trace" in lat, hs, ams, self.device), G
+
+    @torch.no_grad()
+    def explain(self, input_ids=None, inputs_embeds=None, target=None, return_G=False, lengths=None, layer_relevance=False, latent=None,
+                heads=None, attn_map=None):
         """input_ids [B, S] (or inputs_embeds [B, S, H] = HF's scaled embeddings); target: None (arg-max of the last position) or [B]
         vocabulary indices.  Returns dict(idx [B], logit [B], R_tok [B, S] fp32 = sum_h e (*) dlogit/de, logits [B, V]).
         lengths [B] (optional): prompts of different lengths in one call, LEFT-padded to S (as LlamaLRP.explain: pad keys are masked through
-        the attention kernels' per-row key intervals, RoPE is relative, R_tok is exactly 0 at pad positions)."""
+        the attention kernels' per-row key intervals, RoPE is relative, R_tok is exactly 0 at pad positions).
+        layer_relevance, latent, heads, attn_map (optional): the read-outs of LlamaLRP.explain under the same names, shapes and meaning --
+        layer_R [L+1, B];  latent from {"trace", "resid", "mlp"}: R_trace [L+1, B, S], R_resid [L+1, B, H], R_mlp [L, B, I];  heads from
+        {"out", "q", "k", "v"}: R_head_out / _q / _k / _v [L, B, n_heads, S] and R_head [L, B, n_heads] (q / k after the head norms and RoPE,
+        k / v per QUERY head at the source position);  attn_map "sum" and / or (layer, head) pairs: R_attn [L, B, S, S], R_attn_heads
+        [n, B, S, S] and attn_map_heads (bf16 at head dim 256 runs lrp_attn_relmap_d256).  Entries outside a sliding layer's window, above
+        the diagonal and at pad positions are exactly 0.  Requests are checked before a kernel of the model runs; R_tok, logit, idx and logits
+        do not change with them, and a call without them allocates and launches what it always did."""
+        lat, hd, am = self.readout_requests(latent, heads, attn_map)
         B, S, emb, row_iv, idx = explain_inputs(input_ids, inputs_embeds, lengths, target, self.cfg["vocab"], self.max_seq, self.dtype,
                                                 self.device)
         if emb is None:
             emb = self.embed.index_select(0, input_ids.to(self.device).reshape(-1)) * self.embed_scale.to(self.device)
-        fw = self.forward(emb, B, S, row_iv)
-        if idx is None:
-            idx, _ = ops.argmax_rows(fw["logits"])
-        G = self.backward(fw, idx, B, S)
-        return explanation(emb, G, idx, fw["logits"], B, S, return_G)
+        return self.explain_emb(emb, B, S, row_iv, idx, return_G, layer_relevance, lat, hd, am)[0]

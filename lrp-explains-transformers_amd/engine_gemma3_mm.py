@@ -21,7 +21,7 @@ constant [tokens, patches] matrix (power-of-two pooling windows: 1 / k^2 exact i
 import torch
 
 from . import ops
-from .engine import explain_inputs, explanation
+from .engine import explain_inputs
 from .engine_gemma3 import Gemma3LRP
 
 
@@ -251,12 +251,17 @@ class Gemma3MMLRP:
                    SiglipLRP.from_hf(model, dtype=dtype, device=device, vision_attn_rule=vision_attn_rule))
 
     @torch.no_grad()
-    def explain(self, input_ids, pixel_values, token_type_ids=None, target=None, attention_mask=None, lengths=None):
-        """Prompts of ONE length only: this driver builds its masks from the image-token positions alone (causal text, bidirectional image blocks),
+    def explain(self, input_ids, pixel_values, token_type_ids=None, target=None, attention_mask=None, lengths=None, layer_relevance=False,
+                heads=None, attn_map=None):
+        """layer_relevance / heads / attn_map: the text decoder's read-outs, as Gemma3LRP.explain returns them (layer_R, R_head_*, R_attn,
+        R_attn_heads); image-token positions are ordinary rows and columns of the [S, S] maps ("which image patches does head h of layer l
+        pull its relevance from"); the SigLIP tower's own heads are not read out.  Checked before anything runs.
+        Prompts of ONE length only: this driver builds its masks from the image-token positions alone (causal text, bidirectional image blocks),
         so a padded batch would attend to its pad tokens -- refused loudly (use one call per length, or the drop-in path
         lxt_amd.efficient.monkey_patch(modeling_gemma3), which takes HF's padding masks).  Also unlike LlamaLRP / Gemma3LRP: no workspace arena and
         no hipGraph capture yet -- the tower allocates its stashes per call (visible as host_issue_frac in bench.py's config4 image+text line)."""
         tx, vi = self.text, self.vision
+        _, hd, am = tx.readout_requests(None, heads, attn_map)
         dev = tx.device
         ids = input_ids.to(dev)
         B, S = ids.shape
@@ -277,16 +282,17 @@ class Gemma3MMLRP:
             raise ValueError(f"{rows_h.numel()} image tokens in input_ids for {n_img} images of {vi.T} tokens each")
         iv_h = mm_row_intervals(tt_h, tx.cfg["window"]) if bool(tt_h.any()) else None
         rows, is_img = rows_h.to(dev), is_img_h.to(dev)
-        fv = vi.forward(pixel_values)
+        fv = vi.forward(pixel_values) if n_img else None                         # (a text-only prompt: the tower has nothing to run on)
         safe = torch.where(is_img, torch.zeros_like(ids), ids) if self.image_token_id >= tx.cfg["vocab"] else ids
         emb = tx.embed.index_select(0, safe.reshape(-1)) * tx.embed_scale.to(dev)
-        emb.index_copy_(0, rows, fv["feat"].to(emb.dtype))                       # HF: inputs_embeds.masked_scatter(image mask, image features)
+        if fv is not None:
+            emb.index_copy_(0, rows, fv["feat"].to(emb.dtype))                   # HF: inputs_embeds.masked_scatter(image mask, image features)
         iv = None if iv_h is None else {k: (lo.to(dev), hi.to(dev)) for k, (lo, hi) in iv_h.items()}
-        fw = tx.forward(emb, B, S, iv)
-        if idx is None:
-            idx, _ = ops.argmax_rows(fw["logits"])
-        G = tx.backward(fw, idx, B, S)
-        out = explanation(emb, G, idx, fw["logits"], B, S)
+        out, G = tx.explain_emb(emb, B, S, iv, idx, False, layer_relevance, frozenset(), hd, am)
+        if fv is None:
+            out["R_pix"] = torch.zeros(pixel_values.shape, device=dev, dtype=torch.float32)
+            out["R_patch"] = torch.zeros(0, vi.grid, vi.grid, device=dev, dtype=torch.float32)
+            return out
         out["R_tok"].view(-1).index_fill_(0, rows, 0.0)                         # the word embeddings at image positions were replaced: no relevance
         Gpix, Gpatch = vi.backward(fv, G.index_select(0, rows))
         out["R_pix"] = ops.mul(fv["pv"].contiguous(), Gpix.contiguous()).float()

@@ -912,7 +912,8 @@ def attn_relmap(q, k, v, g, lse, B, S, Hq, Hkv, d, scale, heads=None, gscale=1.0
     """out[b, i, j] = gscale sum_{lo <= h < hi} P_h[i, j] (g_h[i] . v_{h // rep}[j])  ([B, S, S] fp32, every element written): the token-to-token
     attention relevance `attn_weights * attn_weights.grad`, summed over the query heads heads = (lo, hi) (None: all of them).  q, g [B S, Hq d]
     and k, v [B S, Hkv d] token-major with unit column stride (any row pitch), lse [B, Hq, S] as attn_fwd left it; g is the gradient at the o
-    projection's input (gscale = 2 for the dgrad epilogue's Gho).  bf16: d in {64, 128}; fp32: any d <= 256 that is a multiple of 4.
+    projection's input (gscale = 2 for the dgrad epilogue's Gho).  bf16: d in {64, 128} (lrp_attn_relmap) and d = 256 (lrp_attn_relmap_d256:
+    K / V staged in two 128-column panels, Gemma-3's head dim); fp32: any d <= 256 that is a multiple of 4.
     Masked (i, j) -- causal, row_iv -- are exactly 0.  Fixed-order fp32 sums, a prompt's result depends on its rows only."""
     lo, hi = (0, Hq) if heads is None else (int(heads[0]), int(heads[1]))
     M = q.shape[0]
@@ -927,8 +928,9 @@ def attn_relmap(q, k, v, g, lse, B, S, Hq, Hkv, d, scale, heads=None, gscale=1.0
     f32(lse, out)
     if tuple(out.shape) != (B, S, S) or not out.is_contiguous():
         raise ValueError(f"attn_relmap: out must be a contiguous [{B}, {S}, {S}] tensor")
-    check(lib.lrp_attn_relmap(pq, pk, pv, pg, pl, p(out), M, B, S, Hq, Hkv, d, lo, hi, q.stride(0), k.stride(0), v.stride(0), g.stride(0),
-                              float(scale), float(gscale), int(causal), *_iv(row_iv, B, S), dt(q), stream()), "lrp_attn_relmap")
+    name = "lrp_attn_relmap_d256" if q.dtype == torch.bfloat16 and d == 256 else "lrp_attn_relmap"
+    check(getattr(lib, name)(pq, pk, pv, pg, pl, p(out), M, B, S, Hq, Hkv, d, lo, hi, q.stride(0), k.stride(0), v.stride(0), g.stride(0),
+                             float(scale), float(gscale), int(causal), *_iv(row_iv, B, S), dt(q), stream()), name)
     return out
 
 
