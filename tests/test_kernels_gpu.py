@@ -1,7 +1,12 @@
 """GPU parity of each HIP kernel (through the C ABI) against the oracle's closed forms /
 a plain PyTorch fp64 restatement of the same op, on seeded inputs.  fp32 kernels: normalised
 max error <= 2e-5 (fp32 MFMA is an exact fma chain; the slack is accumulation order);
-bf16 kernels: <= 2e-2 (bf16 storage rounding of inputs/outputs)."""
+bf16 kernels: <= 2e-2 (bf16 storage rounding of inputs/outputs).
+
+The dispatch edges of the GEMM / attention / RoPE / MoE kernels are in tests/test_kernel_edges_gpu.py; the encoder-family row and
+element-wise kernels (LayerNorm, stand-alone activations, softmax on materialised rows, add_bcast, eps_scale2d, the flat element-wise
+kernels past their grid cap, readout / head_seed off the vector path) have their fp64 parity net in tests/test_rowops_gpu.py --
+the goldens here run them at one shape each."""
 import math
 
 import pytest
