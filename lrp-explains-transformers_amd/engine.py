@@ -18,7 +18,8 @@ MI355X-first decisions:
   * bf16 / head_dim 128 attention reads its transposed operands out of row-major LDS tiles as well; fp32 and the other head dims keep
     head-transposed copies of q/k/v/Gho (attention.hip, `attn_t`);
   * only the last token's logits are formed (the explained logit lives there), and the LM head
-    + final norm backward is a single row per prompt.
+    + final norm backward is a single row per prompt; explain(positions=...) forms and seeds the T explained rows of each prompt
+    instead (answer-span attribution): still one forward and one backward.
 Python only sequences kernel launches on the current stream; it performs no arithmetic.
 """
 import collections
@@ -464,6 +465,85 @@ def explain_inputs(input_ids, inputs_embeds, lengths, target, vocab, max_seq, dt
             raise ValueError(f"seed must have shape ({B}, {vocab}), got {tuple(seed.shape)}")
     emb = None if inputs_embeds is None else inputs_embeds.to(device=device, dtype=dtype).reshape(B * S, -1).contiguous()
     return B, S, emb, row_iv, idx
+
+
+OBJECTIVES = ("logit", "logprob")
+
+SpanRequest = collections.namedtuple("SpanRequest", "T rows idx auto w w_each objective per_position")
+
+
+def position_request(positions, position_weights, objective, per_position, B, S, vocab, device, input_ids=None, target=None, lengths=None,
+                     seed=None, graph=False, mode="efficient", readouts=False):
+    """explain(positions=..., position_weights=..., objective=..., per_position=...) -> None without positions, else a SpanRequest, all in
+    slot order [B, T] (R = B T explained rows; row p of prompt b predicts the token after column p -- teacher forcing):
+      T;  rows int64 [R] = b S + p, the explained rows of the [B S, .] activations;  idx int32 [R], the explained vocabulary indices --
+      target [B, T], else input_ids[b, p + 1] for p < S - 1;  auto int64 [n], the slots with p = S - 1 and no target (the caller fills them
+      with the row's arg-max once the logits exist), or None;  w fp32 [R], the slot weights (default ones);  w_each fp32 [T, R] for
+      per_position (pass t keeps slot t's weight and zeroes the others), else None;  objective, per_position.
+    The tensors are built on the host and moved to `device` (a CPU device serves the checks).  Raises ValueError before a kernel of the model
+    runs: positions that are not [B, T] integers with T >= 1, outside [0, S), repeated within a prompt or on a pad column (< S - lengths[b]);
+    weights or target of another shape, non-finite weights, a target outside [0, vocab), no target with inputs_embeds; an unknown objective;
+    positions together with seed or graph=True; mode="explicit" (its seed is a relevance, not a gradient: no span form is defined for it);
+    per_position together with a read-out keyword (readouts); position_weights / objective / per_position without positions."""
+    if objective not in OBJECTIVES:
+        raise ValueError(f"objective must be one of {OBJECTIVES}, got {objective!r}")
+    if positions is None:
+        if position_weights is not None or per_position or objective != "logit":
+            raise ValueError("position_weights / objective / per_position need positions=...")
+        return None
+    if seed is not None:
+        raise ValueError("positions: pass either positions (with target) or seed, not both")
+    if graph:
+        raise ValueError("positions: graph=True is not supported (the explained rows are an input of the call)")
+    if mode != "efficient":
+        raise ValueError(f"positions: span targets are defined for the efficient placement only, not mode={mode!r}")
+    if per_position and readouts:
+        raise ValueError("per_position=True returns R_tok_each only; it does not combine with layer_relevance / return_G / latent / heads / "
+                         "attn_map / weights / experts")
+    try:
+        pos = torch.as_tensor(positions).cpu()
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"positions must be an integer tensor or nested list [B, T], got {positions!r}") from None
+    if pos.dim() != 2 or pos.shape[0] != B or pos.shape[1] < 1 or pos.is_floating_point() or pos.is_complex() or pos.dtype == torch.bool:
+        raise ValueError(f"positions must be integers of shape [{B}, T] with T >= 1, got {tuple(pos.shape)} {pos.dtype}")
+    pos = pos.long()
+    T = pos.shape[1]
+    if int(pos.min()) < 0 or int(pos.max()) >= S:
+        raise ValueError(f"positions must be column indices in [0, {S})")
+    if bool((pos.sort(1).values.diff(dim=1) == 0).any()):
+        raise ValueError("positions must be distinct within a prompt (point a spare slot at another column and give it weight 0)")
+    if lengths is not None:
+        first = S - torch.as_tensor(lengths).cpu().long().reshape(B, 1)
+        if bool((pos < first).any()):
+            raise ValueError("positions must lie inside the prompt's own columns (>= S - lengths[b]), not on its padding")
+    if position_weights is None:
+        w = torch.ones(B, T, dtype=torch.float32)
+    else:
+        try:
+            w = torch.as_tensor(position_weights).cpu().to(torch.float32)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"position_weights must be a float tensor [B, T], got {position_weights!r}") from None
+        if tuple(w.shape) != (B, T) or not bool(torch.isfinite(w).all()):
+            raise ValueError(f"position_weights must be finite floats of shape ({B}, {T})")
+    auto = None
+    if target is not None:
+        tgt = torch.as_tensor(target).cpu()
+        if tuple(tgt.shape) != (B, T) or tgt.is_floating_point() or int(tgt.min()) < 0 or int(tgt.max()) >= vocab:
+            raise ValueError(f"target must hold vocabulary indices in [0, {vocab}) of shape ({B}, {T}), one per position")
+        idx = tgt.long()
+    else:
+        if input_ids is None:
+            raise ValueError("positions with inputs_embeds needs target [B, T] (there are no next-token ids to default to)")
+        ids = torch.as_tensor(input_ids).cpu().long().reshape(B, S)
+        idx = torch.gather(ids, 1, (pos + 1).clamp(max=S - 1))          # (p = S - 1: a placeholder until the arg-max is known)
+        slots = torch.nonzero((pos == S - 1).reshape(-1))[:, 0]
+        auto = slots.to(device) if slots.numel() else None
+    rows = (torch.arange(B)[:, None] * S + pos).reshape(-1)
+    w_each = None
+    if per_position:
+        w_each = (torch.eye(T, dtype=torch.float32)[:, None, :] * w[None]).reshape(T, B * T).contiguous().to(device)
+    return SpanRequest(T, rows.to(device), idx.reshape(-1).to(torch.int32).contiguous().to(device), auto, w.reshape(-1).contiguous().to(device),
+                       w_each, objective, bool(per_position))
 
 
 LATENT = ("trace", "resid", "mlp")
@@ -985,9 +1065,10 @@ class LlamaLRP:
         self._arena = Arena(self.device, self.dtype)
         self._graphs.clear()
 
-    def forward(self, emb, B, S, row_iv=None, keep_m=False):
+    def forward(self, emb, B, S, row_iv=None, keep_m=False, rows=None):
         """keep_m: every dense layer's m (the down projection's input) in a buffer of its own, ("m", li), for the latent "mlp" read-out;
-        the arithmetic is the same, only where m lands changes"""
+        the arithmetic is the same, only where m lands changes.  rows int64 [R] (explain(positions=...)): the explained rows of the
+        [B S, .] activations in place of each prompt's last one; the top layer then runs dense like every other layer"""
         c = self.cfg
         H, I, d, nq, nk = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"]
         M = B * S
@@ -997,7 +1078,7 @@ class LlamaLRP:
         ar = self._arena
         stash = []
         h_prev, branch = emb, None
-        last = torch.arange(B, device=dev) * S + (S - 1)
+        last = torch.arange(B, device=dev) * S + (S - 1) if rows is None else rows
         coef = self._gated_coef(M)
         explicit = self.mode == "explicit"
         nf = self._norm_fused(M, fwd_only=True) and ops.norm_fusion_part("fwd")          # K1n: the two norms + residual sums of a layer inside the GEMM epilogues around them
@@ -1006,7 +1087,7 @@ class LlamaLRP:
         for li, Lw in enumerate(self.layers):
             self._load_layer(li)
             st = {}
-            top = self.sparse_top and li == nL - 1
+            top = self.sparse_top and li == nL - 1 and rows is None
             if ready is not None:
                 st["h"], st["rstd1"] = ready
                 ready = None
@@ -1073,9 +1154,25 @@ class LlamaLRP:
 
     def _head_bwd(self, fw, idx, B, seed, layer_relevance):
         """LM head eps rule + final-norm identity rule on the single explained row of each prompt, then add2 at h_L = h1 + dn and the eps scale
-        of the last down_proj, still one row per prompt -> (Gh_last, Gs_last, A_last, rel_last or None)"""
+        of the last down_proj, still one row per prompt -> (Gh_last, Gs_last, A_last, rel_last or None).  fw["span"] (explain(positions=...)):
+        the same on the R = B T explained rows, seeded by lrp_span_seed"""
         E, H, dev, dt, ar = self.eps, self.cfg["hidden"], self.device, self.dtype, self._arena
-        if seed is None:
+        span = fw.get("span")
+        if span is not None:
+            # R = B T explained rows in slot order (B below is R): lrp_span_seed leaves logit / logprob, the row scale w (*) rstd_f of the one-hot
+            # route ("logit"), or the dense seed w (delta - softmax) in the engine dtype ("logprob": the route of seed=, without its casts)
+            B = fw["last"].shape[0]
+            dense = span["objective"] == "logprob"
+            sd = ar.new("span_seed", B, self.lm_head.shape[0]) if dense else None
+            span["logit"], span["logprob"], rs, _ = ops.span_seed(fw["logits"], idx, span["w"], fw["rstd_f"], span["objective"], seed=sd,
+                                                                  logit=ar.f32("span_logit", B), logprob=ar.f32("span_logprob", B),
+                                                                  rs=ar.f32("span_rs", B))
+            if dense:
+                g_xn = ops.linear_dgrad(sd, self.lm_head, out_dtype=torch.float32)
+                Gh_last = ops.head_norm_bwd(g_xn, self.norm, fw["rstd_f"], ar.new("Gh_last", B, H))
+            else:
+                Gh_last = ops.head_seed(self.lm_head, fw["logits"], idx, self.norm, rs, ar.new("Gh_last", B, H), 0.0, E["lin"])
+        elif seed is None:
             Gh_last = ops.head_seed(self.lm_head, fw["logits"], idx, self.norm, fw["rstd_f"], ar.new("Gh_last", B, H), 0.0, E["lin"])
         else:
             # dense seed over the last-position logits (contrastive explanations): gradient in efficient mode, relevance
@@ -1109,7 +1206,7 @@ class LlamaLRP:
         nL, lat = len(self.layers), {}
         if "resid" in latent:          # index L: the head's explained rows, the gradient rel_last is formed from (S = 1)
             lat["R_resid"] = torch.empty(nL + 1, B, H, device=dev, dtype=torch.float32)
-            ops.colsum_dot(fw["hL_last"], Gh_last, B, 1, out=lat["R_resid"][nL])
+            ops.colsum_dot(fw["hL_last"], Gh_last, B, fw["last"].shape[0] // B, out=lat["R_resid"][nL])      # (a prompt's explained rows, in slot order)
         if "mlp" in latent:
             lat["R_mlp"] = torch.empty(nL, B, I, device=dev, dtype=torch.float32)
         last, row_iv = fw["last"], fw["row_iv"]
@@ -1306,13 +1403,29 @@ class LlamaLRP:
         return WeightSink(req, self.cfg, self.device, prev)
 
     def _run(self, input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, latent=frozenset(), heads=frozenset(), attn_map=(False, ()),
-             weights=((), ()), weights_out=None, **opts):
+             weights=((), ()), weights_out=None, span=None, **opts):
         """forward + backward + read-out on the current stream: library launches only, no host synchronisation (capturable); opts: further
-        keywords of a subclass's forward / backward (Qwen3MoeLRP: experts)"""
+        keywords of a subclass's forward / backward (Qwen3MoeLRP: experts); span: a SpanRequest (explain(positions=...))"""
         if emb is None:
             emb = self.embed.index_select(0, input_ids.reshape(-1))
         wsink = self._weight_sink(weights, weights_out) if weights[0] else None
-        fw = self.forward(emb, B, S, row_iv, keep_m="mlp" in latent or "down" in weights[0], **opts)
+        fw = self.forward(emb, B, S, row_iv, keep_m="mlp" in latent or "down" in weights[0], **opts, **({} if span is None else dict(rows=span.rows)))
+        if span is not None:
+            idx = span.idx
+            if span.auto is not None:          # the slots at column S - 1 without a target: that row's arg-max (a row copy, no arithmetic)
+                idx.index_copy_(0, span.auto, ops.argmax_rows(fw["logits"])[0].index_select(0, span.auto))
+            fw["span"] = dict(w=span.w, objective=span.objective)
+        if span is not None and span.per_position:
+            # T backward passes over the SAME forward state, pass t seeded at slot t alone (the other slots' weights are 0, so their rows of
+            # the gradient are exactly 0): the backward writes temporaries and gradient buffers only, never a buffer the forward stashed
+            each = torch.empty(B, span.T, S, device=self.device, dtype=torch.float32)
+            for t in range(span.T):
+                fw["span"]["w"] = span.w_each[t]
+                G, _, _ = self.backward(fw, emb, idx, B, S)
+                each[:, t] = ops.readout(emb, G).view(B, S)
+            fw["span"]["w"] = span.w          # (logit / logprob do not depend on the weights; one more head pass is not run for them)
+            return dict(idx=idx.view(B, span.T), logit=fw["span"]["logit"].view(B, span.T).clone(),
+                        logprob=fw["span"]["logprob"].view(B, span.T).clone(), R_tok_each=each, R_tok=each.sum(1))
         if idx is None:
             # (a dense seed explains no single logit; idx / logit then report the arg-max for convenience)
             idx, _ = ops.argmax_rows(fw["logits"])
@@ -1327,9 +1440,19 @@ class LlamaLRP:
         if wsink is not None:
             opts = dict(opts, weights=wsink)
         G, layer_R, lat = self.backward(fw, emb, idx, B, S, layer_relevance or "trace" in latent, seed=seed, latent=latent, heads=hs, attn_map=am, **opts)
-        out = explanation(emb, G, idx, fw["logits"], B, S, return_G)
+        if span is None:
+            out = explanation(emb, G, idx, fw["logits"], B, S, return_G)
+        else:          # (no logits: R V fp32 is hundreds of MB at a 128 k vocabulary)
+            out = dict(idx=idx.view(B, span.T), logit=fw["span"]["logit"].view(B, span.T).clone(),
+                       logprob=fw["span"]["logprob"].view(B, span.T).clone(), R_tok=ops.readout(emb, G).view(B, S))
+            if return_G:
+                out["G_emb"], out["emb"] = G.view(B, S, -1).clone(), emb.view(B, S, -1)
+        if span is not None and (layer_relevance or "trace" in latent):
+            # the head's rows, one per explained row, at their columns (distinct rows: a copy, exactly 0 elsewhere); a prompt's sum is then the
+            # same fixed-order row sum as every other layer's, and R_trace[L].sum(-1) IS layer_R[L]
+            head_rows = torch.zeros(B * S, device=self.device, dtype=torch.float32).index_copy_(0, span.rows, layer_R[0]).view(B, S)
         if layer_relevance:
-            rows = [layer_R[0]] + [r.view(B, S).sum(1) for r in layer_R[1:]]
+            rows = [head_rows.sum(1) if span is not None else layer_R[0]] + [r.view(B, S).sum(1) for r in layer_R[1:]]
             out["layer_R"] = torch.stack(rows[::-1], 0)          # [L+1, B], index 0 = embedding
         if "trace" in latent:
             # the per-token rows layer_R sums: index l = the input of layer l (l = 0: R_tok itself), index L = the head's explained rows
@@ -1338,7 +1461,10 @@ class LlamaLRP:
             trace[0] = out["R_tok"]
             for li in range(1, nL):
                 trace[li] = layer_R[nL - li].view(B, S)
-            trace[nL, :, S - 1] = layer_R[0]
+            if span is None:
+                trace[nL, :, S - 1] = layer_R[0]
+            else:
+                trace[nL] = head_rows
             out["R_trace"] = trace
         out.update(lat)
         if hs is not None:
@@ -1356,7 +1482,8 @@ class LlamaLRP:
 
     @torch.no_grad()
     def explain(self, input_ids=None, inputs_embeds=None, target=None, layer_relevance=False, return_G=False, lengths=None,
-                seed=None, graph=False, latent=None, heads=None, attn_map=None, weights=None, weight_layers=None, weights_out=None):
+                seed=None, graph=False, latent=None, heads=None, attn_map=None, weights=None, weight_layers=None, weights_out=None,
+                positions=None, position_weights=None, objective="logit", per_position=False):
         """input_ids [B,S] (or inputs_embeds [B,S,H]); target: None (arg-max of the last position) or
         int tensor [B].  Returns dict(idx [B], logit [B], R_tok [B,S] fp32, and optionally
         layer_R [L+1, B] (sum_h h (*) G_h at every residual-stream boundary) and G_emb [B,S,H]).
@@ -1389,19 +1516,39 @@ class LlamaLRP:
         HF order (qkv = q_proj | k_proj | v_proj rows, gate_up = gate_proj rows then up_proj rows), and weight_layers, the layer list.
         weight_layers: ascending layer indices (default: all -- at the 8B shape all four matrices of 32 layers are ~28 GB of fp32).
         weights_out: a previous call's R_W; this call's values are added to it in place and it is returned (dataset-level accumulation).
-        Efficient placement only, no graph=True; nothing else changes with it."""
+        Efficient placement only, no graph=True; nothing else changes with it.
+        positions (optional): int [B, T], T >= 1 -- answer-span attribution: T explained rows per prompt in ONE forward
+        and ONE backward.  Entries are distinct column indices of the prompt's own columns (>= S - lengths[b]); row p predicts the token after
+        column p (teacher forcing).  target is then [B, T]; its default is input_ids[b, p + 1], and the row's arg-max for p = S - 1 (required
+        with inputs_embeds).  position_weights: fp32 [B, T], default ones; the explained scalar is sum_t w[b, t] f(b, t) (1 / T: a mean; 0:
+        a spare slot of a shorter answer -- point it at any other valid column, it contributes exactly 0).  objective: "logit",
+        f = logits[b, p, tgt], or "logprob", f = log_softmax(logits[b, p])[tgt] (seed delta - softmax over the row's logits).
+        Returns idx, logit, logprob (all [B, T], both objectives) and R_tok [B, S], the relevance of the weighted sum; `logits` is not
+        returned.  R_tok is exactly 0 at pads and at every column above max(positions[b]).  Every read-out keyword keeps working (they read
+        the backward, which only sees another seed): R_trace[L] is non-zero at the explained columns, layer_R[L] and R_resid[L] sum over a
+        prompt's explained rows.  The sparse top layer is not used for such a call.
+        per_position=True: one forward, then T backward passes over the same forward state, pass t seeded at slot t alone -> additionally
+        R_tok_each [B, T, S] fp32, the answer x prompt map, and R_tok = R_tok_each.sum(1); no read-out keyword with it.
+        Efficient placement only; not with seed or graph=True (ValueError, as for every bad position, weight, target or objective, raised
+        before a kernel of the model runs).  Without positions nothing changes."""
         wr = weight_request(weights, weight_layers, weights_out, self.cfg, len(getattr(self, "layers", ())), self.dtype,
                             getattr(self, "mode", "efficient"), graph)
         am = attn_map_request(attn_map, len(getattr(self, "layers", ())), self.cfg.get("n_heads", 0), self.cfg.get("head_dim"), self.dtype,
                               getattr(self, "mode", "efficient"))
         hd = head_request(heads, self.cfg.get("head_dim"), self.dtype)
         lat = latent_request(latent, self.cfg["hidden"], self.cfg["inter"], self.dtype)
+        nb, ns = (input_ids.shape if inputs_embeds is None else inputs_embeds.shape[:2]) if positions is not None else (0, 0)
+        span = position_request(positions, position_weights, objective, per_position, nb, ns, self.cfg["vocab"], getattr(self, "device", None),
+                                input_ids if inputs_embeds is None else None, target, lengths, seed, graph, getattr(self, "mode", "efficient"),
+                                bool(layer_relevance or return_G or latent or heads or attn_map or weights))
+        if span is not None:
+            target = None          # (checked and converted above; explain_inputs sees the plain form)
         B, S, emb, row_iv, idx = explain_inputs(input_ids, inputs_embeds, lengths, target, self.cfg["vocab"], self.max_seq, self.dtype,
                                                 self.device, seed)
         if inputs_embeds is None:
             input_ids = input_ids.to(self.device)
         if not graph:
-            return self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, lat, hd, am, wr, weights_out)
+            return self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, lat, hd, am, wr, weights_out, span=span)
         if emb is not None or lengths is not None or seed is not None or return_G:
             raise ValueError("graph=True takes input_ids only (no inputs_embeds / lengths / seed / return_G)")
         return self._graphs((B, S, idx is not None, bool(layer_relevance), self.mode, tuple(sorted(lat)), tuple(sorted(hd)), am),

@@ -365,12 +365,12 @@ class Qwen3MoeLRP(Q.QwenLRP):
         return hit
 
     # ---------------------------------------------------------------------------------------------
-    def forward(self, emb, B, S, row_iv=None, keep_m=False, experts=False):
-        """experts: every sparse block's output is kept for the R_block read-out of the backward"""
+    def forward(self, emb, B, S, row_iv=None, keep_m=False, experts=False, rows=None):
+        """experts: every sparse block's output is kept for the R_block read-out of the backward; rows: LlamaLRP.forward's"""
         c, ar = self.cfg, self._arena
         H, I, d, nq, nk, eps = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"], c["rms_eps"]
         M, nqk, nqkv, scale = B * S, (nq + nk) * d, (nq + 2 * nk) * d, d ** -0.5
-        last = torch.arange(B, device=self.device) * S + (S - 1)
+        last = torch.arange(B, device=self.device) * S + (S - 1) if rows is None else rows
         fa, coef = self._attn_fused(M), self._gated_coef(M)
         stash, h_prev, branch = [], emb, None
         for li, Lw in enumerate(self.layers):
@@ -438,7 +438,7 @@ class Qwen3MoeLRP(Q.QwenLRP):
         nL, lat = len(self.layers), {}
         if "resid" in latent:
             lat["R_resid"] = torch.empty(nL + 1, B, H, device=dev, dtype=torch.float32)
-            ops.colsum_dot(fw["hL_last"], Gh_last, B, 1, out=lat["R_resid"][nL])
+            ops.colsum_dot(fw["hL_last"], Gh_last, B, fw["last"].shape[0] // B, out=lat["R_resid"][nL])
         if experts:      # (dense layers: exactly 0 / -1)
             lat["R_expert"] = torch.zeros(nL, B, Ne, device=dev, dtype=torch.float32)
             lat["R_block"] = torch.zeros(nL, B, device=dev, dtype=torch.float32)
@@ -532,7 +532,7 @@ class Qwen3MoeLRP(Q.QwenLRP):
     @torch.no_grad()
     def explain(self, input_ids=None, inputs_embeds=None, target=None, layer_relevance=False, return_G=False, lengths=None, seed=None,
                 graph=False, latent=None, heads=None, attn_map=None, experts=False, weights=None, moe_weights=None, weight_layers=None,
-                weights_out=None):
+                weights_out=None, positions=None, position_weights=None, objective="logit", per_position=False):
         """LlamaLRP.explain for Qwen3-MoE (same arguments and outputs), with
         experts=True: two more outputs -- R_expert [L, B, E] fp32, the relevance of every expert of every layer per prompt (`routing_weights *
         routing_weights.grad` scattered by expert, summed over the prompt's tokens; rows of dense layers are exactly 0, pad tokens contribute
@@ -551,7 +551,9 @@ class Qwen3MoeLRP(Q.QwenLRP):
         Efficient placement only, no graph=True; moe_weights=None launches nothing and every other output is bitwise what it is without it.
         Not part of it: the MLP matrices of dense (mlp_only_layers) layers, the monkey_patch drop-in, expert-parallel multi-GPU.
         Not served: latent="mlp" (a sparse layer has no single MLP), graph=True and weights= (LlamaLRP / QwenLRP's keyword: its names, shapes
-        and layer lists are not this model's -- use moe_weights=) -- all raise ValueError."""
+        and layer lists are not this model's -- use moe_weights=) -- all raise ValueError.
+        positions / position_weights / objective / per_position: LlamaLRP.explain's answer-span attribution, the same
+        arguments, outputs and refusals; experts= and moe_weights= keep working with it (per_position=True takes no read-out keyword)."""
         if weights is not None:
             raise ValueError("Qwen3MoeLRP: weights= (per-weight relevance) is not supported for a model with routed experts; use moe_weights=")
         wr = moe_weight_request(moe_weights, weight_layers, weights_out, self.cfg, self.dtype, getattr(self, "mode", "efficient"), graph)
@@ -564,11 +566,17 @@ class Qwen3MoeLRP(Q.QwenLRP):
         am = E.attn_map_request(attn_map, len(self.layers), self.cfg["n_heads"], self.cfg["head_dim"], self.dtype, self.mode)
         hd = E.head_request(heads, self.cfg["head_dim"], self.dtype)
         lat = E.latent_request(latent, self.cfg["hidden"], self.cfg["inter"], self.dtype)
+        nb, ns = (input_ids.shape if inputs_embeds is None else inputs_embeds.shape[:2]) if positions is not None else (0, 0)
+        span = E.position_request(positions, position_weights, objective, per_position, nb, ns, self.cfg["vocab"], getattr(self, "device", None),
+                                  input_ids if inputs_embeds is None else None, target, lengths, seed, graph, getattr(self, "mode", "efficient"),
+                                  bool(layer_relevance or return_G or latent or heads or attn_map or weights or moe_weights or experts))
+        if span is not None:
+            target = None
         B, S, emb, row_iv, idx = E.explain_inputs(input_ids, inputs_embeds, lengths, target, self.cfg["vocab"], self.max_seq, self.dtype,
                                                   self.device, seed)
         if inputs_embeds is None:
             input_ids = input_ids.to(self.device)
-        out = self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, lat, hd, am, wr, weights_out, experts=bool(experts))
+        out = self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, lat, hd, am, wr, weights_out, span=span, experts=bool(experts))
         if wr[0]:
             out["weight_layers_moe"] = list(wr[2])
         return out

@@ -1072,6 +1072,47 @@ def head_seed(W_lm, logits, idx, w_norm, rstd_last, out, w_offset=0.0, eps_lin=0
     return out
 
 
+SPAN_OBJECTIVES = {"logit": 0, "logprob": 1}          # LRP_SPAN_LOGIT / LRP_SPAN_LOGPROB (include/lrp_hip_span.h)
+
+
+def span_seed(logits, idx, w=None, rstd=None, objective="logit", seed=None, seed_dtype=None, logit=None, logprob=None, rs=None):
+    """the head seed of an answer-span explanation, one launch over the R explained rows of fp32 logits [R, V] (unit column stride, any row
+    pitch): -> (logit [R] = l[idx] bitwise, logprob [R] = log_softmax(l)[idx], rs = w (*) rstd or None, seed or None).  idx [R] int32 in
+    [0, V); w [R] fp32 (None: ones); rstd [R] fp32: rs is formed when it is given.  objective="logprob": seed [R, V] =
+    w (delta(j, idx) - softmax(l)_j) in seed_dtype (float32 / bfloat16; or pass the buffer), rounded once; "logit": no dense seed.
+    Fixed-order fp32 sums, bitwise repeatable, a row's result depends on that row only."""
+    if objective not in SPAN_OBJECTIVES:
+        raise ValueError(f"span_seed: objective must be one of {sorted(SPAN_OBJECTIVES)}, got {objective!r}")
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError(f"span_seed: logits {tuple(logits.shape)} must be [R, V] with contiguous rows")
+    R, V = logits.shape
+    pl = p(logits)                      # (device tensors only: raises before anything is allocated)
+    f32(logits, w, rstd, logit, logprob, rs)
+    if idx.dtype != torch.int32 or idx.numel() != R or not idx.is_contiguous():
+        raise TypeError(f"span_seed: idx must be a contiguous int32 [{R}] tensor")
+    for name, t in (("w", w), ("rstd", rstd), ("logit", logit), ("logprob", logprob), ("rs", rs)):
+        if t is not None and (t.numel() != R or not t.is_contiguous()):
+            raise ValueError(f"span_seed: {name} must be a contiguous [{R}] tensor")
+    new = lambda: torch.empty(R, device=logits.device, dtype=torch.float32)      # noqa: E731
+    logit, logprob = new() if logit is None else logit, new() if logprob is None else logprob
+    if rstd is not None and rs is None:
+        rs = new()
+    ld_seed = sdt = 0
+    if objective == "logprob":
+        if seed is None:
+            seed = torch.empty(R, V, device=logits.device, dtype=seed_dtype or torch.float32)
+        if tuple(seed.shape) != (R, V) or seed.stride(1) != 1 or seed.device != logits.device:
+            raise ValueError(f"span_seed: seed must be a [{R}, {V}] tensor with contiguous rows on {logits.device}")
+        ld_seed, sdt = seed.stride(0) if R > 1 else max(seed.stride(0), V), dt(seed)
+    else:
+        seed = None
+    if R == 0:                          # (empty tensors have no address to hand over)
+        return logit, logprob, rs, seed
+    check(lib.lrp_span_seed(pl, logits.stride(0) if R > 1 else max(logits.stride(0), V), p(idx), p(w), p(rstd), R, V, SPAN_OBJECTIVES[objective],
+                            p(seed), ld_seed, sdt, p(logit), p(logprob), p(rs), stream()), "lrp_span_seed")
+    return logit, logprob, rs, seed
+
+
 SMALLM_MAX = 16          # rows the W-streaming small-M kernels serve (above: the skinny split-K path, then the MFMA GEMM)
 
 
