@@ -19,7 +19,9 @@ MI355X-first decisions:
     head-transposed copies of q/k/v/Gho (attention.hip, `attn_t`);
   * only the last token's logits are formed (the explained logit lives there), and the LM head
     + final norm backward is a single row per prompt; explain(positions=...) forms and seeds the T explained rows of each prompt
-    instead (answer-span attribution): still one forward and one backward.
+    instead (answer-span attribution, DESIGN.md section 20): still one forward and one backward;
+  * explain() keeps no KV cache (it needs every activation of the forward); generate(), forward only, has one and produces the model's own
+    answer on the same resident weights for explain_generated() to explain.
 Python only sequences kernel launches on the current stream; it performs no arithmetic.
 """
 import collections
@@ -465,6 +467,55 @@ def explain_inputs(input_ids, inputs_embeds, lengths, target, vocab, max_seq, dt
             raise ValueError(f"seed must have shape ({B}, {vocab}), got {tuple(seed.shape)}")
     emb = None if inputs_embeds is None else inputs_embeds.to(device=device, dtype=dtype).reshape(B * S, -1).contiguous()
     return B, S, emb, row_iv, idx
+
+
+def generate_request(input_ids, inputs_embeds, max_new_tokens, lengths, eos_token_id, pad_token_id, vocab, max_seq):
+    """The checks in front of generate(); every ValueError is raised before a kernel runs.  -> (ids int64 [B, S] on the host, lens int64 [B] on
+    the host, eos: list of ints (empty: no stopping), pad: int or None (only a finished prompt is ever fed it))"""
+    if inputs_embeds is not None or input_ids is None:
+        raise ValueError("generate takes input_ids: every new token is fed back through the embedding table, inputs_embeds have no ids to continue")
+    try:
+        ids = torch.as_tensor(input_ids).cpu()
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"input_ids must be an integer tensor [B, S], got {input_ids!r}") from None
+    if ids.dim() != 2 or ids.shape[0] < 1 or ids.shape[1] < 1 or ids.is_floating_point() or ids.dtype == torch.bool:
+        raise ValueError(f"input_ids must be integers of shape [B, S], got {tuple(ids.shape)} {ids.dtype}")
+    ids = ids.long()
+    B, S = ids.shape
+    if int(ids.min()) < 0 or int(ids.max()) >= vocab:
+        raise ValueError(f"input_ids must hold vocabulary indices in [0, {vocab})")
+    if isinstance(max_new_tokens, bool) or not isinstance(max_new_tokens, int) or max_new_tokens < 1:
+        raise ValueError(f"max_new_tokens must be an integer >= 1, got {max_new_tokens!r}")
+    if S + max_new_tokens > max_seq:
+        raise ValueError(f"S + max_new_tokens = {S + max_new_tokens} exceeds max_seq={max_seq} (the RoPE tables and the cache end there)")
+    if lengths is None:
+        lens = torch.full((B,), S, dtype=torch.long)
+    else:
+        try:
+            lens = torch.as_tensor(lengths).cpu()
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError(f"lengths must be {B} integers, got {lengths!r}") from None
+        if lens.numel() != B or lens.is_floating_point() or lens.dtype == torch.bool or int(lens.min()) < 1 or int(lens.max()) > S:
+            raise ValueError(f"lengths must be {B} integers in [1, {S}]")
+        lens = lens.long().reshape(B)
+
+    def token(name, t):
+        if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < vocab:
+            raise ValueError(f"{name} must be a vocabulary index in [0, {vocab}), got {t!r}")
+        return t
+
+    if eos_token_id is None:
+        eos = []
+    elif isinstance(eos_token_id, (list, tuple)):
+        if not eos_token_id:
+            raise ValueError("eos_token_id: an empty list stops nothing (pass None)")
+        eos = [token("eos_token_id", t) for t in eos_token_id]
+    else:
+        eos = [token("eos_token_id", eos_token_id)]
+    pad = None if pad_token_id is None else token("pad_token_id", pad_token_id)
+    if pad is None and eos:
+        pad = eos[0]
+    return ids, lens, eos, pad
 
 
 OBJECTIVES = ("logit", "logprob")
@@ -1553,3 +1604,138 @@ class LlamaLRP:
             raise ValueError("graph=True takes input_ids only (no inputs_embeds / lengths / seed / return_G)")
         return self._graphs((B, S, idx is not None, bool(layer_relevance), self.mode, tuple(sorted(lat)), tuple(sorted(hd)), am),
                             lambda ids, idx_: self._run(ids, None, B, S, None, idx_, layer_relevance, False, None, lat, hd, am), input_ids, idx)
+
+    # --------------------------------------------------------------------------------------------- generation
+    def _decode_step(self, tok, pos, lo, kc, vc, ws):
+        """one new token per prompt through every layer on B rows: the sparse top layer's launch sequence (embedding rows, norm, qkv, o
+        projection, norm, gated MLP, down projection: the weight-streaming Linears), with lrp_decode_rope_append and lrp_attn_decode in place of
+        RoPE and attention.  tok int64 [B] and pos int32 [1] (the column the token sits at) are device INPUTS of the step; nothing is
+        incremented inside it, so running it again writes the same cache rows with the same values (what GraphCache's warm-up + capture do).
+        kc, vc [L, B, cap, nk d];  lo int32 [B].  -> (logits [B, V] fp32, idx int32 [B] their arg-max); launches only, capturable"""
+        c = self.cfg
+        H, I, d, nq, nk, eps = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"], c["rms_eps"]
+        B, ar, nqk = tok.shape[0], self._arena, (nq + nk) * d
+        h, branch = self.embed.index_select(0, tok), None
+        for li, Lw in enumerate(self.layers):
+            self._load_layer(li)          # (weight_format="mxfp4": one dequantisation of the layer per token -- the price of one scratch layer)
+            x, rstd = ar.new("dec_x", B, H), ar.f32("dec_rstd", B)
+            if branch is None:
+                ops.add_rmsnorm_fwd(h, None, Lw["ln1"], eps, y=x, rstd=rstd)
+            else:
+                hs = ar.new("dec_h", B, H)
+                ops.add_rmsnorm_fwd(h, branch, Lw["ln1"], eps, hsum_out=hs, y=x, rstd=rstd)
+                h = hs
+            qkv, qkn = ops.linear_fwd(x, Lw["wqkv"], Lw.get("bqkv"), out=ar.new("dec_qkv", B, nqk + nk * d)), self._qk_norm(Lw)
+            qk = qkv[:, :nqk]
+            if qkn is not None:
+                qk = ar.new("dec_qkn", B, nqk)
+                ops.head_rmsnorm_fwd(qkv[:, : nq * d], qkn[0], qk[:, : nq * d], ar.f32("dec_rstd_q", B * nq), nq, d, eps)
+                ops.head_rmsnorm_fwd(qkv[:, nq * d: nqk], qkn[1], qk[:, nq * d:], ar.f32("dec_rstd_k", B * nk), nk, d, eps)
+            q = ops.decode_rope_append(qk, qkv[:, nqk:], self.cos, self.sin, pos, ar.new("dec_q", B, nq * d), kc[li], vc[li], nq, nk, d)
+            o = ops.attn_decode(q, kc[li], vc[li], lo, pos, nq, nk, d, self.meta[-1], out=ar.new("dec_o", B, nq * d), ws=ws)
+            a = self._lin_fwd(o, Lw["wo"], ar.new("dec_a", B, H))
+            h1 = ar.new("dec_h1", B, H)
+            x2, _ = ops.add_rmsnorm_fwd(h, a, Lw["ln2"], eps, hsum_out=h1, y=x, rstd=rstd)
+            _, m = ops.gemm_gated_fwd(x2, Lw["wgu"], ar.new("dec_gu", B, 2 * I), ar.new("dec_m", B, I), self.act)
+            h, branch = h1, self._lin_fwd(m, Lw["wd"], ar.new("dec_dn", B, H))
+        logits = head_fwd(ar, h, branch, True, tok, self.norm, self.lm_head, eps)["logits"]      # (top form: one row per prompt already)
+        return logits, ops.argmax_rows(logits)[0]
+
+    @torch.no_grad()
+    def generate(self, input_ids=None, max_new_tokens=1, lengths=None, eos_token_id=None, pad_token_id=None, graph=False, return_logits=False,
+                 inputs_embeds=None, force_tokens=None):
+        """Greedy continuation of input_ids [B, S] on the resident weights, forward only, with a KV cache:
+        -> dict(sequences int64 [B, S + T'], new_tokens int64 [B, T'], n_new int64 [B], logit / logprob fp32 [B, T'] = the step's logit and
+        log-probability of new_tokens[b, t], lengths int64 [B] = the input lengths + T'[, logits fp32 [B, T', V] with return_logits]).
+        The prefill is the forward explain() runs; every layer's rotated K and its V are copied into caches [L, B, cap, nk d] of the arena,
+        cap = S + max_new_tokens <= max_seq.  The first new token is the arg-max (lrp_argmax_rows, the one explain() takes its default target
+        from) of the prefill's logits; each further one costs one _decode_step.  lengths: prompts LEFT-padded to S as for explain(); the result
+        equals the un-padded single-prompt run up to rounding.
+        eos_token_id (int or list): a prompt that emits one is finished; it is fed pad_token_id (default: the first EOS id) from then on and its
+        later new_tokens are pad_token_id (logit / logprob there are those of the pad id).  n_new[b] counts the tokens up to and including the
+        EOS; the loop ends when every prompt has finished, T' = max_b n_new[b] <= max_new_tokens.  Stopping reads B flags back per token;
+        without eos_token_id nothing is read back before the end.
+        graph=True: the step is captured once per (B, cap) into a hipGraph and replayed, its token ids and its column copied into the graph's
+        static inputs before each replay; bitwise the eager result.
+        force_tokens int [B, max_new_tokens] (optional): teacher forcing -- token t of the continuation is force_tokens[b, t] in place of the
+        arg-max (logit / logprob are then the model's values of the given answer: scoring it through the cache).
+        weight_format="mxfp4" engines dequantise every layer once per token.  Greedy only: no sampling, beam search or repetition penalty.
+        ValueError before any kernel runs: inputs_embeds, max_new_tokens < 1, S + max_new_tokens > max_seq, bad lengths, an eos_token_id,
+        pad_token_id or forced token outside [0, vocab)."""
+        c = self.cfg
+        ids, lens, eos, pad = generate_request(input_ids, inputs_embeds, max_new_tokens, lengths, eos_token_id, pad_token_id, c["vocab"], self.max_seq)
+        B, S = ids.shape
+        dev, ar, L, nkd, nq, nk, d = self.device, self._arena, len(self.layers), c["n_kv"] * c["head_dim"], c["n_heads"], c["n_kv"], c["head_dim"]
+        cap = S + max_new_tokens
+        forced = None
+        if force_tokens is not None:
+            forced = torch.as_tensor(force_tokens).cpu()
+            if tuple(forced.shape) != (B, max_new_tokens) or forced.is_floating_point() or int(forced.min()) < 0 or int(forced.max()) >= c["vocab"]:
+                raise ValueError(f"force_tokens must hold vocabulary indices in [0, {c['vocab']}) of shape ({B}, {max_new_tokens})")
+            forced = forced.to(device=dev, dtype=torch.int32)
+        _, _, _, row_iv, _ = explain_inputs(ids, None, None if lengths is None else lens, None, c["vocab"], self.max_seq, self.dtype, dev)
+        ids = ids.to(dev)
+        fw = self.forward(self.embed.index_select(0, ids.reshape(-1)), B, S, row_iv)
+        kc, vc = ar.new("kcache", L, B, cap, nkd), ar.new("vcache", L, B, cap, nkd)
+        for li, st in enumerate(fw["stash"]):
+            kc[li, :, :S].copy_(st["qkr"][:, nq * d:].view(B, S, nkd))
+            vc[li, :, :S].copy_(st["qkv"][:, (nq + nk) * d:].view(B, S, nkd))
+        lo = ar.get("dec_lo", (B,), torch.int32).copy_(S - lens)
+        ws = ar.get("dec_ws", (ops.attn_decode_ws(B, nq, d, cap),), torch.uint8)
+        cols = torch.arange(S, cap, device=dev, dtype=torch.int32)          # cols[t - 1: t]: the column of step t's input token
+        if graph:
+            step = lambda tok, pos: self._graphs(("decode", B, cap, self.mode), lambda t_, p_: self._decode_step(t_, p_, lo, kc, vc, ws), tok, pos)      # noqa: E731
+        else:
+            step = lambda tok, pos: self._decode_step(tok, pos, lo, kc, vc, ws)      # noqa: E731
+        eos_t = torch.tensor(eos, device=dev, dtype=torch.int32) if eos else None
+        fin = torch.zeros(B, device=dev, dtype=torch.bool)
+        n_new = torch.zeros(B, device=dev, dtype=torch.long)
+        toks, logit, logprob, rows = [], [], [], []
+        logits, idx = fw["logits"], ops.argmax_rows(fw["logits"])[0]
+        for t in range(max_new_tokens):
+            if t:
+                logits, idx = step(toks[-1], cols[t - 1: t])
+            if forced is not None:
+                idx = forced[:, t]
+            if eos:
+                idx = torch.where(fin, torch.full_like(idx, pad), idx)          # (a copy: idx may be a graph's static output)
+            lg, lp, _, _ = ops.span_seed(logits, idx.contiguous())
+            toks.append(idx.long())
+            logit.append(lg)
+            logprob.append(lp)
+            if return_logits:
+                rows.append(logits.clone())
+            n_new += ~fin
+            if eos:
+                fin |= torch.isin(idx, eos_t)
+                if bool(fin.all()):
+                    break
+        new = torch.stack(toks, 1)
+        out = dict(sequences=torch.cat((ids, new), 1), new_tokens=new, n_new=n_new, logit=torch.stack(logit, 1), logprob=torch.stack(logprob, 1),
+                   lengths=lens.to(dev) + new.shape[1])
+        if return_logits:
+            out["logits"] = torch.stack(rows, 1)
+        return out
+
+    @torch.no_grad()
+    def explain_generated(self, input_ids=None, max_new_tokens=1, lengths=None, eos_token_id=None, pad_token_id=None, graph=False,
+                          objective="logprob", position_weights=None, **readout_kw):
+        """Prompt in, the model's own answer and its attribution out, on one resident copy of the weights: generate(), then
+        explain(sequences, lengths=out["lengths"], positions=[S - 1 .. S + T' - 2], position_weights=w, objective=objective, **readout_kw) --
+        row S - 1 + t predicts new token t, so the default targets of positions ARE the generated tokens.  w[b, t] = 1 for t < n_new[b], else 0
+        (the slots after an EOS are the zero-weight spare slots positions defines); position_weights="mean": 1 / n_new[b] instead; or an
+        explicit fp32 [B, T'].  The last column is no explained row: R_tok is exactly 0 there, as at pads.  -> explain's dict plus sequences,
+        new_tokens, n_new.  graph applies to the generation; per_position=True and every read-out keyword pass through to explain()."""
+        out = self.generate(input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph=graph)
+        new, n_new = out["new_tokens"], out["n_new"]
+        S, T = out["sequences"].shape[1] - new.shape[1], new.shape[1]
+        if position_weights is None or (isinstance(position_weights, str) and position_weights == "mean"):
+            w = (torch.arange(T, device=n_new.device)[None] < n_new[:, None]).to(torch.float32)
+            if position_weights is not None:
+                w = w / n_new[:, None].to(torch.float32)
+        else:
+            w = position_weights
+        positions = torch.arange(S - 1, S + T - 1).expand(new.shape[0], T)
+        res = self.explain(out["sequences"], lengths=out["lengths"], positions=positions, position_weights=w, objective=objective, **readout_kw)
+        res.update(sequences=out["sequences"], new_tokens=new, n_new=n_new)
+        return res

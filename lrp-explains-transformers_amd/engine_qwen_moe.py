@@ -581,6 +581,12 @@ class Qwen3MoeLRP(Q.QwenLRP):
             out["weight_layers_moe"] = list(wr[2])
         return out
 
+    def generate(self, *args, **kw):
+        raise NotImplementedError("Qwen3MoeLRP: generate() / explain_generated() serve the dense LlamaLRP / QwenLRP drivers only (the decode "
+                                  "step has no routed-expert layer); produce the answer elsewhere and pass it to explain(positions=...)")
+
+    explain_generated = generate
+
     @classmethod
     def from_hf(cls, model, **kw):
         cfg, W = weights_from_hf(model)

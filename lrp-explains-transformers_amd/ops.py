@@ -1449,6 +1449,91 @@ def gqa_reduce(x, out, rows, Hkv, rep, d):
     return out
 
 
+# ------------------------------------------------------------------------------------------- KV-cached decode (csrc/decode.hip)
+ATTN_DECODE_SLAB = int(lib.lrp_attn_decode_slab())          # keys per slab of attn_decode, counted from key 0
+
+
+def _decode_rows(name, t, what, rows, cols, ref=None):
+    if t.dim() != 2 or t.shape[0] != rows or t.shape[1] != cols or t.stride(1) != 1:
+        raise ValueError(f"{name}: {what} {tuple(t.shape)} must be [{rows}, {cols}] with contiguous rows")
+    if ref is not None:
+        same(ref, t)
+
+
+def _decode_cache(name, kc, vc, B, cols, ref):
+    """-> (cap, ldc) of the caches kc, vc [B, cap, cols]: unit column stride, one row pitch, batch stride cap * pitch"""
+    for what, t in (("kc", kc), ("vc", vc)):
+        if t.dim() != 3 or t.shape[0] != B or t.shape[2] != cols or t.shape[1] < 1 or t.stride(2) != 1 or t.shape != kc.shape \
+                or t.stride() != kc.stride() or (B > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
+            raise ValueError(f"{name}: {what} {tuple(t.shape)} / strides {t.stride()} must be [{B}, cap, {cols}] with contiguous rows, batch stride "
+                             "cap * row pitch, kc and vc alike")
+    same(ref, kc, vc)
+    return int(kc.shape[1]), int(kc.stride(1))
+
+
+def _decode_pos(name, pos, ref):
+    if pos.dtype != torch.int32 or pos.numel() != 1 or pos.device != ref.device:
+        raise TypeError(f"{name}: pos must be an int32 tensor of one element on {ref.device} (the step's column, read on the device)")
+
+
+def decode_rope_append(qk, v, cos, sin, pos, q_rot, kc, vc, nq, nk, d):
+    """one decode step's RoPE and cache append, one launch: q_rot [B, nq d] = RoPE(qk[:, : nq d]), kc[b, pos] = RoPE(qk[:, nq d:]),
+    vc[b, pos] = v, at the tables' row pos -- bitwise rope_fwd(seq=1) with cos[pos: pos + 1].  qk [B, (nq + nk) d], v [B, nk d]: 2-D views
+    with unit column stride (the two column ranges of one qkv buffer); kc, vc [B, cap, nk d]; cos / sin fp32 [rows, d] contiguous; pos:
+    device int32 [1].  A pos outside [0, cap) or past the tables writes nothing (checked on the device)."""
+    B = qk.shape[0]
+    pq = p(qk)                          # (device tensors only: raises before anything else)
+    _decode_rows("decode_rope_append", qk, "qk", B, (nq + nk) * d)
+    _decode_rows("decode_rope_append", v, "v", B, nk * d, qk)
+    _decode_rows("decode_rope_append", q_rot, "q_rot", B, nq * d, qk)
+    cap, ldc = _decode_cache("decode_rope_append", kc, vc, B, nk * d, qk)
+    _decode_pos("decode_rope_append", pos, qk)
+    f32(cos, sin)
+    if cos.dim() != 2 or cos.shape[1] != d or cos.shape != sin.shape or not cos.is_contiguous() or not sin.is_contiguous():
+        raise ValueError(f"decode_rope_append: cos / sin must be contiguous [rows, {d}] tables")
+    ld = lambda t: t.stride(0) if B > 1 else max(t.stride(0), t.shape[1])      # noqa: E731  (a one-row view's pitch is arbitrary)
+    check(lib.lrp_decode_rope_append(pq, ld(qk), p(v), ld(v), p(cos), p(sin), cos.shape[0], p(pos), p(q_rot), ld(q_rot), p(kc), p(vc), ldc, B, cap,
+                                     nq, nk, d, dt(qk), stream()), "lrp_decode_rope_append")
+    return q_rot
+
+
+def attn_decode_ws(B, Hq, d, cap):
+    """bytes of attn_decode's workspace"""
+    n = int(lib.lrp_attn_decode_ws(B, Hq, d, cap))
+    if n < 0:
+        raise ValueError(f"attn_decode: no kernel for B = {B}, Hq = {Hq}, d = {d}, cap = {cap} (d a multiple of 8, at most 256)")
+    return n
+
+
+def attn_decode(q, kc, vc, lo, pos, Hq, Hkv, d, scale, out=None, ws=None):
+    """single-query attention over a KV cache: out[b, h] = sum_{lo[b] <= j <= pos} softmax_j(scale q[b, h] . kc[b, j, h // rep]) vc[b, j, h // rep]
+    ([B, Hq d], q's dtype).  q [B, Hq d] with unit column stride; kc, vc [B, cap, Hkv d]; lo int32 [B] (clamped into [0, pos] by the kernel);
+    pos: device int32 [1].  Rows of the cache outside [lo[b], pos] are never loaded.  ws: a uint8 workspace of attn_decode_ws bytes (None:
+    ops.workspace).  Fixed-order fp32 sums over slabs of ATTN_DECODE_SLAB keys counted from key 0: bitwise repeatable, a prompt's result does
+    not depend on the batch or on cap."""
+    B = q.shape[0]
+    pq = p(q)
+    _decode_rows("attn_decode", q, "q", B, Hq * d)
+    cap, ldc = _decode_cache("attn_decode", kc, vc, B, Hkv * d, q)
+    _decode_pos("attn_decode", pos, q)
+    if lo.dtype != torch.int32 or lo.numel() != B or not lo.is_contiguous() or lo.device != q.device:
+        raise TypeError(f"attn_decode: lo must be a contiguous int32 [{B}] tensor on {q.device}")
+    if out is None:
+        out = torch.empty(B, Hq * d, device=q.device, dtype=q.dtype)
+    _decode_rows("attn_decode", out, "out", B, Hq * d, q)
+    if B == 0:
+        return out
+    need = attn_decode_ws(B, Hq, d, cap)
+    if ws is None:
+        ws = workspace(need, q)
+    elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous() or ws.device != q.device:
+        raise ValueError(f"attn_decode: ws must be a contiguous uint8 tensor of >= {need} bytes on {q.device}")
+    ld = lambda t: t.stride(0) if B > 1 else max(t.stride(0), t.shape[1])      # noqa: E731
+    check(lib.lrp_attn_decode(pq, ld(q), p(kc), p(vc), ldc, p(lo), p(pos), p(out), ld(out), p(ws), ws.numel(), B, cap, Hq, Hkv, d, float(scale),
+                              dt(q), stream()), "lrp_attn_decode")
+    return out
+
+
 # ------------------------------------------------------------------------------------------- MoE experts (csrc/moe.hip)
 class MoePlan:
     """device-side routing plan of one MoE layer (lrp_moe_plan): int32 words, nothing read back to the host"""
