@@ -578,6 +578,10 @@ int launch_stream_m(const void* x, const void* W, const void* bias, void* z, int
 
 }  // namespace
 
+// the two policies above for the kernel's quantised twin (linear_stream_q.hip): one definition, so the twin splits and blocks exactly alike
+int lrp_stream_rows_per_wave(int N) { return stream_rows_per_wave(N); }
+int lrp_stream_fwd_splits(int N, int K) { return fwd_splits(N, K); }
+
 // can lrp_linear_stream_fwd serve the problem, and is it the right kernel for it?  bf16, 1 <= M <= 128 rows (every workgroup re-reads x from
 // L2: beyond that the x traffic outgrows the weight's), K a multiple of 512 (the 8-tile ring), operands below 2^31 bytes, and enough 64-row
 // workgroups to put one on (nearly) every CU

@@ -78,22 +78,7 @@ template <> struct MxStage<float> {
     static LRP_DEVICE codes_t load(const uint8_t* p) { return *(gvec8_ptr_t)p; }
 };
 
-// the eight elements of one code word (element i in nibble i) times 2^(E - 127), as T.
-// v_cvt_scalef32_pk_{bf16,f32}_fp4: two elements per instruction (byte `sel` of the word, low nibble first); the scale operand is a float
-// whose EXPONENT FIELD is the e8m0 byte (E << 23, E = 0 included).  Verified on the device against lrp_mxfp4_dequant, bit for bit: all 16
-// codes (-0 included), E = 0 / 1 / 2 (subnormal results in both types) and an all-zero block (tests/test_moe_mxfp4_gpu.py)
-LRP_DEVICE void mx_decode8(uint32_t word, uint32_t E, bf16_t* out) {
-    const float sc = __builtin_bit_cast(float, E << 23);
-    bf16x2 v0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 0), v1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 1);
-    bf16x2 v2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 2), v3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(word, sc, 3);
-    out[0] = v0[0]; out[1] = v0[1]; out[2] = v1[0]; out[3] = v1[1]; out[4] = v2[0]; out[5] = v2[1]; out[6] = v3[0]; out[7] = v3[1];
-}
-LRP_DEVICE void mx_decode8(uint32_t word, uint32_t E, float* out) {
-    const float sc = __builtin_bit_cast(float, E << 23);
-    f32x2 v0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(word, sc, 0), v1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(word, sc, 1);
-    f32x2 v2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(word, sc, 2), v3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(word, sc, 3);
-    out[0] = v0[0]; out[1] = v0[1]; out[2] = v1[0]; out[3] = v1[1]; out[4] = v2[0]; out[5] = v2[1]; out[6] = v3[0]; out[7] = v3[1];
-}
+// (the decode itself: mx_decode8 of common.hpp)
 
 template <typename T, int AMODE, int BMODE, int EPI, int ACT, bool QB = false>
 __global__ __launch_bounds__(256) void moe_gemm_kernel(MoeGemmArgs g) {

@@ -996,15 +996,17 @@ class LlamaLRP:
         for k in MX_MATRICES:
             ops.mxfp4_quantize(Lw[k], Q[k + "_c"], Q[k + "_s"])
 
-    def _load_layer(self, li):
+    def _load_layer(self, li, only=MX_MATRICES):
         """weight_format="mxfp4": layer li's four Linears, dequantised into the scratch layer on the current stream -- in front of the layer's
         forward and of its backward, each matrix once per layer and pass (capturable: kernel launches only); nothing otherwise.  The W^T
-        copies ops.weight_t caches on a weight (fp32 parity engine, odd shapes) are keyed on the scratch: dropped at every load"""
-        if self.flat_q is None:
+        copies ops.weight_t caches on a weight (fp32 parity engine, odd shapes) are keyed on the scratch: dropped at every load.
+        only: the subset of MX_MATRICES to load (the decode step: the matrices it does not read as codes); an empty one launches nothing"""
+        if self.flat_q is None or not only:
             return
         Lw, Q = self.layers[li], self._qlayers[li]
         for k in MX_MATRICES:
-            ops.mxfp4_dequant(Q[k + "_c"], Q[k + "_s"], Lw[k])
+            if k in only:
+                ops.mxfp4_dequant(Q[k + "_c"], Q[k + "_s"], Lw[k])
         ops.clear_weight_cache(self.scratch)
 
     def weight_bytes(self):
@@ -1039,6 +1041,19 @@ class LlamaLRP:
     # one-row-per-prompt top layer and the LM head, the 256x256 ping-pong GEMM (NT forward, NN backward) for M = B*S rows
     def _lin_fwd(self, x, W, out):
         return ops.linear_fwd(x, W, out=out)
+
+    def _decode_served(self, B):
+        """the matrices of MX_MATRICES a decode step at B rows reads as codes (ops.linear_stream_fwd_q): a quantised
+        bf16 engine, and per matrix the quantised stream kernel serves the step's operand AND the scratch matrix would take the plain stream
+        kernel (ops.linear_fwd's rule), so the step's bits are those of the dequantise-then-stream path.  Every layer has the same shapes,
+        pitches and alignment: layer 0 decides.  Empty for an unquantised or fp32 engine, tiny models, B > 128"""
+        if self.flat_q is None or self.dtype != torch.bfloat16 or not self.layers or B > ops.SKINNY_MAX:
+            return frozenset()
+        c, ar = self.cfg, self._arena
+        x, o, m = ar.new("dec_x", B, c["hidden"]), ar.new("dec_o", B, c["n_heads"] * c["head_dim"]), ar.new("dec_m", B, c["inter"])
+        Lw, Q = self.layers[0], self._qlayers[0]
+        return frozenset(k for k, a in (("wqkv", x), ("wo", o), ("wgu", x), ("wd", m))
+                         if ops.linear_stream_q_ok(a, Q[k + "_c"], Q[k + "_s"]) and ops.linear_stream_ok(a, Lw[k]))
 
     def _lin_bwd(self, A, W, out):
         return ops.linear_dgrad(A, W, out=out)
@@ -1616,8 +1631,18 @@ class LlamaLRP:
         H, I, d, nq, nk, eps = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"], c["rms_eps"]
         B, ar, nqk = tok.shape[0], self._arena, (nq + nk) * d
         h, branch = self.embed.index_select(0, tok), None
+        served = self._decode_served(B)          # weight_format="mxfp4": the matrices read as codes (section 22), decided once per step shape
+        rest = tuple(k for k in MX_MATRICES if k not in served)
+
+        def lin(li, k, x, out, bias=None):
+            """the step's Linear on matrix k of layer li: on its codes where served, else on the scratch matrix _load_layer has filled"""
+            if k in served:
+                Q = self._qlayers[li]
+                return ops.linear_stream_fwd_q(x, Q[k + "_c"], Q[k + "_s"], bias, out=out)
+            return ops.linear_fwd(x, self.layers[li][k], bias, out=out)
+
         for li, Lw in enumerate(self.layers):
-            self._load_layer(li)          # (weight_format="mxfp4": one dequantisation of the layer per token -- the price of one scratch layer)
+            self._load_layer(li, rest)    # (what is not served: one dequantisation of the matrix per token -- the price of one scratch layer)
             x, rstd = ar.new("dec_x", B, H), ar.f32("dec_rstd", B)
             if branch is None:
                 ops.add_rmsnorm_fwd(h, None, Lw["ln1"], eps, y=x, rstd=rstd)
@@ -1625,7 +1650,7 @@ class LlamaLRP:
                 hs = ar.new("dec_h", B, H)
                 ops.add_rmsnorm_fwd(h, branch, Lw["ln1"], eps, hsum_out=hs, y=x, rstd=rstd)
                 h = hs
-            qkv, qkn = ops.linear_fwd(x, Lw["wqkv"], Lw.get("bqkv"), out=ar.new("dec_qkv", B, nqk + nk * d)), self._qk_norm(Lw)
+            qkv, qkn = lin(li, "wqkv", x, ar.new("dec_qkv", B, nqk + nk * d), Lw.get("bqkv")), self._qk_norm(Lw)
             qk = qkv[:, :nqk]
             if qkn is not None:
                 qk = ar.new("dec_qkn", B, nqk)
@@ -1633,11 +1658,15 @@ class LlamaLRP:
                 ops.head_rmsnorm_fwd(qkv[:, nq * d: nqk], qkn[1], qk[:, nq * d:], ar.f32("dec_rstd_k", B * nk), nk, d, eps)
             q = ops.decode_rope_append(qk, qkv[:, nqk:], self.cos, self.sin, pos, ar.new("dec_q", B, nq * d), kc[li], vc[li], nq, nk, d)
             o = ops.attn_decode(q, kc[li], vc[li], lo, pos, nq, nk, d, self.meta[-1], out=ar.new("dec_o", B, nq * d), ws=ws)
-            a = self._lin_fwd(o, Lw["wo"], ar.new("dec_a", B, H))
+            a = lin(li, "wo", o, ar.new("dec_a", B, H))
             h1 = ar.new("dec_h1", B, H)
             x2, _ = ops.add_rmsnorm_fwd(h, a, Lw["ln2"], eps, hsum_out=h1, y=x, rstd=rstd)
-            _, m = ops.gemm_gated_fwd(x2, Lw["wgu"], ar.new("dec_gu", B, 2 * I), ar.new("dec_m", B, I), self.act)
-            h, branch = h1, self._lin_fwd(m, Lw["wd"], ar.new("dec_dn", B, H))
+            gu, m = ar.new("dec_gu", B, 2 * I), ar.new("dec_m", B, I)
+            if "wgu" in served:               # (what ops.gemm_gated_fwd composes: the Linear, then the interleaved activation)
+                ops.gated_act_fwd_il(lin(li, "wgu", x2, gu), m, self.act)
+            else:
+                ops.gemm_gated_fwd(x2, Lw["wgu"], gu, m, self.act)
+            h, branch = h1, lin(li, "wd", m, ar.new("dec_dn", B, H))
         logits = head_fwd(ar, h, branch, True, tok, self.norm, self.lm_head, eps)["logits"]      # (top form: one row per prompt already)
         return logits, ops.argmax_rows(logits)[0]
 
@@ -1659,7 +1688,8 @@ class LlamaLRP:
         static inputs before each replay; bitwise the eager result.
         force_tokens int [B, max_new_tokens] (optional): teacher forcing -- token t of the continuation is force_tokens[b, t] in place of the
         arg-max (logit / logprob are then the model's values of the given answer: scoring it through the cache).
-        weight_format="mxfp4" engines dequantise every layer once per token.  Greedy only: no sampling, beam search or repetition penalty.
+        weight_format="mxfp4" bf16 engines read the layers' codes in place at B <= 128 (ops.linear_stream_fwd_q; a matrix the kernel does not
+        serve is dequantised once per token).  Greedy only: no sampling, beam search or repetition penalty.
         ValueError before any kernel runs: inputs_embeds, max_new_tokens < 1, S + max_new_tokens > max_seq, bad lengths, an eos_token_id,
         pad_token_id or forced token outside [0, vocab)."""
         c = self.cfg

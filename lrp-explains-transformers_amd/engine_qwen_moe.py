@@ -293,7 +293,7 @@ class Qwen3MoeLRP(Q.QwenLRP):
             Lw[k] = ops.MoeQuantWeight(w, self._eq_layers[li][k + "_c"], self._eq_layers[li][k + "_s"])
             del w
 
-    def _load_layer(self, li):
+    def _load_layer(self, li, only=()):
         """nothing to load: the quantised experts are read in place by the grouped GEMMs"""
 
     def weight_bytes(self):

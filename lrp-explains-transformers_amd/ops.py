@@ -1876,3 +1876,53 @@ def mxfp4_dequant(codes, scales, out):
     check(lib.lrp_mxfp4_dequant(p(codes), p(scales), p(out), rows, cols, codes.stride(0), scales.stride(0), out.stride(0), dt(out), stream()),
           name)
     return out
+
+
+def _mx_stream_operands(name, x2, codes, scales):
+    """the operands of the weight-streaming Linear on codes: device tensors, x2 a 2-D matrix, codes / scales uint8 [N, K / 2] / [N, K / 32]"""
+    for t in (x2, codes, scales):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: lrp_hip kernels need device tensors (no CPU fallback)")
+    if x2.dim() != 2 or x2.stride(1) != 1 or x2.dtype not in _DT:
+        raise ValueError(f"{name}: x must be a 2-D float32 / bfloat16 matrix with contiguous rows, got {x2.dtype} {tuple(x2.shape)}")
+    K = x2.shape[1]
+    if K < MX_BLOCK or K % MX_BLOCK or codes.dim() != 2:
+        raise ValueError(f"{name}: x is {tuple(x2.shape)}, codes {tuple(codes.shape)}; K must be a multiple of {MX_BLOCK}")
+    _mx_bytes(name, codes, "codes", codes.shape[0], K // 2, x2)
+    _mx_bytes(name, scales, "scales", codes.shape[0], K // MX_BLOCK, x2)
+
+
+STREAM_Q = True          # module attribute (A/B measurements): False = no Linear reads MXFP4 codes in place (dequantise, then the bf16 kernels)
+
+
+def linear_stream_q_ok(x2, codes, scales):
+    """does lrp_linear_stream_fwd_q (the weight-streaming forward reading MXFP4 codes / scales directly) serve z = x2 D^T?  linear_stream_ok on
+    the dequantised shape -- bf16, M <= 128 rows, K % 512 == 0, enough workgroups, the STREAM_FWD / STREAM_FWD_SPLITS switches -- and the
+    format's pitch / alignment rules"""
+    _mx_stream_operands("lrp_linear_stream_q_ok", x2, codes, scales)
+    if not STREAM_FWD or not STREAM_Q or x2.dtype != torch.bfloat16:
+        return False
+    if x2.data_ptr() % 16 or codes.data_ptr() % 16 or scales.data_ptr() % 4:
+        return False
+    M, K, N = x2.shape[0], x2.shape[1], codes.shape[0]
+    if not lib.lrp_linear_stream_q_ok(M, N, K, x2.stride(0), codes.stride(0), scales.stride(0)):
+        return False
+    return bool(STREAM_FWD_SPLITS or lib.lrp_linear_stream_fwd_splits(M, N, K) == 1)
+
+
+def linear_stream_fwd_q(x2, codes, scales, bias=None, out=None, out_dtype=None):
+    """z[M,N] = x2[M,K] @ D[N,K]^T (+ bias), D = the matrix codes / scales hold (mxfp4_dequant), in ONE launch that reads the codes: bit for
+    bit mxfp4_dequant into bf16 followed by linear_stream_fwd (include/lrp_hip_mxfp4_stream.h)"""
+    name = "lrp_linear_stream_fwd_q"
+    _mx_stream_operands(name, x2, codes, scales)
+    M, K = x2.shape
+    N = codes.shape[0]
+    if out is None:
+        out = torch.empty(M, N, device=x2.device, dtype=out_dtype or x2.dtype)
+    need = lib.lrp_linear_stream_fwd_ws(M, N, K) if STREAM_FWD_SPLITS else 0      # the plain entry's split policy: bit identity needs it
+    ws = workspace(need, x2) if need else None
+    ntk = lib.lrp_linear_stream_fwd_tickets(M, N, K) if need else 0
+    check(lib.lrp_linear_stream_fwd_q(p(x2), p(codes), p(scales), p(aux(bias, x2, N)), p(out), M, N, K, x2.stride(0), codes.stride(0),
+                                      scales.stride(0), out.stride(0), dt(x2), _DT[out.dtype], p(ws), p(tickets(ntk, x2) if ntk else None),
+                                      stream()), name)
+    return out

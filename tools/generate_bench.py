@@ -8,7 +8,9 @@
      decode steps, eager and graph=True (the prefill is timed on its own and taken off), against the floor (the bytes of the weights a step
      streams + the live K / V bytes) / 6.3 TB/s, and HF `generate` (sdpa, its own cache) on the same device at the same shape (a model of its
      own random init: timing only).
-usage: python tools/generate_bench.py [--out FILE] [--reps 30] [--layers 32] [--new 64] [--no-hf]"""
+     --weight-format mxfp4 adds the quantised engine: reading the codes in place and, on the same build, the
+     dequantise-per-token launch sequence it replaced (ops.STREAM_Q = False), alternated call by call with the bf16 engine.
+usage: python tools/generate_bench.py [--out FILE] [--reps 30] [--layers 32] [--new 64] [--no-hf] [--no-kernel] [--weight-format mxfp4]"""
 import argparse
 import os
 import statistics
@@ -87,32 +89,52 @@ def kernel_part(ops, say, reps):
                 f"{nbytes / sm / 1e6:6.3f} TB/s   [decode vs attn_fwd row, max-normalised {err:.1e}]")
 
 
-def engine_part(say, layers, new, hf):
+def engine_part(say, layers, new, hf, weight_format=None):
     import bench
     import lxt_amd.engine as E
+    from lxt_amd import ops
     cfg = dict(bench.LLAMA3_8B, n_layers=layers)
     S = 2048
-    eng = E.LlamaLRP(cfg, bench.synth_weights(cfg, "cuda", torch.bfloat16, seed=0), dtype=torch.bfloat16, mode="efficient", max_seq=S + new + 1)
     H, I, d, nq, nk, V = cfg["hidden"], cfg["inter"], cfg["head_dim"], cfg["n_heads"], cfg["n_kv"], cfg["vocab"]
-    wbytes = 2.0 * (layers * ((nq + 2 * nk) * d * H + H * nq * d + 3 * I * H) + V * H)          # the Linears of every layer + the LM head
-    say(f"LlamaLRP.generate, Llama-3-8B shape, {layers} layers, bf16, S = {S}, {new} new tokens; ms per token = (call - a 1-token call) / {new - 1}; "
-        f"weights streamed per step {wbytes / 1e9:.2f} GB")
+    W = bench.synth_weights(cfg, "cuda", torch.bfloat16, seed=0)
+    mk = lambda fmt: E.LlamaLRP(cfg, W, dtype=torch.bfloat16, mode="efficient", max_seq=S + new + 1, weight_format=fmt)      # noqa: E731
+    lin = layers * ((nq + 2 * nk) * d * H + H * nq * d + 3 * I * H)                                # elements of the Linears of every layer
+    # variants: (label, engine, ops.STREAM_Q while it runs, bytes of weights a step must read).  weight_format="mxfp4": the engine that reads the
+    # codes, the SAME build with ops.STREAM_Q = False -- the launch sequence before section 22: four dequantisations per
+    # layer and token, then the bf16 stream kernels -- on an engine (and graph cache) of its own, and the bf16 engine; alternated call by call
+    if weight_format is None:
+        variants = [("bf16", mk(None), True, 2.0 * (lin + V * H))]
+    else:
+        qb = lin * 4.25 / 8 + 2.0 * V * H
+        variants = [(f"{weight_format} codes", mk(weight_format), True, qb), (f"{weight_format} dequant per token", mk(weight_format), False, qb),
+                    ("bf16", mk(None), True, 2.0 * (lin + V * H))]
+    del W
+    say(f"LlamaLRP.generate, Llama-3-8B shape, {layers} layers, bf16, S = {S}, {new} new tokens; ms per token = (call - a 1-token call) / {new - 1}, "
+        f"medians of 3 rounds, the variants alternated inside each round")
     rows = {}
     for B in (1, 4):
         ids = torch.randint(0, V, (B, S), generator=torch.Generator().manual_seed(B)).cuda()
         kv = 2.0 * layers * B * (S + new / 2) * nk * d * 2                                       # live K and V rows, mid-way through the answer
-        floor = (wbytes + kv) / HBM * 1e3
         for graph in (False, True):
-            for _ in range(2):
-                eng.generate(ids, 3, graph=graph)
-                eng.generate(ids, new, graph=graph)
-            pre = statistics.median(wall(lambda: eng.generate(ids, 1))[0] for _ in range(3))
-            tot = statistics.median(wall(lambda: eng.generate(ids, new, graph=graph))[0] for _ in range(3))
-            per = (tot - pre) / (new - 1)
-            rows[(B, graph)] = per
-            say(f"  B {B} {'graph' if graph else 'eager'}: prefill + first token {pre:8.2f} ms, {new} tokens {tot:8.2f} ms -> {per:6.3f} ms per token; "
-                f"floor {floor:5.3f} ms ({wbytes / 1e9:.2f} GB weights + {kv / 1e9:.3f} GB K / V at 6.3 TB/s) = {floor / per:5.3f} of the step")
-    del eng
+            pre, tot = {v[0]: [] for v in variants}, {v[0]: [] for v in variants}
+            for rnd in range(5):                                                                # two warm-up rounds (capture included), three timed
+                for label, eng, sq, _ in variants:
+                    ops.STREAM_Q = sq
+                    if rnd < 2:
+                        eng.generate(ids, 3, graph=graph)
+                        eng.generate(ids, new, graph=graph)
+                    else:
+                        pre[label].append(wall(lambda: eng.generate(ids, 1))[0])
+                        tot[label].append(wall(lambda: eng.generate(ids, new, graph=graph))[0])
+            ops.STREAM_Q = True
+            for label, _, _, wbytes in variants:
+                p_, t_ = statistics.median(pre[label]), statistics.median(tot[label])
+                per, floor = (t_ - p_) / (new - 1), (wbytes + kv) / HBM * 1e3
+                rows[(label, B, graph)] = per
+                say(f"  B {B} {'graph' if graph else 'eager'} {label:28s}: prefill + first token {p_:8.2f} ms, {new} tokens {t_:8.2f} ms -> {per:6.3f} ms per "
+                    f"token; floor {floor:5.3f} ms ({wbytes / 1e9:.2f} GB weights + {kv / 1e9:.3f} GB K / V at 6.3 TB/s) = {floor / per:5.3f} of the step")
+    rows.update({(B, g): rows[("bf16", B, g)] for B in (1, 4) for g in (False, True)})
+    del variants
     torch.cuda.empty_cache()
     if not hf:
         return
@@ -144,6 +166,9 @@ def main():
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--new", type=int, default=64)
     ap.add_argument("--no-hf", action="store_true")
+    ap.add_argument("--weight-format", default=None, choices=[None, "mxfp4"], help="also run the quantised engine (codes read in place, and the "
+                    "dequantise-per-token sequence) beside the bf16 one")
+    ap.add_argument("--no-kernel", action="store_true", help="skip part 1 (lrp_attn_decode alone)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("generate_bench needs a HIP device")
@@ -157,8 +182,9 @@ def main():
             with open(a.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
 
-    kernel_part(ops, say, a.reps)
-    engine_part(say, a.layers, a.new, not a.no_hf)
+    if not a.no_kernel:
+        kernel_part(ops, say, a.reps)
+    engine_part(say, a.layers, a.new, not a.no_hf, a.weight_format)
 
 
 if __name__ == "__main__":
