@@ -518,6 +518,16 @@ def generate_request(input_ids, inputs_embeds, max_new_tokens, lengths, eos_toke
     return ids, lens, eos, pad
 
 
+def force_request(force_tokens, B, max_new_tokens, vocab, device):
+    """generate(force_tokens=...) -> None or int32 [B, max_new_tokens] on the device; ValueError before a kernel runs"""
+    if force_tokens is None:
+        return None
+    forced = torch.as_tensor(force_tokens).cpu()
+    if tuple(forced.shape) != (B, max_new_tokens) or forced.is_floating_point() or int(forced.min()) < 0 or int(forced.max()) >= vocab:
+        raise ValueError(f"force_tokens must hold vocabulary indices in [0, {vocab}) of shape ({B}, {max_new_tokens})")
+    return forced.to(device=device, dtype=torch.int32)
+
+
 OBJECTIVES = ("logit", "logprob")
 
 SpanRequest = collections.namedtuple("SpanRequest", "T rows idx auto w w_each objective per_position")
@@ -872,6 +882,57 @@ class GraphCache:
                 s.copy_(t)
         cg.replay()
         return out
+
+
+def greedy_decode(logits, step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits):
+    """the token loop of generate(), shared by the drivers: logits fp32 [B, V] of the prefill's last rows; step(tok int64 [B], pos int32 [1])
+    -> (logits, arg-max idx) of one decode step (eager or a GraphCache replay); cols int32 [max_new_tokens]: cols[t - 1: t] is the column of
+    step t's input token; ids int64 [B, S] on the device, lens int64 [B] on the host; eos / pad as generate_request returns them; forced
+    int32 [B, max_new_tokens] or None.  -> generate()'s dict.  B flags are read back per token with eos, nothing without"""
+    dev, B = ids.device, ids.shape[0]
+    eos_t = torch.tensor(eos, device=dev, dtype=torch.int32) if eos else None
+    fin = torch.zeros(B, device=dev, dtype=torch.bool)
+    n_new = torch.zeros(B, device=dev, dtype=torch.long)
+    toks, logit, logprob, rows = [], [], [], []
+    idx = ops.argmax_rows(logits)[0]
+    for t in range(max_new_tokens):
+        if t:
+            logits, idx = step(toks[-1], cols[t - 1: t])
+        if forced is not None:
+            idx = forced[:, t]
+        if eos:
+            idx = torch.where(fin, torch.full_like(idx, pad), idx)          # (a copy: idx may be a graph's static output)
+        lg, lp, _, _ = ops.span_seed(logits, idx.contiguous())
+        toks.append(idx.long())
+        logit.append(lg)
+        logprob.append(lp)
+        if return_logits:
+            rows.append(logits.clone())
+        n_new += ~fin
+        if eos:
+            fin |= torch.isin(idx, eos_t)
+            if bool(fin.all()):
+                break
+    new = torch.stack(toks, 1)
+    out = dict(sequences=torch.cat((ids, new), 1), new_tokens=new, n_new=n_new, logit=torch.stack(logit, 1), logprob=torch.stack(logprob, 1),
+               lengths=lens.to(dev) + new.shape[1])
+    if return_logits:
+        out["logits"] = torch.stack(rows, 1)
+    return out
+
+
+def generated_span(out, position_weights):
+    """generate()'s dict -> (positions [B, T'], weights) of explain_generated(): the rows S - 1 .. S + T' - 2 that predict the new tokens;
+    weights None: 1 for t < n_new[b], else 0; "mean": 1 / n_new[b] instead; anything else is handed on as given"""
+    new, n_new = out["new_tokens"], out["n_new"]
+    S, T = out["sequences"].shape[1] - new.shape[1], new.shape[1]
+    if position_weights is None or (isinstance(position_weights, str) and position_weights == "mean"):
+        w = (torch.arange(T, device=n_new.device)[None] < n_new[:, None]).to(torch.float32)
+        if position_weights is not None:
+            w = w / n_new[:, None].to(torch.float32)
+    else:
+        w = position_weights
+    return torch.arange(S - 1, S + T - 1).expand(new.shape[0], T), w
 
 
 def head_fwd(ar, h, branch, top, last, norm, lm_head, eps, w_offset=0.0):
@@ -1697,12 +1758,7 @@ class LlamaLRP:
         B, S = ids.shape
         dev, ar, L, nkd, nq, nk, d = self.device, self._arena, len(self.layers), c["n_kv"] * c["head_dim"], c["n_heads"], c["n_kv"], c["head_dim"]
         cap = S + max_new_tokens
-        forced = None
-        if force_tokens is not None:
-            forced = torch.as_tensor(force_tokens).cpu()
-            if tuple(forced.shape) != (B, max_new_tokens) or forced.is_floating_point() or int(forced.min()) < 0 or int(forced.max()) >= c["vocab"]:
-                raise ValueError(f"force_tokens must hold vocabulary indices in [0, {c['vocab']}) of shape ({B}, {max_new_tokens})")
-            forced = forced.to(device=dev, dtype=torch.int32)
+        forced = force_request(force_tokens, B, max_new_tokens, c["vocab"], dev)
         _, _, _, row_iv, _ = explain_inputs(ids, None, None if lengths is None else lens, None, c["vocab"], self.max_seq, self.dtype, dev)
         ids = ids.to(dev)
         fw = self.forward(self.embed.index_select(0, ids.reshape(-1)), B, S, row_iv)
@@ -1717,35 +1773,7 @@ class LlamaLRP:
             step = lambda tok, pos: self._graphs(("decode", B, cap, self.mode), lambda t_, p_: self._decode_step(t_, p_, lo, kc, vc, ws), tok, pos)      # noqa: E731
         else:
             step = lambda tok, pos: self._decode_step(tok, pos, lo, kc, vc, ws)      # noqa: E731
-        eos_t = torch.tensor(eos, device=dev, dtype=torch.int32) if eos else None
-        fin = torch.zeros(B, device=dev, dtype=torch.bool)
-        n_new = torch.zeros(B, device=dev, dtype=torch.long)
-        toks, logit, logprob, rows = [], [], [], []
-        logits, idx = fw["logits"], ops.argmax_rows(fw["logits"])[0]
-        for t in range(max_new_tokens):
-            if t:
-                logits, idx = step(toks[-1], cols[t - 1: t])
-            if forced is not None:
-                idx = forced[:, t]
-            if eos:
-                idx = torch.where(fin, torch.full_like(idx, pad), idx)          # (a copy: idx may be a graph's static output)
-            lg, lp, _, _ = ops.span_seed(logits, idx.contiguous())
-            toks.append(idx.long())
-            logit.append(lg)
-            logprob.append(lp)
-            if return_logits:
-                rows.append(logits.clone())
-            n_new += ~fin
-            if eos:
-                fin |= torch.isin(idx, eos_t)
-                if bool(fin.all()):
-                    break
-        new = torch.stack(toks, 1)
-        out = dict(sequences=torch.cat((ids, new), 1), new_tokens=new, n_new=n_new, logit=torch.stack(logit, 1), logprob=torch.stack(logprob, 1),
-                   lengths=lens.to(dev) + new.shape[1])
-        if return_logits:
-            out["logits"] = torch.stack(rows, 1)
-        return out
+        return greedy_decode(fw["logits"], step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits)
 
     @torch.no_grad()
     def explain_generated(self, input_ids=None, max_new_tokens=1, lengths=None, eos_token_id=None, pad_token_id=None, graph=False,
@@ -1757,15 +1785,7 @@ class LlamaLRP:
         explicit fp32 [B, T'].  The last column is no explained row: R_tok is exactly 0 there, as at pads.  -> explain's dict plus sequences,
         new_tokens, n_new.  graph applies to the generation; per_position=True and every read-out keyword pass through to explain()."""
         out = self.generate(input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph=graph)
-        new, n_new = out["new_tokens"], out["n_new"]
-        S, T = out["sequences"].shape[1] - new.shape[1], new.shape[1]
-        if position_weights is None or (isinstance(position_weights, str) and position_weights == "mean"):
-            w = (torch.arange(T, device=n_new.device)[None] < n_new[:, None]).to(torch.float32)
-            if position_weights is not None:
-                w = w / n_new[:, None].to(torch.float32)
-        else:
-            w = position_weights
-        positions = torch.arange(S - 1, S + T - 1).expand(new.shape[0], T)
+        positions, w = generated_span(out, position_weights)
         res = self.explain(out["sequences"], lengths=out["lengths"], positions=positions, position_weights=w, objective=objective, **readout_kw)
-        res.update(sequences=out["sequences"], new_tokens=new, n_new=n_new)
+        res.update(sequences=out["sequences"], new_tokens=out["new_tokens"], n_new=out["n_new"])
         return res

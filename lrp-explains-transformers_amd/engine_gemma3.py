@@ -18,8 +18,9 @@ activations live in the same tagged arena as the Llama driver's.
 import torch
 
 from . import ops
-from .engine import (EFFICIENT, Arena, AttnMapSink, HeadSink, attn_map_request, explain_inputs, explanation, fused_layout, head_fwd,
-                     head_request, latent_request, pack_flat, pitch_pad, put_gate_up, put_rows, rope_tables, top_attn_operands)
+from .engine import (EFFICIENT, Arena, AttnMapSink, GraphCache, HeadSink, attn_map_request, explain_inputs, explanation, force_request, fused_layout,
+                     generate_request, generated_span, greedy_decode, head_fwd, head_request, latent_request, pack_flat, pitch_pad,
+                     position_request, put_gate_up, put_rows, rope_tables, top_attn_operands)
 
 _STATIC_ROPE = ("default", "linear")
 
@@ -91,11 +92,15 @@ def gemma_attn_map_request(attn_map, nL, nq, d, dtype, mode="efficient"):
     return attn_map_request(attn_map, nL, nq, d, dtype, mode)
 
 
-def readout_outputs(out, B, S, layer_R, lat, want_layer_R, want_trace, hs, am, device):
+def readout_outputs(out, B, S, layer_R, lat, want_layer_R, want_trace, hs, am, device, span_rows=None):
     """the read-outs of one explanation added to explain()'s dict under LlamaLRP.explain's names (README, DESIGN.md section 12 - 12.2);
-    layer_R: [rel_last [B], per-token rows [M] from the top boundary down to the embedding] or None"""
+    layer_R: [rel_last [B], per-token rows [M] from the top boundary down to the embedding] or None.  span_rows int64 [B T]
+    (explain(positions=...)): rel_last has one entry per explained row; they are placed at their columns (distinct rows: a copy, exactly
+    0 elsewhere), so a prompt's head sum is the same fixed-order row sum as every other layer's and R_trace[L].sum(-1) IS layer_R[L]"""
+    if span_rows is not None and (want_layer_R or want_trace):
+        head_rows = torch.zeros(B * S, device=device, dtype=torch.float32).index_copy_(0, span_rows, layer_R[0]).view(B, S)
     if want_layer_R:
-        rows = [layer_R[0]] + [r.view(B, S).sum(1) for r in layer_R[1:]]
+        rows = [layer_R[0] if span_rows is None else head_rows.sum(1)] + [r.view(B, S).sum(1) for r in layer_R[1:]]
         out["layer_R"] = torch.stack(rows[::-1], 0)          # [L+1, B], index 0 = embedding
     if want_trace:
         nL = len(layer_R) - 1
@@ -103,7 +108,10 @@ def readout_outputs(out, B, S, layer_R, lat, want_layer_R, want_trace, hs, am, d
         trace[0] = out["R_tok"]
         for li in range(1, nL):
             trace[li] = layer_R[nL - li].view(B, S)
-        trace[nL, :, S - 1] = layer_R[0]
+        if span_rows is None:
+            trace[nL, :, S - 1] = layer_R[0]
+        else:
+            trace[nL] = head_rows
         out["R_trace"] = trace
     out.update(lat)
     if hs is not None:
@@ -120,7 +128,8 @@ def readout_outputs(out, B, S, layer_R, lat, want_layer_R, want_trace, hs, am, d
 
 class Gemma3LRP:
     """explain(input_ids) -> dict(idx, logit, R_tok, logits): AttnLRP (lxt.efficient) token relevances of a Gemma-3 text decoder; on request
-    the layer, latent, per-head and token-to-token read-outs of LlamaLRP.explain"""
+    the layer, latent, per-head and token-to-token read-outs of LlamaLRP.explain, answer-span attribution
+    (positions=...), and generate() / explain_generated() on a KV cache"""
 
     def __init__(self, cfg, W, dtype=torch.bfloat16, device="cuda", max_seq=4096, sparse_top=True):
         if not torch.cuda.is_available():
@@ -146,8 +155,10 @@ class Gemma3LRP:
         self.attn_t = ops.attn_needs_transposed(self.embed, cfg["head_dim"])
         self.rope = {lt: rope_tables(inv, att, max_seq, dtype, dev) for lt, (inv, att) in cfg["rope"].items()}     # per layer type
         self.embed_scale = torch.tensor(cfg["embed_scale"], dtype=dtype)   # HF: the scale itself is rounded to the model dtype
+        self._embed_scale_dev = self.embed_scale.to(dev)                   # (the decode step is captured: no host-to-device copy inside it)
         self.max_seq = max_seq
         self._arena = Arena(dev, dtype)
+        self._graphs = GraphCache(dev, lambda: self._arena.gen)          # generate(graph=True): the decode step, one graph per (B, cap)
         torch.cuda.synchronize(dev)
 
     @staticmethod
@@ -170,6 +181,7 @@ class Gemma3LRP:
 
     def release(self):
         self._arena = Arena(self.device, self.dtype)
+        self._graphs.clear()
 
     def _window(self, li):
         return self.cfg["window"] if self.cfg["layer_types"][li] == "sliding_attention" else 0
@@ -184,9 +196,11 @@ class Gemma3LRP:
         return True, self._window(li), row_iv
 
     # ---------------------------------------------------------------------------------------------
-    def forward(self, emb, B, S, row_iv=None, keep_h=False, keep_m=False):
+    def forward(self, emb, B, S, row_iv=None, keep_h=False, keep_m=False, rows=None):
         """keep_h / keep_m: every layer's input h / down-projection input m gets a buffer of its own (the read-outs of the backward need
-        them); otherwise h lives in a two-buffer ping-pong and m in one shared buffer, and neither survives its layer"""
+        them); otherwise h lives in a two-buffer ping-pong and m in one shared buffer, and neither survives its layer.  rows int64 [R]
+        (explain(positions=...)): the explained rows of the [B S, .] activations in place of each prompt's last one; the top layer then
+        runs dense like every other layer, whatever self.sparse_top says"""
         c = self.cfg
         H, I, d, nq, nk = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"]
         M, dt, dev = B * S, self.dtype, self.device
@@ -195,7 +209,7 @@ class Gemma3LRP:
         eps = c["rms_eps"]
         stash = []
         h_prev, branch, nxt = emb, None, None
-        last = torch.arange(B, device=dev) * S + (S - 1)
+        last = torch.arange(B, device=dev) * S + (S - 1) if rows is None else rows
         site = ops.sandwich_norm_ok(emb)      # Gemma-3's norms / q-k norm / RoPE fused per site (ops.SITE_FUSION; results bit-identical)
         h_tag = (lambda li: ("h_keep", li)) if keep_h else (lambda li: ("h", li & 1))
         m_buf = (lambda li: ar.get(("m_keep", li), (M, I), dt, pad=pitch_pad(I, dt.itemsize))) if keep_m else (lambda li: ar.wide("m", M, I))
@@ -231,7 +245,7 @@ class Gemma3LRP:
             v_t = ops.transpose_heads(v, B, S, nk, d) if self.attn_t else None
             o, lse = ar.new(("o", li), M, nqd), ar.f32(("lse", li), B, nq, S)
             causal, win, iv = self._attn_mask(li, row_iv)
-            if self.sparse_top and li == len(self.layers) - 1:
+            if self.sparse_top and rows is None and li == len(self.layers) - 1:
                 # ---- the top layer above its attention: one row per prompt
                 ops.attn_fwd(qr, kr, v, v_t, o, lse, B, S, nq, nk, d, c["scale"], causal, win, q_begin=S - 1, row_iv=iv)
                 o_l, h_l = o.index_select(0, last), h.index_select(0, last)
@@ -309,14 +323,29 @@ class Gemma3LRP:
         plain = not (layer_relevance or latent or heads is not None or attn_map is not None)
         lat, layer_R, iv_cache = {}, None, {}
         # LM head (gradient of the explained logit) + final (1 + w) norm on the one explained row of each prompt, scattered into [M, H]
-        Gh_last = ops.head_seed(self.lm_head, fw["logits"], idx, self.norm, fw["rstd_f"], ar.new("Gh_last", B, H), 1.0, E["lin"])
+        span, R = fw.get("span"), fw["last"].shape[0]
+        if span is None:
+            Gh_last = ops.head_seed(self.lm_head, fw["logits"], idx, self.norm, fw["rstd_f"], ar.new("Gh_last", B, H), 1.0, E["lin"])
+        else:
+            # R = B T explained rows in slot order: lrp_span_seed leaves logit / logprob, the row scale w (*) rstd_f of the one-hot route
+            # ("logit"), or the dense seed w (delta - softmax) in the engine dtype ("logprob"), as LlamaLRP._head_bwd
+            dense = span["objective"] == "logprob"
+            sd = ar.new("span_seed", R, self.lm_head.shape[0]) if dense else None
+            span["logit"], span["logprob"], rs, _ = ops.span_seed(fw["logits"], idx, span["w"], fw["rstd_f"], span["objective"], seed=sd,
+                                                                  logit=ar.f32("span_logit", R), logprob=ar.f32("span_logprob", R),
+                                                                  rs=ar.f32("span_rs", R))
+            if dense:
+                g_xn = ops.linear_dgrad(sd, self.lm_head, out_dtype=torch.float32)
+                Gh_last = ops.head_norm_bwd(g_xn, self.norm, fw["rstd_f"], ar.new("Gh_last", R, H), 1.0)
+            else:
+                Gh_last = ops.head_seed(self.lm_head, fw["logits"], idx, self.norm, rs, ar.new("Gh_last", R, H), 1.0, E["lin"])
         top = bool(fw["stash"]) and fw["stash"][-1].get("top", False)
         Gs = None if top else ar.zeros(("Gs", len(self.layers) & 1), M, H).index_copy_(0, fw["last"], Gh_last)       # gradient w.r.t. h_L = h1 + pff
         if layer_relevance:          # index L: the head's explained rows (S = 1)
-            layer_R = [ops.readout(fw["hL_last"], Gh_last, out=ar.f32("rel_last", B))]
+            layer_R = [ops.readout(fw["hL_last"], Gh_last, out=ar.f32("rel_last", R))]
         if "resid" in latent:
             lat["R_resid"] = torch.empty(nL + 1, B, H, device=dev, dtype=torch.float32)
-            ops.colsum_dot(fw["hL_last"], Gh_last, B, 1, out=lat["R_resid"][nL])
+            ops.colsum_dot(fw["hL_last"], Gh_last, B, R // B, out=lat["R_resid"][nL])          # (a prompt's explained rows, in slot order)
         if "mlp" in latent:
             lat["R_mlp"] = torch.empty(nL, B, I, device=dev, dtype=torch.float32)
         site, Gdn = fw["site"], None
@@ -428,11 +457,15 @@ class Gemma3LRP:
         am = gemma_attn_map_request(attn_map, len(getattr(self, "layers", ())), c.get("n_heads", 0), c.get("head_dim"), self.dtype)
         return latent_request(latent, c["hidden"], c["inter"], self.dtype), head_request(heads, c.get("head_dim"), self.dtype), am
 
-    def explain_emb(self, emb, B, S, row_iv, idx, return_G=False, layer_relevance=False, lat=frozenset(), hd=frozenset(), am=(False, ())):
+    def explain_emb(self, emb, B, S, row_iv, idx, return_G=False, layer_relevance=False, lat=frozenset(), hd=frozenset(), am=(False, ()),
+                    span=None):
         """forward + backward + read-outs on prepared embeddings and CHECKED requests (readout_requests) -> (explain()'s dict, G at the embedding);
-        with no request the buffers, the launches and every output are those of the plain call"""
+        with no request the buffers, the launches and every output are those of the plain call.  span: a SpanRequest
+        (engine.position_request, explain(positions=...)); None: nothing of it is touched"""
         c = self.cfg
         want_R = layer_relevance or "trace" in lat
+        if span is not None:
+            return self._explain_span(emb, B, S, row_iv, span, return_G, layer_relevance, lat, hd, am)
         fw = self.forward(emb, B, S, row_iv, keep_h=want_R or "resid" in lat, keep_m="mlp" in lat)
         if idx is None:
             idx, _ = ops.argmax_rows(fw["logits"])
@@ -446,9 +479,43 @@ class Gemma3LRP:
         out = explanation(emb, G, idx, fw["logits"], B, S, return_G)
         return readout_outputs(out, B, S, layer_R, sums, layer_relevance, "trace" in lat, hs, ams, self.device), G
 
+    def _explain_span(self, emb, B, S, row_iv, span, return_G, layer_relevance, lat, hd, am):
+        """explain_emb for an answer span: the forward with the dense top layer and the head on the R = B T explained
+        rows, then one backward seeded by lrp_span_seed (per_position: T backwards over the same forward state, pass t seeded at slot t
+        alone -- the backward writes gradient buffers and temporaries only, never a buffer the forward stashed)"""
+        c, T = self.cfg, span.T
+        want_R = layer_relevance or "trace" in lat
+        fw = self.forward(emb, B, S, row_iv, keep_h=want_R or "resid" in lat, keep_m="mlp" in lat, rows=span.rows)
+        idx = span.idx
+        if span.auto is not None:          # the slots at column S - 1 without a target: that row's arg-max (a row copy, no arithmetic)
+            idx.index_copy_(0, span.auto, ops.argmax_rows(fw["logits"])[0].index_select(0, span.auto))
+        fw["span"] = sp = dict(w=span.w, objective=span.objective)
+        head = lambda: dict(idx=idx.view(B, T), logit=sp["logit"].view(B, T).clone(), logprob=sp["logprob"].view(B, T).clone())      # noqa: E731
+        if span.per_position:
+            each = torch.empty(B, T, S, device=self.device, dtype=torch.float32)
+            for t in range(T):
+                sp["w"] = span.w_each[t]
+                G = self.backward(fw, idx, B, S)
+                each[:, t] = ops.readout(emb, G).view(B, S)
+            return dict(head(), R_tok_each=each, R_tok=each.sum(1)), G
+        plain = not (want_R or lat or hd or am[0] or am[1])
+        nL, hs, ams, layer_R, sums = len(self.layers), None, None, None, {}
+        if plain:
+            G = self.backward(fw, idx, B, S)
+        else:
+            hs = HeadSink(hd, nL, B, S, c["n_heads"], c["head_dim"], self.device) if hd else None
+            ams = AttnMapSink(am, nL, B, S, c["n_heads"], c["n_kv"], c["head_dim"], c["scale"], self.device) if am[0] or am[1] else None
+            G, layer_R, sums = self.backward(fw, idx, B, S, want_R, lat, hs, ams)
+        out = dict(head(), R_tok=ops.readout(emb, G).view(B, S))          # (no logits: R V fp32 is hundreds of MB at a 262 k vocabulary)
+        if return_G:
+            out["G_emb"], out["emb"] = G.view(B, S, -1).clone(), emb.view(B, S, -1)
+        if plain:
+            return out, G
+        return readout_outputs(out, B, S, layer_R, sums, layer_relevance, "trace" in lat, hs, ams, self.device, span.rows), G
+
     @torch.no_grad()
     def explain(self, input_ids=None, inputs_embeds=None, target=None, return_G=False, lengths=None, layer_relevance=False, latent=None,
-                heads=None, attn_map=None):
+                heads=None, attn_map=None, positions=None, position_weights=None, objective="logit", per_position=False):
         """input_ids [B, S] (or inputs_embeds [B, S, H] = HF's scaled embeddings); target: None (arg-max of the last position) or [B]
         vocabulary indices.  Returns dict(idx [B], logit [B], R_tok [B, S] fp32 = sum_h e (*) dlogit/de, logits [B, V]).
         lengths [B] (optional): prompts of different lengths in one call, LEFT-padded to S (as LlamaLRP.explain: pad keys are masked through
@@ -459,10 +526,116 @@ class Gemma3LRP:
         k / v per QUERY head at the source position);  attn_map "sum" and / or (layer, head) pairs: R_attn [L, B, S, S], R_attn_heads
         [n, B, S, S] and attn_map_heads (bf16 at head dim 256 runs lrp_attn_relmap_d256).  Entries outside a sliding layer's window, above
         the diagonal and at pad positions are exactly 0.  Requests are checked before a kernel of the model runs; R_tok, logit, idx and logits
-        do not change with them, and a call without them allocates and launches what it always did."""
+        do not change with them, and a call without them allocates and launches what it always did.
+        positions int [B, T] (optional), with position_weights, objective and per_position: answer-span attribution with the semantics, shapes
+        and refusals of LlamaLRP.explain (DESIGN.md sections 20 and 23) -- T explained rows per prompt in one forward and one backward, target
+        then [B, T] (default: the next token, the arg-max at column S - 1); returns idx, logit, logprob [B, T] and R_tok [B, S] (no logits),
+        exactly 0 at pads and above the highest explained column; per_position=True adds R_tok_each [B, T, S] from T backwards.  Every
+        read-out keyword keeps working.  Such a call runs the top layer dense; self.sparse_top stays as it is."""
         lat, hd, am = self.readout_requests(latent, heads, attn_map)
+        nb, ns = (input_ids.shape if inputs_embeds is None else inputs_embeds.shape[:2]) if positions is not None else (0, 0)
+        span = position_request(positions, position_weights, objective, per_position, nb, ns, self.cfg["vocab"], getattr(self, "device", None),
+                                input_ids if inputs_embeds is None else None, target, lengths,
+                                readouts=bool(layer_relevance or return_G or latent or heads or attn_map))
+        if span is not None:
+            target = None          # (checked and converted above; explain_inputs sees the plain form)
         B, S, emb, row_iv, idx = explain_inputs(input_ids, inputs_embeds, lengths, target, self.cfg["vocab"], self.max_seq, self.dtype,
                                                 self.device)
         if emb is None:
             emb = self.embed.index_select(0, input_ids.to(self.device).reshape(-1)) * self.embed_scale.to(self.device)
-        return self.explain_emb(emb, B, S, row_iv, idx, return_G, layer_relevance, lat, hd, am)[0]
+        return self.explain_emb(emb, B, S, row_iv, idx, return_G, layer_relevance, lat, hd, am, span)[0]
+
+    # --------------------------------------------------------------------------------------------- generation (DESIGN.md section 23)
+    def _decode_step(self, tok, pos, lo, kc, vc, ws):
+        """one new token per prompt through every layer on B rows (LlamaLRP._decode_step for Gemma-3): embedding rows times embed_scale, then
+        per layer the input norm, the QKV Linear, lrp_decode_qknorm_rope_append (both head norms, RoPE with the layer type's table and the
+        cache append in one launch), lrp_attn_decode, the o projection, the post-attention / pre-feed-forward norm pair, the gated MLP, the
+        down projection, and the post-feed-forward norm with the next layer's input norm.  A sliding layer's first live key is
+        max(lo[b], p - window + 1), formed on the device once per step.  tok int64 [B] and pos int32 [1] are device INPUTS of the step,
+        nothing is incremented inside it.  kc, vc [L, B, cap, nk d];  lo int32 [B].  -> (logits [B, V] fp32, idx int32 [B]); launches only,
+        capturable"""
+        c = self.cfg
+        H, I, d, nq, nk, eps = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"], c["rms_eps"]
+        B, ar, nqk, nL = tok.shape[0], self._arena, (nq + nk) * d, len(self.layers)
+        h = torch.mul(self.embed.index_select(0, tok), self._embed_scale_dev, out=ar.new("dec_emb", B, H))
+        lo_win = None
+        if "sliding_attention" in c["layer_types"]:
+            first = torch.sub(pos, c["window"] - 1, out=ar.get("dec_first", (1,), torch.int32))
+            lo_win = torch.maximum(lo, first, out=ar.get("dec_lo_win", (B,), torch.int32))
+        site = ops.sandwich_norm_ok(h)
+        x, r1, r2 = ar.new("dec_x", B, H), ar.f32("dec_rstd_a", B), ar.f32("dec_rstd_b", B)
+        ops.add_rmsnorm_fwd(h, None, self.layers[0]["ln_in"], eps, 1.0, y=x, rstd=r1)
+        for li, Lw in enumerate(self.layers):
+            cos, sin = self.rope[c["layer_types"][li]]
+            qkv = ops.linear_fwd(x, Lw["wqkv"], out=ar.new("dec_qkv", B, nqk + nk * d))
+            q = ops.decode_qknorm_rope_append(qkv[:, :nqk], qkv[:, nqk:], Lw["qn"], Lw["kn"], eps, cos, sin, pos, ar.new("dec_q", B, nq * d),
+                                              kc[li], vc[li], nq, nk, d, 1.0)
+            o = ops.attn_decode(q, kc[li], vc[li], lo_win if self._window(li) else lo, pos, nq, nk, d, c["scale"],
+                                out=ar.new("dec_o", B, nq * d), ws=ws)
+            a = ops.linear_fwd(o, Lw["wo"], out=ar.new("dec_a", B, H))
+            h1, x2 = ar.new("dec_h1", B, H), ar.new("dec_x2", B, H)
+            if site:
+                ops.sandwich_norm_fwd(a, h, Lw["ln_pa"], Lw["ln_pf"], eps, 1.0, h1, x2, r1, r2)
+            else:
+                pa = ar.new("dec_pa", B, H)
+                ops.add_rmsnorm_fwd(a, None, Lw["ln_pa"], eps, 1.0, y=pa, rstd=r1)
+                ops.add_rmsnorm_fwd(h, pa, Lw["ln_pf"], eps, 1.0, hsum_out=h1, y=x2, rstd=r2)
+            gu, m = ops.gemm_gated_fwd(x2, Lw["wgu"], ar.new("dec_gu", B, 2 * I), ar.new("dec_m", B, I), self.act)
+            dn = ops.linear_fwd(m, Lw["wd"], out=ar.new("dec_dn", B, H))
+            if li + 1 == nL:
+                pff = ar.new("dec_pff", B, H)
+                ops.add_rmsnorm_fwd(dn, None, Lw["ln_pff"], eps, 1.0, y=pff, rstd=r1)
+                break
+            h = ar.new(("dec_h", li & 1), B, H)          # (the next layer's input: not h1, which this very step reads)
+            if site:
+                ops.sandwich_norm_fwd(dn, h1, Lw["ln_pff"], self.layers[li + 1]["ln_in"], eps, 1.0, h, x, r1, r2)
+            else:
+                pff = ar.new("dec_pff", B, H)
+                ops.add_rmsnorm_fwd(dn, None, Lw["ln_pff"], eps, 1.0, y=pff, rstd=r1)
+                ops.add_rmsnorm_fwd(h1, pff, self.layers[li + 1]["ln_in"], eps, 1.0, hsum_out=h, y=x, rstd=r2)
+        logits = head_fwd(ar, h1, pff, True, tok, self.norm, self.lm_head, eps, 1.0)["logits"]      # (top form: one row per prompt already)
+        return logits, ops.argmax_rows(logits)[0]
+
+    @torch.no_grad()
+    def generate(self, input_ids=None, max_new_tokens=1, lengths=None, eos_token_id=None, pad_token_id=None, graph=False, return_logits=False,
+                 inputs_embeds=None, force_tokens=None):
+        """Greedy continuation of input_ids [B, S] on the resident weights, forward only, with a KV cache: LlamaLRP.generate's signature,
+        returned dict (sequences, new_tokens, n_new, logit, logprob, lengths[, logits]) and EOS / pad / force_tokens / lengths behaviour
+        (DESIGN.md sections 21 and 23).  The prefill is the forward explain() runs; every layer's normed, rotated K and its V are copied into
+        caches [L, B, cap, nk d] of the arena, cap = S + max_new_tokens <= max_seq (sliding layers keep all cap rows: no ring buffer); the
+        first new token is the lrp_argmax_rows of the prefill's logits, each further one costs one _decode_step.  graph=True: the step is
+        captured once per (B, cap) and replayed, bitwise the eager result.  Greedy only.  ValueError before any kernel runs: inputs_embeds,
+        max_new_tokens < 1, S + max_new_tokens > max_seq, bad lengths, an eos_token_id, pad_token_id or forced token outside [0, vocab)."""
+        c = self.cfg
+        ids, lens, eos, pad = generate_request(input_ids, inputs_embeds, max_new_tokens, lengths, eos_token_id, pad_token_id, c["vocab"], self.max_seq)
+        B, S = ids.shape
+        dev, ar, L, nq, nk, d = self.device, self._arena, len(self.layers), c["n_heads"], c["n_kv"], c["head_dim"]
+        nkd, cap = nk * d, S + max_new_tokens
+        forced = force_request(force_tokens, B, max_new_tokens, c["vocab"], dev)
+        _, _, _, row_iv, _ = explain_inputs(ids, None, None if lengths is None else lens, None, c["vocab"], self.max_seq, self.dtype, dev)
+        ids = ids.to(dev)
+        fw = self.forward(self.embed.index_select(0, ids.reshape(-1)) * self.embed_scale.to(dev), B, S, row_iv)
+        kc, vc = ar.new("kcache", L, B, cap, nkd), ar.new("vcache", L, B, cap, nkd)
+        for li, st in enumerate(fw["stash"]):
+            kc[li, :, :S].copy_(st["kr"].view(B, S, nkd))
+            vc[li, :, :S].copy_(st["qkv"][:, (nq + nk) * d:].view(B, S, nkd))
+        lo = ar.get("dec_lo", (B,), torch.int32).copy_(S - lens)
+        ws = ar.get("dec_ws", (ops.attn_decode_ws(B, nq, d, cap),), torch.uint8)
+        cols = torch.arange(S, cap, device=dev, dtype=torch.int32)          # cols[t - 1: t]: the column of step t's input token
+        if graph:
+            step = lambda tok, pos: self._graphs(("decode", B, cap), lambda t_, p_: self._decode_step(t_, p_, lo, kc, vc, ws), tok, pos)      # noqa: E731
+        else:
+            step = lambda tok, pos: self._decode_step(tok, pos, lo, kc, vc, ws)      # noqa: E731
+        return greedy_decode(fw["logits"], step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits)
+
+    @torch.no_grad()
+    def explain_generated(self, input_ids=None, max_new_tokens=1, lengths=None, eos_token_id=None, pad_token_id=None, graph=False,
+                          objective="logprob", position_weights=None, **readout_kw):
+        """generate(), then explain(sequences, lengths=out["lengths"], positions=[S - 1 .. S + T' - 2], position_weights=w,
+        objective=objective, **readout_kw) with the weight rules of LlamaLRP.explain_generated (1 for t < n_new[b] else 0; "mean";
+        or explicit) -> explain's dict plus sequences, new_tokens, n_new.  The last column is no explained row: R_tok is exactly 0 there"""
+        out = self.generate(input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph=graph)
+        positions, w = generated_span(out, position_weights)
+        res = self.explain(out["sequences"], lengths=out["lengths"], positions=positions, position_weights=w, objective=objective, **readout_kw)
+        res.update(sequences=out["sequences"], new_tokens=out["new_tokens"], n_new=out["n_new"])
+        return res

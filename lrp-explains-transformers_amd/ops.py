@@ -1497,6 +1497,31 @@ def decode_rope_append(qk, v, cos, sin, pos, q_rot, kc, vc, nq, nk, d):
     return q_rot
 
 
+def decode_qknorm_rope_append(qk, v, wq, wk, eps, cos, sin, pos, q_rot, kc, vc, nq, nk, d, w_offset=0.0):
+    """decode_rope_append with the per-head RMSNorms of q and k (wq, wk [d] in qk's dtype, eps, w_offset: 1 for Gemma's (1 + w)) in front
+    of the rotation, one launch (csrc/decode_site.hip) -- bitwise head_rmsnorm_fwd on the q columns, head_rmsnorm_fwd on the k columns, then
+    decode_rope_append.  Operands and the device-side check of pos as there; no rstd is written.  d * element size / 16 a power of two,
+    d <= 256."""
+    B = qk.shape[0]
+    pq = p(qk)
+    _decode_rows("decode_qknorm_rope_append", qk, "qk", B, (nq + nk) * d)
+    _decode_rows("decode_qknorm_rope_append", v, "v", B, nk * d, qk)
+    _decode_rows("decode_qknorm_rope_append", q_rot, "q_rot", B, nq * d, qk)
+    cap, ldc = _decode_cache("decode_qknorm_rope_append", kc, vc, B, nk * d, qk)
+    _decode_pos("decode_qknorm_rope_append", pos, qk)
+    f32(cos, sin)
+    if cos.dim() != 2 or cos.shape[1] != d or cos.shape != sin.shape or not cos.is_contiguous() or not sin.is_contiguous():
+        raise ValueError(f"decode_qknorm_rope_append: cos / sin must be contiguous [rows, {d}] tables")
+    same(qk, wq, wk)          # (no conversion here: the step is captured, a cast would allocate)
+    if wq.numel() != d or wk.numel() != d or not wq.is_contiguous() or not wk.is_contiguous():
+        raise ValueError(f"decode_qknorm_rope_append: wq / wk must be contiguous [{d}] norm weights")
+    ld = lambda t: t.stride(0) if B > 1 else max(t.stride(0), t.shape[1])      # noqa: E731  (a one-row view's pitch is arbitrary)
+    check(lib.lrp_decode_qknorm_rope_append(pq, ld(qk), p(v), ld(v), p(wq), p(wk), float(eps), float(w_offset), p(cos), p(sin), cos.shape[0],
+                                            p(pos), p(q_rot), ld(q_rot), p(kc), p(vc), ldc, B, cap, nq, nk, d, dt(qk), stream()),
+          "lrp_decode_qknorm_rope_append")
+    return q_rot
+
+
 def attn_decode_ws(B, Hq, d, cap):
     """bytes of attn_decode's workspace"""
     n = int(lib.lrp_attn_decode_ws(B, Hq, d, cap))
