@@ -18,49 +18,29 @@
 // Grid: ceil(N / (4 rw)) workgroups, rw = W rows per wave (8 .. 16, stream_rows_per_wave: whole rounds of the 256 CUs); the host uses the kernel when
 // ceil(N / 64) >= 192 and K is a multiple of 512.
 // D = mfma(Wfrag, xfrag): lane l holds z[m = 16 i + (l & 15)][n = n0 + 16 w + 4 (l >> 4) + e].
-#include "common.hpp"
+#include "linear_stream.hpp"
 
 namespace {
 
-constexpr int LS_KT = 64;      // K elements per K tile
-constexpr int LS_WD = 8;       // K tiles of W in flight per wave (register ring)
-typedef __attribute__((address_space(3))) void* ls_lds_ptr_t;
-
-template <int MBMAX> struct LSCfg {
-    static constexpr int XD = 3;                                   // x prefetch distance in K tiles
-    static constexpr int NBUF = XD + 2;                            // LDS ring: tile t + XD is written while tiles t - 1, t may still be read
-    static constexpr int P = MBMAX / 2;                            // 1-KiB staging pieces (8 rows x 128 B) per wave per K tile
-    static constexpr int XTILE = MBMAX * 16 * 128;                 // bytes of one x tile
-    static constexpr int BS = MBMAX < 4 ? MBMAX : 4;               // row blocks per LDS read batch
-    static constexpr int NBATCH = MBMAX / BS;
-    static constexpr int VMC = XD * (P + 2);                       // VMEM operations younger than x(t) at the wait of tile t (steady state)
+template <int MBMAX> struct LSPCfg : LSCfg<MBMAX, 3> {
+    using B = LSCfg<MBMAX, 3>;
+    static constexpr int VMC = B::XD * (B::P + 2);                 // VMEM operations younger than x(t) at the wait of tile t (steady state)
 };
 // the same count inside the peeled last block (static s = position in the block; no W loads, x stages only while t + XD < nkt)
 template <int MBMAX> constexpr int ls_last_vmc(int s) {
-    constexpr int XD = LSCfg<MBMAX>::XD, P = LSCfg<MBMAX>::P;
+    constexpr int XD = LSPCfg<MBMAX>::XD, P = LSPCfg<MBMAX>::P;
     int c = 0;
     for (int j = s - XD + 1; j <= s; ++j) c += (j <= 7 - XD) ? P : 0;      // x stages issued at (relative) iterations s - XD + 1 .. s
     for (int j = s - XD; j <= s - 1; ++j) c += (j < 0) ? 2 : 0;            // W loads issued at the end of iterations s - XD .. s - 1
     return c;
 }
 
-template <int V> struct LSI { static constexpr int value = V; };
-template <int I, int N, typename F> LRP_DEVICE void ls_for(F&& f) {
-    if constexpr (I < N) {
-        f(LSI<I>{});
-        ls_for<I + 1, N>(static_cast<F&&>(f));
-    }
-}
-
-#define LS_DSRD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-
 template <typename TO, int MBMAX>
 __global__ __launch_bounds__(256, (MBMAX <= 4) ? 2 : 1) void linear_stream_fwd_kernel(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ W, TO* __restrict__ z, const bf16_t* __restrict__ bias, int M, int N, int K,
     int64_t ldx, int64_t ldw, int64_t ldz, int rw, int kt_per_split, int64_t slab_stride, unsigned* __restrict__ tickets,
     void* __restrict__ fin, int64_t ldf, int fin_f32) {
-    using C = LSCfg<MBMAX>;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+    using C = LSPCfg<MBMAX>;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // rw = W rows per wave (8 .. 16): the host picks it so that ceil(N / (4 rw)) workgroups cover the 256 CUs in whole rounds -- N = 14336 with
@@ -69,7 +49,7 @@ __global__ __launch_bounds__(256, (MBMAX <= 4) ? 2 : 1) void linear_stream_fwd_k
     const int n0 = blockIdx.x * (4 * rw);
     // round 5 -- K SPLITS for narrow weights (N = 4096: 64 workgroups of full K would leave three quarters of the chip idle, and the split-K path of
     // the ping-pong GEMM costs a second launch): blockIdx.y owns kt_per_split K tiles and writes an fp32 partial slab; the slabs of a column block
-    // are summed by the LAST workgroup to arrive on it (tickets: the protocol of the dgrad kernel below)
+    // are summed by the LAST workgroup to arrive on it (tickets: linear_stream.hpp)
     const int kt0 = (int)blockIdx.y * kt_per_split;
     const int nkt = (gridDim.y > 1) ? kt_per_split : K / LS_KT;
     int nb = (M + 15) >> 4;
@@ -80,12 +60,13 @@ __global__ __launch_bounds__(256, (MBMAX <= 4) ? 2 : 1) void linear_stream_fwd_k
     const int prow = lane >> 3, pslot = lane & 7;
     int voW[2];
 #pragma unroll
-    for (int p = 0; p < 2; ++p) voW[p] = (8 * p + prow < rw) ? (int)(prow * ldw * 2) + ((pslot ^ prow) << 4) : 0x40000000;
+    for (int p = 0; p < 2; ++p) voW[p] = (8 * p + prow < rw) ? (int)(prow * ldw * 2) + ((pslot ^ prow) << 4) : LS_OOB;
     const int soW = (int)((int64_t)(n0 + rw * wave) * ldw * 2);
     char* const wring = smem + C::NBUF * C::XTILE + wave * (LS_WD * 2048);       // [LS_WD tiles][16 rows][128 B], wave-private
-    // ---- x: LDS-DMA pieces of 8 rows x 128 B; lane l -> row l >> 3, LDS slot l & 7, source chunk slot ^ (row & 7)
     const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)(((int64_t)(M - 1) * ldx + K) * 2), 0x00020000);
     const int voX = (int)(prow * ldx * 2) + ((pslot ^ prow) << 4);
+    // ---- x (M rows, L2-resident, shared by the 4 waves): K tile kt into ring buffer buf by LDS-DMA pieces of 8 rows x 128 B; lane l -> row l >> 3,
+    // LDS slot l & 7, source chunk slot ^ (row & 7).  linear_stream_q.hip's stage_x is this one (+ its range test): they change together
     auto stage_x = [&](int kt, int buf) {
 #pragma unroll
         for (int p = 0; p < C::P; ++p) {
@@ -94,16 +75,11 @@ __global__ __launch_bounds__(256, (MBMAX <= 4) ? 2 : 1) void linear_stream_fwd_k
                                                      (int)((int64_t)(8 * q) * ldx * 2) + (kt + kt0) * 128, 0, 0);
         }
     };
-    // fragment of row block i, k-step ks: row 16 i + (l & 15), chunk (4 ks + (l >> 4)) ^ (row & 7)
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(ls_lds_ptr_t)smem;
-    uint32_t cX[2];
+    uint32_t cX[2], cW[2];
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) cX[ks] = lds0 + (uint32_t)((lane & 15) * 128) + (uint32_t)((((4 * ks + (lane >> 4)) ^ (lane & 7))) << 4);
-
-    // W fragment of ring slot s, k-step ks: same image as x (row l & 15 of the wave's 16 rows)
-    uint32_t cW[2];
+    for (int ks = 0; ks < 2; ++ks) cX[ks] = ls_frag_x(lane, ks);
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) cW[ks] = cX[ks] + (uint32_t)(C::NBUF * C::XTILE + wave * (LS_WD * 2048));
+    for (int ks = 0; ks < 2; ++ks) cW[ks] = cX[ks] + ls_w_ring<C>(wave);
     f32x4 acc[MBMAX];
 #pragma unroll
     for (int i = 0; i < MBMAX; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -136,47 +112,7 @@ __global__ __launch_bounds__(256, (MBMAX <= 4) ? 2 : 1) void linear_stream_fwd_k
         else asm volatile("s_waitcnt vmcnt(%[cnt])" :: [cnt] "n"(C::VMC) : "memory");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        const uint32_t xb = (uint32_t)((t % C::NBUF) * C::XTILE);
-        const uint32_t a0 = cX[0] + xb, a1 = cX[1] + xb;
-        // this wave's W fragments of the tile (ring slot s): two reads, first in the LDS queue
-        u32x4 wq0, wq1;
-        LS_DSRD(wq0, cW[0], s * 2048);
-        LS_DSRD(wq1, cW[1], s * 2048);
-        // units u = (ks, batch): BS fragment reads each, read one unit ahead
-        u32x4 xf[2][C::BS];
-        constexpr int U = 2 * C::NBATCH;
-        auto issue = [&](auto uc) {
-            constexpr int u = decltype(uc)::value, ks = u / C::NBATCH, b = u % C::NBATCH;
-            (void)&xf; (void)&a0; (void)&a1;
-            ls_for<0, C::BS>([&](auto ic) {
-                constexpr int i = decltype(ic)::value;
-                (void)&xf; (void)&a0; (void)&a1;
-                if constexpr (ks == 0) LS_DSRD(xf[u & 1][i], a0, (b * C::BS + i) * 2048);
-                else LS_DSRD(xf[u & 1][i], a1, (b * C::BS + i) * 2048);
-            });
-        };
-        issue(LSI<0>{});
-        if constexpr (C::BS == 4) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(wq0), "+v"(wq1));
-        else asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(wq0), "+v"(wq1));
-        const bf16x8 w0 = __builtin_bit_cast(bf16x8, wq0), w1 = __builtin_bit_cast(bf16x8, wq1);
-        ls_for<0, U>([&](auto uc) {
-            constexpr int u = decltype(uc)::value, ks = u / C::NBATCH, b = u % C::NBATCH;
-            (void)&xf;
-            if constexpr (u + 1 < U) {
-                issue(LSI<u + 1>{});
-                if constexpr (C::BS == 4) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(xf[u & 1][0]), "+v"(xf[u & 1][1]), "+v"(xf[u & 1][2]), "+v"(xf[u & 1][3]));
-                else asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(xf[u & 1][0]), "+v"(xf[u & 1][1]));
-            } else {
-                if constexpr (C::BS == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xf[u & 1][0]), "+v"(xf[u & 1][1]), "+v"(xf[u & 1][2]), "+v"(xf[u & 1][3]));
-                else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xf[u & 1][0]), "+v"(xf[u & 1][1]));
-            }
-            ls_for<0, C::BS>([&](auto ic) {
-                constexpr int i = decltype(ic)::value, blk = b * C::BS + i;
-                if (blk < nb)
-                    acc[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ks == 0 ? w0 : w1, __builtin_bit_cast(bf16x8, xf[u & 1][i]), acc[blk], 0, 0, 0);
-            });
-            __builtin_amdgcn_sched_barrier(0);
-        });
+        ls_tile_mma<C>(cX, cW, (uint32_t)((t % C::NBUF) * C::XTILE), sc, acc, nb);
         if constexpr (!LAST) load_w(sc, t + LS_WD);
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -186,7 +122,10 @@ __global__ __launch_bounds__(256, (MBMAX <= 4) ? 2 : 1) void linear_stream_fwd_k
         ls_for<0, LS_WD>([&](auto sc) { tile(sc, LSI<0>{}, t0 + decltype(sc)::value); });
     ls_for<0, LS_WD>([&](auto sc) { tile(sc, LSI<1>{}, t0 + decltype(sc)::value); });
 
-    // ---- epilogue: lane holds z[16 i + (l & 15)][n0 + 16 w + 4 (l >> 4) + e]
+    // ---- epilogue: ls_fwd_epilogue's statements, written out.  Called as the function, this kernel's split (fp32) instantiations compile to other
+    // code (the slab sum's address arithmetic and block order) and <float, 4> measured 0.1 - 0.2 us over the written-out form at [6144, 4096],
+    // M = 64 (profiles/linear_stream_refactor_ab.txt).  The publish / ticket / slab sum below are ls_publish_quad, ls_last_arriver and
+    // ls_sum_quad of linear_stream.hpp, where the ordering argument is written; a change to that protocol is made here as well.
     const int c16 = 4 * (lane >> 4);                                  // column of the wave's 16-row block: live while < rw
     const int ncol = n0 + rw * wave + c16;
     f32x4 bv = {0.f, 0.f, 0.f, 0.f};
@@ -198,8 +137,6 @@ __global__ __launch_bounds__(256, (MBMAX <= 4) ? 2 : 1) void linear_stream_fwd_k
     const bool vec = (c16 + 3 < rw) && (ncol + 3 < N) && ((ncol & 3) == 0) && ((ldz & 3) == 0) && ((reinterpret_cast<uintptr_t>(z) & 15) == 0);
     if constexpr (sizeof(TO) == 4) {
         if (tickets != nullptr) {
-            // ---- split K: publish the partial quad (the host guarantees whole, aligned quads: rw = 16, N % 64 == 0), take a ticket, and the last
-            // arriver of the column block sums the slabs in slab order, adds the bias and writes z
             float* const slab = reinterpret_cast<float*>(z) + (int64_t)blockIdx.y * slab_stride;
 #pragma unroll
             for (int i = 0; i < MBMAX; ++i) {
@@ -218,11 +155,6 @@ __global__ __launch_bounds__(256, (MBMAX <= 4) ? 2 : 1) void linear_stream_fwd_k
             __syncthreads();
             const unsigned nsp = gridDim.y;
             if (tk[0] != nsp - 1) return;
-            // last arriver.  Ordering: the producers' side is the hardware path -- sc1 write-through stores, drained by vmcnt(0) and a
-            // workgroup barrier BEFORE the ticket atomic is issued, so the slabs are at the device coherence point when the ticket moves (a RELEASE
-            // on the ticket would add a whole-L2 write-back per workgroup: round 3 measured that at more than the second launch it replaces); the
-            // consumer's side is made explicit: an agent-scope ACQUIRE fence (one L2 / vector-cache invalidate per column block) ahead of the
-            // slab loads, which are agent-scope atomics the compiler may not hoist above it
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             if (threadIdx.x == 0) __hip_atomic_store(tickets + blockIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm for the next launch
 #pragma unroll
@@ -272,17 +204,6 @@ __global__ __launch_bounds__(256, (MBMAX <= 4) ? 2 : 1) void linear_stream_fwd_k
     }
 }
 
-// rows of W per wave: the count in 8 .. 16 that covers N in the fewest whole rounds of the 256 CUs (cost = rounds x rows per workgroup; ties
-// go to the larger block).  N = 14336: 14 (256 workgroups instead of 224); N = 28672: 14 (512 = two rounds instead of 448 = 1.75).
-inline int stream_rows_per_wave(int N) {
-    int best = 16, best_cost = ((((N + 63) / 64) + 255) / 256) * 16;
-    for (int rw = 15; rw >= 8; --rw) {
-        const int wgs = (N + 4 * rw - 1) / (4 * rw), cost = ((wgs + 255) / 256) * rw;
-        if (cost < best_cost) { best = rw; best_cost = cost; }
-    }
-    return best;
-}
-
 // =====================================================================================================================
 // Redistribution half of the eps-rule in the same regime: c[M, Kout] = s[M, N] . W[N, Kout] from the STORED weight (contraction over W's
 // rows; ref lxt/explicit/functional.py:355-364, rules.py:206-222), M <= 64 rows.
@@ -312,7 +233,6 @@ __global__ __launch_bounds__(256, 1) void linear_stream_dgrad_kernel(
     unsigned* __restrict__ tickets, void* __restrict__ fin, int64_t ldf, int fin_f32) {
     constexpr int OPS = 4 + (SC ? 2 : 1) * MBMAX;        // VMEM operations per tile and wave
     constexpr int WSLOT = 4096, SSLOT = MBMAX * 1024, SLOT = WSLOT + (SC ? 2 : 1) * SSLOT;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int cb = blockIdx.x, sp = blockIdx.y;
@@ -455,21 +375,13 @@ __global__ __launch_bounds__(256, 1) void linear_stream_dgrad_kernel(
             for (int w2 = 1; w2 < 4; ++w2) v += red[((w2 * MBMAX + i) * 4 + wave) * 64 + lane];
             TO* dst = c + (int64_t)m * ldc + col;
             if constexpr (sizeof(TO) == 4) {
-                if (tickets != nullptr) {                // slab of the in-kernel reduction: agent-scope stores (write-through: visible to the last
-                    uint64_t* d8 = reinterpret_cast<uint64_t*>(dst);        // arriver's agent-scope loads whatever XCD it runs on)
-                    const f32x2 lo = {v[0], v[1]}, hi2 = {v[2], v[3]};
-                    __hip_atomic_store(d8, __builtin_bit_cast(uint64_t, lo), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(d8 + 1, __builtin_bit_cast(uint64_t, hi2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (tickets != nullptr) {                // slab of the in-kernel reduction
+                    ls_publish_quad(dst, v);
                     continue;
                 }
             }
-            if (col + 3 < Kout && (ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(c) & 15) == 0) {
-                if constexpr (sizeof(TO) == 4) *reinterpret_cast<f32x4*>(dst) = v;
-                else {
-                    bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-                    *reinterpret_cast<bf16x4*>(dst) = o;
-                }
-            } else {
+            if (col + 3 < Kout && (ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(c) & 15) == 0) ls_store_quad(dst, 0, sizeof(TO) == 4, v);
+            else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
                     if (col + e < Kout) dst[e] = from_f32<TO>(v[e]);
@@ -477,45 +389,17 @@ __global__ __launch_bounds__(256, 1) void linear_stream_dgrad_kernel(
         }
     }
     // ---- in-kernel reduction of the contraction splits (round 5; replaces the second launch: ~1.5 us of kernel boundary + 3.4-5.6 us of reduce kernel
-    // for 1-5 MB of slabs).  Every split's workgroup publishes its fp32 partial tile write-through (sc0 sc1 stores, drained), takes a ticket of
-    // its column block; the LAST arriver (ticket == splits - 1; it re-arms the word to 0 for the next launch) sums the slabs in
-    // slab order -- its own from memory as well, so the result does not depend on who arrives last -- and writes the output.  Other workgroups'
-    // slabs are read with sc0 sc1 loads: lines this workgroup's XCD never held in this launch (MI355X_MICROARCH.md: "sc0 sc1 stores and loads both
-    // sides" is a valid inter-workgroup form on non-coherent per-XCD L2s).
+    // for 1-5 MB of slabs): the last-arriver protocol of linear_stream.hpp on the column block's slabs, `red` being the LDS no longer read.  Other
+    // workgroups' slabs are read with sc0 sc1 loads: lines this workgroup's XCD never held in this launch (MI355X_MICROARCH.md: "sc0 sc1 stores and
+    // loads both sides" is a valid inter-workgroup form on non-coherent per-XCD L2s).
     if constexpr (sizeof(TO) == 4) {
         if (tickets != nullptr) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();                              // every wave's slab stores have left; `red` is no longer read
-            unsigned* tk = reinterpret_cast<unsigned*>(smem);
-            if (threadIdx.x == 0) tk[0] = __hip_atomic_fetch_add(tickets + cb, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __syncthreads();
-            const unsigned nsp = gridDim.y;
-            if (tk[0] != nsp - 1) return;
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");          // (see lrp_linear_stream_fwd_tk's last arriver above)
-            if (threadIdx.x == 0) __hip_atomic_store(tickets + cb, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // all arrivals of this launch are in: re-arm
+            if (!ls_last_arriver(tickets + cb)) return;
 #pragma unroll
             for (int i = 0; i < MBMAX; ++i) {
                 const int m = 16 * i + i16;
-                if (i < nb && m < M) {
-                    // (compiler-visible agent-scope loads, NOT inline asm: an asm load's destination registers are unprotected until one's own
-                    // wait -- the register allocator re-used them for the next address while the load was in flight: a memory fault on the box)
-                    const float* src = reinterpret_cast<const float*>(c0) + (int64_t)m * ldc + col;
-                    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int k = 0; k < 8; ++k)
-                        if (k < (int)nsp) {
-                            uint64_t* s8 = reinterpret_cast<uint64_t*>(const_cast<float*>(src + (int64_t)k * slab_stride));
-                            const f32x2 lo = __builtin_bit_cast(f32x2, __hip_atomic_load(s8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                            const f32x2 hi2 = __builtin_bit_cast(f32x2, __hip_atomic_load(s8 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                            const f32x4 pk = {lo[0], lo[1], hi2[0], hi2[1]};
-                            v = (k == 0) ? pk : v + pk;
-                        }
-                    if (fin_f32) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(fin) + (int64_t)m * ldf + col) = v;
-                    else {
-                        bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-                        *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(fin) + (int64_t)m * ldf + col) = o;
-                    }
-                }
+                if (i < nb && m < M)
+                    ls_store_quad(fin, (int64_t)m * ldf + col, fin_f32, ls_sum_quad(reinterpret_cast<const float*>(c0) + (int64_t)m * ldc + col, slab_stride));
             }
         }
     }
@@ -529,23 +413,10 @@ inline int dgrad_splits(int N, int Kout) {
     return 0;
 }
 
-// K splits of the forward for narrow weights: the smallest count in {2, 3, 4, 6, 8} that puts 192 ... 1024 workgroups of 64 rows on the chip with
-// whole 8-tile rings per split (1: the full-K form applies; 0: neither does)
-inline int fwd_splits(int N, int K) {
-    if (N < 1 || K < 512 || (K % 512)) return 0;
-    const int wgs = (N + 63) / 64;
-    if (wgs >= 192) return wgs <= 1024 ? 1 : 0;
-    if (N % 64) return 0;                                 // whole quads per lane in the slabs: 16 rows per wave
-    for (int s_ : {2, 3, 4, 6, 8})
-        if (wgs * s_ >= 192 && wgs * s_ <= 1024 && (K % (512 * s_)) == 0) return s_;
-    return 0;
-}
-
 template <typename TO, int MBMAX>
 int launch_stream(const void* x, const void* W, const void* bias, void* z, int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldz,
                   hipStream_t st) {
-    using C = LSCfg<MBMAX>;
-    const size_t lds = (size_t)C::NBUF * C::XTILE + 4 * (size_t)LS_WD * 2048;        // x ring + four wave-private W rings
+    const size_t lds = ls_fwd_lds<LSPCfg<MBMAX>>();
     auto kern = linear_stream_fwd_kernel<TO, MBMAX>;
     LRP_SET_MAX_LDS(kern, lds);
     const int rw = stream_rows_per_wave(N);
@@ -558,8 +429,7 @@ int launch_stream(const void* x, const void* W, const void* bias, void* z, int M
 template <int MBMAX>
 int launch_stream_split(const void* x, const void* W, const void* bias, void* z, int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldz,
                         int out_f32, int splits, void* ws, unsigned* tickets, hipStream_t st) {
-    using C = LSCfg<MBMAX>;
-    const size_t lds = (size_t)C::NBUF * C::XTILE + 4 * (size_t)LS_WD * 2048;
+    const size_t lds = ls_fwd_lds<LSPCfg<MBMAX>>();
     auto kern = linear_stream_fwd_kernel<float, MBMAX>;
     LRP_SET_MAX_LDS(kern, lds);
     hipLaunchKernelGGL(kern, dim3(N / 64, splits), dim3(256), lds, st, (const bf16_t*)x, (const bf16_t*)W, (float*)ws, (const bf16_t*)bias, M, N, K, ldx,
@@ -567,20 +437,7 @@ int launch_stream_split(const void* x, const void* W, const void* bias, void* z,
     return lrp_check_launch();
 }
 
-template <typename TO>
-int launch_stream_m(const void* x, const void* W, const void* bias, void* z, int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldz,
-                    hipStream_t st) {
-    const int nb = (M + 15) / 16;
-    if (nb <= 2) return launch_stream<TO, 2>(x, W, bias, z, M, N, K, ldx, ldw, ldz, st);
-    if (nb <= 4) return launch_stream<TO, 4>(x, W, bias, z, M, N, K, ldx, ldw, ldz, st);
-    return launch_stream<TO, 8>(x, W, bias, z, M, N, K, ldx, ldw, ldz, st);
-}
-
 }  // namespace
-
-// the two policies above for the kernel's quantised twin (linear_stream_q.hip): one definition, so the twin splits and blocks exactly alike
-int lrp_stream_rows_per_wave(int N) { return stream_rows_per_wave(N); }
-int lrp_stream_fwd_splits(int N, int K) { return fwd_splits(N, K); }
 
 // can lrp_linear_stream_fwd serve the problem, and is it the right kernel for it?  bf16, 1 <= M <= 128 rows (every workgroup re-reads x from
 // L2: beyond that the x traffic outgrows the weight's), K a multiple of 512 (the 8-tile ring), operands below 2^31 bytes, and enough 64-row
@@ -614,13 +471,16 @@ extern "C" int lrp_linear_stream_fwd_tk(const void* x, const void* W, const void
     const int splits = (ws && tickets) ? fwd_splits(N, K) : 1;          // without the scratch: the full-K form, whatever the workgroup count
     if (splits > 1) {
         if ((reinterpret_cast<uintptr_t>(z) & 15) || (ldz % 4) || (reinterpret_cast<uintptr_t>(ws) & 15)) return LRP_EALIGN;
-        const int nb = (M + 15) / 16, f32o = out_dtype == LRP_F32 ? 1 : 0;
-        if (nb <= 2) return launch_stream_split<2>(x, W, bias, z, M, N, K, ldx, ldw, ldz, f32o, splits, ws, (unsigned*)tickets, st);
-        if (nb <= 4) return launch_stream_split<4>(x, W, bias, z, M, N, K, ldx, ldw, ldz, f32o, splits, ws, (unsigned*)tickets, st);
-        return launch_stream_split<8>(x, W, bias, z, M, N, K, ldx, ldw, ldz, f32o, splits, ws, (unsigned*)tickets, st);
+        const int f32o = out_dtype == LRP_F32 ? 1 : 0;
+        return ls_with_row_blocks(M, [&](auto mb) {
+            return launch_stream_split<decltype(mb)::value>(x, W, bias, z, M, N, K, ldx, ldw, ldz, f32o, splits, ws, (unsigned*)tickets, st);
+        });
     }
-    if (out_dtype == LRP_F32) return launch_stream_m<float>(x, W, bias, z, M, N, K, ldx, ldw, ldz, st);
-    return launch_stream_m<bf16_t>(x, W, bias, z, M, N, K, ldx, ldw, ldz, st);
+    return ls_with_row_blocks(M, [&](auto mb) {
+        constexpr int MB = decltype(mb)::value;
+        if (out_dtype == LRP_F32) return launch_stream<float, MB>(x, W, bias, z, M, N, K, ldx, ldw, ldz, st);
+        return launch_stream<bf16_t, MB>(x, W, bias, z, M, N, K, ldx, ldw, ldz, st);
+    });
 }
 
 extern "C" int lrp_linear_stream_fwd(const void* x, const void* W, const void* bias, void* z, int M, int N, int K, int64_t ldx, int64_t ldw,

@@ -4,10 +4,11 @@
 //
 // BIT IDENTITY with lrp_mxfp4_dequant + lrp_linear_stream_fwd_tk is the contract, and the construction is the one of moe_gemm.hpp: the codes are
 // decoded between their global load and an LDS write, and the decoded W tile lands in the SAME wave-private LDS image the plain kernel's
-// LDS-DMA staging produces ([8 slots][16 rows][128 B], 16-byte chunk c of row r at c ^ (r & 7)).  Everything after that image -- the x ring, the
-// ds_read_b128 fragments, the v_mfma_f32_16x16x32_bf16 per accumulator in ascending K, the K splits (kt_per_split, slab order, tickets) and the
-// epilogue -- is the plain kernel's, statement for statement; every decoded value is exact in bf16.  Policy (rows per wave, splits) is read from
-// linear_stream.hip, not restated.
+// LDS-DMA staging produces ([8 slots][16 rows][128 B], 16-byte chunk c of row r at c ^ (r & 7)).  Everything after that image is
+// linear_stream.hpp's, the code the plain kernel runs: the fragment addresses, a K tile's multiply (ls_tile_mma) and the policy
+// (stream_rows_per_wave, fwd_splits, the row-block ladder).  Two parts the plain kernel has written out in linear_stream.hip, and bit identity
+// holds only while they say the same there and here: the x stager (stage_x below) and the epilogue with its K splits (ls_fwd_epilogue: bias,
+// slab order, tickets).  A CHANGE TO EITHER IS MADE IN BOTH PLACES; tests/test_mxfp4_stream_gpu.py compares the two kernels bit for bit.
 //
 // What differs is how W travels:
 //   * a GROUP is 4 K tiles = 256 K elements = one 128-byte line of codes per row.  A wave instruction loads 8 rows x 8 lanes x 16 B: FULL lines
@@ -22,32 +23,22 @@
 //     hand-counted ds_read is outstanding).  The ring is wave-private and a wave's LDS operations complete in order: no barrier guards it;
 //   * nothing is peeled: a load past the split's K range, or of a row past rw / N (x: past M), goes out with a voffset beyond num_records -- it
 //     fetches nothing and returns zero -- so every wait count is one constant.
-#include "common.hpp"
+#include "linear_stream.hpp"
 
-int lrp_stream_rows_per_wave(int N);          // linear_stream.hip: the plain kernel's policy (stream_rows_per_wave, fwd_splits)
-int lrp_stream_fwd_splits(int N, int K);
 extern "C" int lrp_linear_stream_ok(int M, int N, int K, int64_t ldx, int64_t ldw);
 
 namespace {
 
-constexpr int LQ_KT = 64;      // K elements per K tile
-constexpr int LQ_WD = 8;       // LDS ring slots per wave: two halves of one group each
-constexpr int LQ_GT = 4;       // K tiles per group (one 128-byte line of codes per row)
+constexpr int LQ_GT = 4;       // K tiles per group (one 128-byte line of codes per row); the LDS ring's LS_WD slots are two halves of one group each
 constexpr int LQ_RD = 8;       // groups of codes in registers per wave
-constexpr int LQ_OOB = 0x40000000;
-typedef __attribute__((address_space(3))) void* lq_lds_ptr_t;
 
-template <int MBMAX> struct LQCfg {
-    // x prefetch distance in K tiles: the plain kernel's 3, but 2 at MBMAX = 2 -- a ring of 4 x 4 KiB beside the 64 KiB of W rings is 80 KiB, HALF
-    // the CU's LDS, so two workgroups share a CU.  At a quarter of the plain kernel's bytes per tile the kernel is bound by the serial chain of a
-    // K tile (barrier, fragment reads, dependent MFMAs, decode) at one wave per SIMD, not by HBM; a second resident workgroup overlaps two chains
-    // (measured: [28672, 4096], 512 workgroups, 41.4 -> 33.5 us; staging x 11 tiles ahead instead moved nothing)
-    static constexpr int XD = MBMAX == 2 ? 2 : 3;
-    static constexpr int NBUF = XD + 2;                            // LDS ring: tile t + XD is written while tiles t - 1, t may still be read
-    static constexpr int P = MBMAX / 2;                            // 1-KiB staging pieces (8 rows x 128 B) per wave per K tile
-    static constexpr int XTILE = MBMAX * 16 * 128;                 // bytes of one x tile
-    static constexpr int BS = MBMAX < 4 ? MBMAX : 4;               // row blocks per LDS read batch
-    static constexpr int NBATCH = MBMAX / BS;
+// x prefetch distance in K tiles: the plain kernel's 3, but 2 at MBMAX = 2 -- a ring of 4 x 4 KiB beside the 64 KiB of W rings is 80 KiB, HALF
+// the CU's LDS, so two workgroups share a CU.  At a quarter of the plain kernel's bytes per tile the kernel is bound by the serial chain of a
+// K tile (barrier, fragment reads, dependent MFMAs, decode) at one wave per SIMD, not by HBM; a second resident workgroup overlaps two chains
+// (measured: [28672, 4096], 512 workgroups, 41.4 -> 33.5 us; staging x 11 tiles ahead instead moved nothing)
+template <int MBMAX> struct LQCfg : LSCfg<MBMAX, MBMAX == 2 ? 2 : 3> {
+    using B = LSCfg<MBMAX, MBMAX == 2 ? 2 : 3>;
+    static constexpr int XD = B::XD, P = B::P;
     // is there a group end (its 4 loads: 2 codes, 2 scales) between the x stages of tiles u + XD and u + 1 + XD?  After tile u = 3 (mod 4)
     static constexpr bool group_end(int u) { return ((u % LQ_GT) + LQ_GT) % LQ_GT == LQ_GT - 1; }
     // VMEM operations younger than x(t) at the wait of tile t = s4 (mod 4): the x stages of tiles t - XD + 1 .. t, and the loads of the group
@@ -67,15 +58,6 @@ template <int MBMAX> struct LQCfg {
     static constexpr int NGE = ge_upto(XD - 1);
 };
 
-template <int V> struct LQI { static constexpr int value = V; };
-template <int I, int N, typename F> LRP_DEVICE void lq_for(F&& f) {
-    if constexpr (I < N) {
-        f(LQI<I>{});
-        lq_for<I + 1, N>(static_cast<F&&>(f));
-    }
-}
-
-#define LQ_DSRD(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 // loads hipcc does not count (file header): the destination is named again, "+v", by the wait that retires it, before anything reads it
 #define LQ_LD16(dst, vo, rs, so) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen nt" : "=v"(dst) : "v"(vo), "s"(rs), "s"(so) : "memory")
 #define LQ_LD4(dst, vo, rs, so) asm volatile("buffer_load_dword %0, %1, %2, %3 offen" : "=v"(dst) : "v"(vo), "s"(rs), "s"(so) : "memory")
@@ -92,12 +74,11 @@ __global__ __launch_bounds__(256, 1) void linear_stream_q_fwd_kernel(
     const bf16_t* __restrict__ bias, int M, int N, int K, int64_t ldx, int64_t ldc, int64_t ldsc, int64_t ldz, int rw, int kt_per_split,
     int64_t slab_stride, unsigned* __restrict__ tickets, void* __restrict__ fin, int64_t ldf, int fin_f32) {
     using C = LQCfg<MBMAX>;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int n0 = blockIdx.x * (4 * rw);
     const int kt0 = (int)blockIdx.y * kt_per_split;
-    const int nkt = (gridDim.y > 1) ? kt_per_split : K / LQ_KT;
+    const int nkt = (gridDim.y > 1) ? kt_per_split : K / LS_KT;
     const int nG = nkt / LQ_GT;                                       // even: K (and a split's share) is a multiple of 512
     const int g0 = kt0 / LQ_GT;
     int nb = (M + 15) >> 4;
@@ -112,8 +93,8 @@ __global__ __launch_bounds__(256, 1) void linear_stream_q_fwd_kernel(
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         const bool live = (8 * p + prow < rw) && (wrow0 + 8 * p + prow < N);         // rows rw .. 15 and rows past N: never fetched, never stored
-        voC[p] = live ? (int)((int64_t)(wrow0 + 8 * p + prow) * ldc) + (pslot << 4) : LQ_OOB;
-        voS[p] = live ? (int)((int64_t)(wrow0 + 8 * p + prow) * ldsc) + ((pslot >> 2) << 2) : LQ_OOB;
+        voC[p] = live ? (int)((int64_t)(wrow0 + 8 * p + prow) * ldc) + (pslot << 4) : LS_OOB;
+        voS[p] = live ? (int)((int64_t)(wrow0 + 8 * p + prow) * ldsc) + ((pslot >> 2) << 2) : LS_OOB;
     }
     const uint32_t esh = (uint32_t)((pslot & 3) << 3);                 // the lane's scale byte inside its 4-byte load
     u32x4 cq[LQ_RD][2];
@@ -126,13 +107,13 @@ __global__ __launch_bounds__(256, 1) void linear_stream_q_fwd_kernel(
         const int soc = (g0 + g) * 128, sos = (g0 + g) * 8;
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-            const int vc = in ? voC[p] : LQ_OOB, vs = in ? voS[p] : LQ_OOB;
+            const int vc = in ? voC[p] : LS_OOB, vs = in ? voS[p] : LS_OOB;
             LQ_LD16(cq[j][p], vc, rsC, soc);
             LQ_LD4(sq[j][p], vs, rsS, sos);
         }
     };
     // ---- the decoded image: the lane's 32 elements are K tile (l & 7) >> 1 of the group, chunks 4 (l & 1) + d (d = code word) of row 8 p + prow
-    char* const wring = smem + C::NBUF * C::XTILE + wave * (LQ_WD * 2048);       // [LQ_WD tiles][16 rows][128 B], wave-private
+    char* const wring = smem + C::NBUF * C::XTILE + wave * (LS_WD * 2048);       // [LS_WD tiles][16 rows][128 B], wave-private
     const uint32_t wst = (uint32_t)((pslot >> 1) * 2048 + prow * 128) + (uint32_t)((((pslot & 1) << 2) ^ prow) << 4);
     // quarter d (code word d of both pieces) of register slot j into ring half `half`
     auto decode_q = [&](auto jc, auto dc, auto hc) {
@@ -146,46 +127,43 @@ __global__ __launch_bounds__(256, 1) void linear_stream_q_fwd_kernel(
         }
     };
 
-    // ---- x: LDS-DMA pieces of 8 rows x 128 B; lane l -> row l >> 3, LDS slot l & 7, source chunk slot ^ (row & 7)
+    // ---- x: past the split's K range nothing is fetched
     const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)(((int64_t)(M - 1) * ldx + K) * 2), 0x00020000);
     const int voX = (int)(prow * ldx * 2) + ((pslot ^ prow) << 4);
+    // (linear_stream.hip's stage_x + the range test: they change together)
     auto stage_x = [&](int kt, int buf) {
-        const int vo = kt < nkt ? voX : LQ_OOB;
+        const int vo = kt < nkt ? voX : LS_OOB;
 #pragma unroll
         for (int p = 0; p < C::P; ++p) {
             const int q = wave * C::P + p;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lq_lds_ptr_t)(smem + buf * C::XTILE + q * 1024), 16, vo,
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (ls_lds_ptr_t)(smem + buf * C::XTILE + q * 1024), 16, vo,
                                                      (int)((int64_t)(8 * q) * ldx * 2) + (kt + kt0) * 128, 0, 0);
         }
     };
-    // fragment of row block i, k-step ks: row 16 i + (l & 15), chunk (4 ks + (l >> 4)) ^ (row & 7)
-    const uint32_t lds0 = (uint32_t)(uintptr_t)(lq_lds_ptr_t)smem;
-    uint32_t cX[2];
+    uint32_t cX[2], cW[2];
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) cX[ks] = lds0 + (uint32_t)((lane & 15) * 128) + (uint32_t)((((4 * ks + (lane >> 4)) ^ (lane & 7))) << 4);
-    // W fragment of ring slot s, k-step ks: same image as x (row l & 15 of the wave's 16 rows)
-    uint32_t cW[2];
+    for (int ks = 0; ks < 2; ++ks) cX[ks] = ls_frag_x(lane, ks);
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) cW[ks] = cX[ks] + (uint32_t)(C::NBUF * C::XTILE + wave * (LQ_WD * 2048));
+    for (int ks = 0; ks < 2; ++ks) cW[ks] = cX[ks] + ls_w_ring<C>(wave);
     f32x4 acc[MBMAX];
 #pragma unroll
     for (int i = 0; i < MBMAX; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // ---- prologue: codes(0 .. RD - NGE); group 0 decoded whole; x(0 .. XD - 1) with codes(RD - NGE + 1 .. RD) at the group-end places between
     // them (the last one, behind x(XD - 1), refills slot 0) -- the order the steady state continues
-    lq_for<0, LQ_RD - C::NGE + 1>([&](auto jc) { load_g(jc, decltype(jc)::value); });
+    ls_for<0, LQ_RD - C::NGE + 1>([&](auto jc) { load_g(jc, decltype(jc)::value); });
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt vmcnt(%[cnt])" : "+v"(cq[0][0]), "+v"(cq[0][1]), "+v"(sq[0][0]), "+v"(sq[0][1]) : [cnt] "n"(4 * (LQ_RD - C::NGE)) : "memory");
     __builtin_amdgcn_sched_barrier(0);
-    lq_for<0, 4>([&](auto dc) { decode_q(LQI<0>{}, dc, LQI<0>{}); });
+    ls_for<0, 4>([&](auto dc) { decode_q(LSI<0>{}, dc, LSI<0>{}); });
     __builtin_amdgcn_sched_barrier(0);
-    lq_for<0, C::XD>([&](auto vc) {
+    ls_for<0, C::XD>([&](auto vc) {
         constexpr int v = decltype(vc)::value;
         stage_x(v, v);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (C::group_end(v - C::XD)) {
             constexpr int g = LQ_RD - C::NGE + C::ge_upto(v);
-            load_g(LQI<g % LQ_RD>{}, g);
+            load_g(LSI<g % LQ_RD>{}, g);
             __builtin_amdgcn_sched_barrier(0);
         }
     });
@@ -203,154 +181,37 @@ __global__ __launch_bounds__(256, 1) void linear_stream_q_fwd_kernel(
             asm volatile("s_waitcnt vmcnt(%[cnt])" :: [cnt] "n"(C::vmc(s4)) : "memory");
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        const uint32_t xb = (uint32_t)((t % C::NBUF) * C::XTILE);
-        const uint32_t a0 = cX[0] + xb, a1 = cX[1] + xb;
-        u32x4 wq0, wq1;
-        LQ_DSRD(wq0, cW[0], s * 2048);
-        LQ_DSRD(wq1, cW[1], s * 2048);
-        // units u = (ks, batch): BS fragment reads each, read one unit ahead
-        u32x4 xf[2][C::BS];
-        constexpr int U = 2 * C::NBATCH;
-        auto issue = [&](auto uc) {
-            constexpr int u = decltype(uc)::value, ks = u / C::NBATCH, b = u % C::NBATCH;
-            (void)&xf; (void)&a0; (void)&a1;
-            lq_for<0, C::BS>([&](auto ic) {
-                constexpr int i = decltype(ic)::value;
-                (void)&xf; (void)&a0; (void)&a1;
-                if constexpr (ks == 0) LQ_DSRD(xf[u & 1][i], a0, (b * C::BS + i) * 2048);
-                else LQ_DSRD(xf[u & 1][i], a1, (b * C::BS + i) * 2048);
-            });
-        };
-        issue(LQI<0>{});
-        if constexpr (C::BS == 4) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(wq0), "+v"(wq1));
-        else asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(wq0), "+v"(wq1));
-        const bf16x8 w0 = __builtin_bit_cast(bf16x8, wq0), w1 = __builtin_bit_cast(bf16x8, wq1);
-        lq_for<0, U>([&](auto uc) {
-            constexpr int u = decltype(uc)::value, ks = u / C::NBATCH, b = u % C::NBATCH;
-            (void)&xf;
-            if constexpr (u + 1 < U) {
-                issue(LQI<u + 1>{});
-                if constexpr (C::BS == 4) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(xf[u & 1][0]), "+v"(xf[u & 1][1]), "+v"(xf[u & 1][2]), "+v"(xf[u & 1][3]));
-                else asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(xf[u & 1][0]), "+v"(xf[u & 1][1]));
-            } else {
-                if constexpr (C::BS == 4) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xf[u & 1][0]), "+v"(xf[u & 1][1]), "+v"(xf[u & 1][2]), "+v"(xf[u & 1][3]));
-                else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xf[u & 1][0]), "+v"(xf[u & 1][1]));
-            }
-            lq_for<0, C::BS>([&](auto ic) {
-                constexpr int i = decltype(ic)::value, blk = b * C::BS + i;
-                if (blk < nb)
-                    acc[blk] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ks == 0 ? w0 : w1, __builtin_bit_cast(bf16x8, xf[u & 1][i]), acc[blk], 0, 0, 0);
-            });
-            __builtin_amdgcn_sched_barrier(0);
-        });
+        ls_tile_mma<C>(cX, cW, (uint32_t)((t % C::NBUF) * C::XTILE), LSI<s>{}, acc, nb);
         // no hand-counted ds_read is outstanding here (the last unit waited lgkmcnt(0)): the compiler's own ds_writes cannot disturb a count
-        decode_q(LQI<j1>{}, s4c, LQI<(j1 & 1)>{});
+        decode_q(LSI<j1>{}, s4c, LSI<(j1 & 1)>{});
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (s4 == LQ_GT - 1) {
-            load_g(LQI<j1>{}, t / LQ_GT + 1 + LQ_RD);                 // slot j1 is decoded whole: refill it, LQ_RD groups ahead
+            load_g(LSI<j1>{}, t / LQ_GT + 1 + LQ_RD);                 // slot j1 is decoded whole: refill it, LQ_RD groups ahead
             __builtin_amdgcn_sched_barrier(0);
         }
     };
 
     for (int G = 0; G < nG; G += LQ_RD)
-        lq_for<0, LQ_RD / 2>([&](auto hc) {
+        ls_for<0, LQ_RD / 2>([&](auto hc) {
             constexpr int h = decltype(hc)::value;
             if (G + 2 * h < nG) {
-                lq_for<0, LQ_GT>([&](auto s4c) { tile(LQI<2 * h>{}, s4c, (G + 2 * h) * LQ_GT + decltype(s4c)::value); });
-                lq_for<0, LQ_GT>([&](auto s4c) { tile(LQI<2 * h + 1>{}, s4c, (G + 2 * h + 1) * LQ_GT + decltype(s4c)::value); });
+                ls_for<0, LQ_GT>([&](auto s4c) { tile(LSI<2 * h>{}, s4c, (G + 2 * h) * LQ_GT + decltype(s4c)::value); });
+                ls_for<0, LQ_GT>([&](auto s4c) { tile(LSI<2 * h + 1>{}, s4c, (G + 2 * h + 1) * LQ_GT + decltype(s4c)::value); });
             }
         });
     // the loads still outstanding fetched nothing (past the K range); they are retired before the registers and the LDS go back
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-    // ---- epilogue (the plain kernel's): lane holds z[16 i + (l & 15)][n0 + rw w + 4 (l >> 4) + e]
-    const int c16 = 4 * (lane >> 4);                                  // column of the wave's 16-row block: live while < rw
-    const int ncol = n0 + rw * wave + c16;
-    f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-    if (bias) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (c16 + e < rw && ncol + e < N) bv[e] = to_f32(bias[ncol + e]);
-    }
-    const bool vec = (c16 + 3 < rw) && (ncol + 3 < N) && ((ncol & 3) == 0) && ((ldz & 3) == 0) && ((reinterpret_cast<uintptr_t>(z) & 15) == 0);
-    if constexpr (sizeof(TO) == 4) {
-        if (tickets != nullptr) {
-            // ---- split K: the slab / ticket protocol of linear_stream_fwd_kernel (ordering argument: there), same slab order
-            float* const slab = reinterpret_cast<float*>(z) + (int64_t)blockIdx.y * slab_stride;
-#pragma unroll
-            for (int i = 0; i < MBMAX; ++i) {
-                const int m = 16 * i + (lane & 15);
-                if (i < nb && m < M) {
-                    uint64_t* d8 = reinterpret_cast<uint64_t*>(slab + (int64_t)m * ldz + ncol);
-                    const f32x2 lo = {acc[i][0], acc[i][1]}, hi2 = {acc[i][2], acc[i][3]};
-                    __hip_atomic_store(d8, __builtin_bit_cast(uint64_t, lo), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(d8 + 1, __builtin_bit_cast(uint64_t, hi2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();                              // every wave's slab stores have left; the LDS rings are no longer read
-            unsigned* tk = reinterpret_cast<unsigned*>(smem);
-            if (threadIdx.x == 0) tk[0] = __hip_atomic_fetch_add(tickets + blockIdx.x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __syncthreads();
-            const unsigned nsp = gridDim.y;
-            if (tk[0] != nsp - 1) return;
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            if (threadIdx.x == 0) __hip_atomic_store(tickets + blockIdx.x, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-arm for the next launch
-#pragma unroll
-            for (int i = 0; i < MBMAX; ++i) {
-                const int m = 16 * i + (lane & 15);
-                if (i < nb && m < M) {
-                    const float* src = reinterpret_cast<const float*>(z) + (int64_t)m * ldz + ncol;
-                    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int k = 0; k < 8; ++k)
-                        if (k < (int)nsp) {
-                            uint64_t* s8 = reinterpret_cast<uint64_t*>(const_cast<float*>(src + (int64_t)k * slab_stride));
-                            const f32x2 lo = __builtin_bit_cast(f32x2, __hip_atomic_load(s8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                            const f32x2 hi2 = __builtin_bit_cast(f32x2, __hip_atomic_load(s8 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                            const f32x4 pk = {lo[0], lo[1], hi2[0], hi2[1]};
-                            v = (k == 0) ? pk : v + pk;
-                        }
-                    v += bv;
-                    if (fin_f32) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(fin) + (int64_t)m * ldf + ncol) = v;
-                    else {
-                        bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-                        *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(fin) + (int64_t)m * ldf + ncol) = o;
-                    }
-                }
-            }
-            return;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < MBMAX; ++i) {
-        const int m = 16 * i + (lane & 15);
-        if (i < nb && m < M) {
-            const f32x4 v = acc[i] + bv;
-            TO* dst = z + (int64_t)m * ldz + ncol;
-            if (vec) {
-                if constexpr (sizeof(TO) == 4) *reinterpret_cast<f32x4*>(dst) = v;
-                else {
-                    bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-                    *reinterpret_cast<bf16x4*>(dst) = o;
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (c16 + e < rw && ncol + e < N) dst[e] = from_f32<TO>(v[e]);
-            }
-        }
-    }
+    ls_fwd_epilogue<TO, MBMAX>(acc, wave, n0, rw, nb, z, bias, M, N, ldz, slab_stride, tickets, fin, ldf, fin_f32);
 }
 
 template <typename TO, int MBMAX>
 int launch_q(const void* x, const void* codes, const void* scales, const void* bias, void* z, int M, int N, int K, int64_t ldx, int64_t ldc,
              int64_t ldsc, int64_t ldz, hipStream_t st) {
-    using C = LQCfg<MBMAX>;
-    const size_t lds = (size_t)C::NBUF * C::XTILE + 4 * (size_t)LQ_WD * 2048;        // x ring + four wave-private W rings
+    const size_t lds = ls_fwd_lds<LQCfg<MBMAX>>();
     auto kern = linear_stream_q_fwd_kernel<TO, MBMAX>;
     LRP_SET_MAX_LDS(kern, lds);
-    const int rw = lrp_stream_rows_per_wave(N);
+    const int rw = stream_rows_per_wave(N);
     hipLaunchKernelGGL(kern, dim3((N + 4 * rw - 1) / (4 * rw)), dim3(256), lds, st, (const bf16_t*)x, (const uint8_t*)codes, (const uint8_t*)scales,
                        (TO*)z, (const bf16_t*)bias, M, N, K, ldx, ldc, ldsc, ldz, rw, 0, (int64_t)0, (unsigned*)nullptr, (void*)nullptr, (int64_t)0, 0);
     return lrp_check_launch();
@@ -360,22 +221,12 @@ int launch_q(const void* x, const void* codes, const void* scales, const void* b
 template <int MBMAX>
 int launch_q_split(const void* x, const void* codes, const void* scales, const void* bias, void* z, int M, int N, int K, int64_t ldx, int64_t ldc,
                    int64_t ldsc, int64_t ldz, int out_f32, int splits, void* ws, unsigned* tickets, hipStream_t st) {
-    using C = LQCfg<MBMAX>;
-    const size_t lds = (size_t)C::NBUF * C::XTILE + 4 * (size_t)LQ_WD * 2048;
+    const size_t lds = ls_fwd_lds<LQCfg<MBMAX>>();
     auto kern = linear_stream_q_fwd_kernel<float, MBMAX>;
     LRP_SET_MAX_LDS(kern, lds);
     hipLaunchKernelGGL(kern, dim3(N / 64, splits), dim3(256), lds, st, (const bf16_t*)x, (const uint8_t*)codes, (const uint8_t*)scales, (float*)ws,
-                       (const bf16_t*)bias, M, N, K, ldx, ldc, ldsc, (int64_t)N, 16, K / LQ_KT / splits, (int64_t)M * N, tickets, z, ldz, out_f32);
+                       (const bf16_t*)bias, M, N, K, ldx, ldc, ldsc, (int64_t)N, 16, K / LS_KT / splits, (int64_t)M * N, tickets, z, ldz, out_f32);
     return lrp_check_launch();
-}
-
-template <typename TO>
-int launch_q_m(const void* x, const void* codes, const void* scales, const void* bias, void* z, int M, int N, int K, int64_t ldx, int64_t ldc,
-               int64_t ldsc, int64_t ldz, hipStream_t st) {
-    const int nb = (M + 15) / 16;
-    if (nb <= 2) return launch_q<TO, 2>(x, codes, scales, bias, z, M, N, K, ldx, ldc, ldsc, ldz, st);
-    if (nb <= 4) return launch_q<TO, 4>(x, codes, scales, bias, z, M, N, K, ldx, ldc, ldsc, ldz, st);
-    return launch_q<TO, 8>(x, codes, scales, bias, z, M, N, K, ldx, ldc, ldsc, ldz, st);
 }
 
 // the shape the kernel can address: the plain entry's domain on the dequantised matrix, the pitches at least a row, byte offsets inside 2^30
@@ -401,14 +252,17 @@ extern "C" int lrp_linear_stream_fwd_q(const void* x, const void* codes, const v
     if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(codes) & 15) || (ldx % 8) || (ldc % 16)) return LRP_EALIGN;
     if ((reinterpret_cast<uintptr_t>(scales) & 3) || (ldsc % 4)) return LRP_EALIGN;
     hipStream_t st = (hipStream_t)stream;
-    const int splits = (ws && tickets) ? lrp_stream_fwd_splits(N, K) : 1;          // without the scratch: the full-K form, as in the plain entry
+    const int splits = (ws && tickets) ? fwd_splits(N, K) : 1;          // without the scratch: the full-K form, as in the plain entry
     if (splits > 1) {
         if ((reinterpret_cast<uintptr_t>(z) & 15) || (ldz % 4) || (reinterpret_cast<uintptr_t>(ws) & 15)) return LRP_EALIGN;
-        const int nb = (M + 15) / 16, f32o = out_dtype == LRP_F32 ? 1 : 0;
-        if (nb <= 2) return launch_q_split<2>(x, codes, scales, bias, z, M, N, K, ldx, ldc, ldsc, ldz, f32o, splits, ws, (unsigned*)tickets, st);
-        if (nb <= 4) return launch_q_split<4>(x, codes, scales, bias, z, M, N, K, ldx, ldc, ldsc, ldz, f32o, splits, ws, (unsigned*)tickets, st);
-        return launch_q_split<8>(x, codes, scales, bias, z, M, N, K, ldx, ldc, ldsc, ldz, f32o, splits, ws, (unsigned*)tickets, st);
+        const int f32o = out_dtype == LRP_F32 ? 1 : 0;
+        return ls_with_row_blocks(M, [&](auto mb) {
+            return launch_q_split<decltype(mb)::value>(x, codes, scales, bias, z, M, N, K, ldx, ldc, ldsc, ldz, f32o, splits, ws, (unsigned*)tickets, st);
+        });
     }
-    if (out_dtype == LRP_F32) return launch_q_m<float>(x, codes, scales, bias, z, M, N, K, ldx, ldc, ldsc, ldz, st);
-    return launch_q_m<bf16_t>(x, codes, scales, bias, z, M, N, K, ldx, ldc, ldsc, ldz, st);
+    return ls_with_row_blocks(M, [&](auto mb) {
+        constexpr int MB = decltype(mb)::value;
+        if (out_dtype == LRP_F32) return launch_q<float, MB>(x, codes, scales, bias, z, M, N, K, ldx, ldc, ldsc, ldz, st);
+        return launch_q<bf16_t, MB>(x, codes, scales, bias, z, M, N, K, ldx, ldc, ldsc, ldz, st);
+    });
 }

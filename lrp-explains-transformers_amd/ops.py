@@ -1204,18 +1204,26 @@ def linear_stream_ok(x2, W):
     return bool(STREAM_FWD_SPLITS or lib.lrp_linear_stream_fwd_splits(x2.shape[0], W.shape[0], x2.shape[1]) == 1)
 
 
+def _stream_fwd_buffers(x2, N, out, out_dtype):
+    """-> (out, slab workspace, tickets) of the streaming forward and its MXFP4 form: the output allocated when not given, and for narrow
+    weights (K splits, slabs summed in-kernel; one split policy for both forms: bit identity needs it) the scratch, else None / None"""
+    M, K = x2.shape
+    if out is None:
+        out = torch.empty(M, N, device=x2.device, dtype=out_dtype or x2.dtype)
+    need = lib.lrp_linear_stream_fwd_ws(M, N, K) if STREAM_FWD_SPLITS else 0
+    ws = workspace(need, x2) if need else None
+    ntk = lib.lrp_linear_stream_fwd_tickets(M, N, K) if need else 0
+    return out, ws, tickets(ntk, x2) if ntk else None
+
+
 def linear_stream_fwd(x2, W, bias=None, out=None, out_dtype=None):
     """z[M,N] = x2[M,K] @ W[N,K]^T (+ bias), M <= 256, in ONE launch: every workgroup streams 64 rows of W over the whole K range"""
     M, K = x2.shape
     N = W.shape[0]
     same(x2, W)
-    if out is None:
-        out = torch.empty(M, N, device=x2.device, dtype=out_dtype or x2.dtype)
-    need = lib.lrp_linear_stream_fwd_ws(M, N, K) if STREAM_FWD_SPLITS else 0      # narrow weights: K splits, slabs summed in-kernel (tickets)
-    ws = workspace(need, x2) if need else None
-    ntk = lib.lrp_linear_stream_fwd_tickets(M, N, K) if need else 0
+    out, ws, tk = _stream_fwd_buffers(x2, N, out, out_dtype)
     check(lib.lrp_linear_stream_fwd_tk(p(x2), p(W), p(aux(bias, x2, N)), p(out), M, N, K, x2.stride(0), W.stride(0), out.stride(0), dt(x2),
-                                       _DT[out.dtype], p(ws), p(tickets(ntk, x2) if ntk else None), stream()), "lrp_linear_stream_fwd_tk")
+                                       _DT[out.dtype], p(ws), p(tk), stream()), "lrp_linear_stream_fwd_tk")
     return out
 
 
@@ -1942,12 +1950,7 @@ def linear_stream_fwd_q(x2, codes, scales, bias=None, out=None, out_dtype=None):
     _mx_stream_operands(name, x2, codes, scales)
     M, K = x2.shape
     N = codes.shape[0]
-    if out is None:
-        out = torch.empty(M, N, device=x2.device, dtype=out_dtype or x2.dtype)
-    need = lib.lrp_linear_stream_fwd_ws(M, N, K) if STREAM_FWD_SPLITS else 0      # the plain entry's split policy: bit identity needs it
-    ws = workspace(need, x2) if need else None
-    ntk = lib.lrp_linear_stream_fwd_tickets(M, N, K) if need else 0
+    out, ws, tk = _stream_fwd_buffers(x2, N, out, out_dtype)
     check(lib.lrp_linear_stream_fwd_q(p(x2), p(codes), p(scales), p(aux(bias, x2, N)), p(out), M, N, K, x2.stride(0), codes.stride(0),
-                                      scales.stride(0), out.stride(0), dt(x2), _DT[out.dtype], p(ws), p(tickets(ntk, x2) if ntk else None),
-                                      stream()), name)
+                                      scales.stride(0), out.stride(0), dt(x2), _DT[out.dtype], p(ws), p(tk), stream()), name)
     return out
