@@ -546,4 +546,5 @@ int lrp_moe_gate_up_dgrad(const void* Agu, const void* Wgu, const int* plan, voi
 #include "lrp_hip_decode.h"
 #include "lrp_hip_decode_site.h"
 #include "lrp_hip_mxfp4_stream.h"
+#include "lrp_hip_sample.h"
 #endif /* LRP_HIP_H */

@@ -17,7 +17,7 @@ ERRORS = {-1: "LRP_EINVAL (bad argument)", -2: "LRP_EALIGN (pointer / leading di
           -3: "LRP_ESHAPE (unsupported shape)", -4: "LRP_ELAUNCH (HIP launch failed)"}
 
 _CTYPE = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
-          "void*": ctypes.c_void_p, "float*": ctypes.c_void_p, "int*": ctypes.c_void_p,
+          "void*": ctypes.c_void_p, "float*": ctypes.c_void_p, "int*": ctypes.c_void_p, "int64_t*": ctypes.c_void_p,
           "char*": ctypes.c_char_p}
 
 

@@ -528,6 +528,50 @@ def force_request(force_tokens, B, max_new_tokens, vocab, device):
     return forced.to(device=device, dtype=torch.int32)
 
 
+SampleSpec = collections.namedtuple("SampleSpec", "temperature top_k top_p min_p seeds streams")
+
+
+def sample_request(do_sample, temperature, top_k, top_p, min_p, seed, B, force_tokens):
+    """generate(do_sample=..., temperature=..., top_k=..., top_p=..., min_p=..., seed=...) -> None (greedy) or a SampleSpec: the scalars as
+    ops.sample_rows takes them, seeds int64 [B] and streams int32 [B] on the host.  seed an int: prompt b draws from (seed, stream b);
+    seed a list of B ints: prompt b draws from (seed[b], stream 0) -- its continuation then does not depend on the batch it sits in.
+    Seeds are taken modulo 2^64.  No device, no weights; ValueError before a kernel runs: a sampling argument or a seed without do_sample,
+    do_sample without seed or with force_tokens, temperature <= 0 or not finite, top_k not an int >= 0, top_p outside (0, 1], min_p outside
+    [0, 1], seed neither an int nor B ints."""
+    if not do_sample:
+        if (temperature, top_k, top_p, min_p) != (1.0, 0, 1.0, 0.0) or isinstance(top_k, bool) or seed is not None:
+            raise ValueError("temperature, top_k, top_p, min_p and seed apply to do_sample=True only (the default continuation is greedy)")
+        return None
+    if seed is None:
+        raise ValueError("do_sample=True needs seed=int or a list of B ints: a sampled continuation is reproducible from its seed only")
+    if force_tokens is not None:
+        raise ValueError("do_sample=True together with force_tokens: the forced answer leaves nothing to draw")
+
+    def real(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+        return float(v)
+
+    temperature, top_p, min_p = real("temperature", temperature), real("top_p", top_p), real("min_p", min_p)
+    if temperature <= 0.0:
+        raise ValueError(f"temperature must be > 0, got {temperature} (greedy decoding is do_sample=False, or top_k=1)")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0:
+        raise ValueError(f"top_k must be an integer >= 0 (0: off), got {top_k!r}")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p must lie in (0, 1] (1: off), got {top_p}")
+    if not 0.0 <= min_p <= 1.0:
+        raise ValueError(f"min_p must lie in [0, 1] (0: off), got {min_p}")
+    is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)      # noqa: E731
+    if is_int(seed):
+        seeds, streams = [seed] * B, list(range(B))
+    elif isinstance(seed, (list, tuple)) and len(seed) == B and all(is_int(v) for v in seed):
+        seeds, streams = list(seed), [0] * B
+    else:
+        raise ValueError(f"seed must be an int or a list of {B} ints, got {seed!r}")
+    seeds = [((v & (2 ** 64 - 1)) ^ 2 ** 63) - 2 ** 63 for v in seeds]          # (modulo 2^64, as the int64 that carries the bits)
+    return SampleSpec(temperature, top_k, top_p, min_p, torch.tensor(seeds, dtype=torch.int64), torch.tensor(streams, dtype=torch.int32))
+
+
 OBJECTIVES = ("logit", "logprob")
 
 SpanRequest = collections.namedtuple("SpanRequest", "T rows idx auto w w_each objective per_position")
@@ -884,20 +928,28 @@ class GraphCache:
         return out
 
 
-def greedy_decode(logits, step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits):
+def greedy_decode(logits, step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits, sampler=None):
     """the token loop of generate(), shared by the drivers: logits fp32 [B, V] of the prefill's last rows; step(tok int64 [B], pos int32 [1])
     -> (logits, arg-max idx) of one decode step (eager or a GraphCache replay); cols int32 [max_new_tokens]: cols[t - 1: t] is the column of
     step t's input token; ids int64 [B, S] on the device, lens int64 [B] on the host; eos / pad as generate_request returns them; forced
-    int32 [B, max_new_tokens] or None.  -> generate()'s dict.  B flags are read back per token with eos, nothing without"""
+    int32 [B, max_new_tokens] or None.  -> generate()'s dict.  B flags are read back per token with eos, nothing without.
+    sampler: a SampleSpec (sample_request) -- token t is ops.sample_rows of step t's logits at Philox counter t in place of the arg-max, one
+    launch per token next to span_seed's (outside the captured step); logit / logprob stay the model's own, untempered values of the drawn
+    token, and the dict gains sample_logprob [B, T'] = log(q_tok / Z) under the temperature and the filters"""
     dev, B = ids.device, ids.shape[0]
     eos_t = torch.tensor(eos, device=dev, dtype=torch.int32) if eos else None
     fin = torch.zeros(B, device=dev, dtype=torch.bool)
     n_new = torch.zeros(B, device=dev, dtype=torch.long)
     toks, logit, logprob, rows = [], [], [], []
     idx = ops.argmax_rows(logits)[0]
+    if sampler is not None:
+        seeds, streams, slp = sampler.seeds.to(dev), sampler.streams.to(dev), []
     for t in range(max_new_tokens):
         if t:
             logits, idx = step(toks[-1], cols[t - 1: t])
+        if sampler is not None:
+            idx, lq, _, _ = ops.sample_rows(logits, sampler.temperature, sampler.top_k, sampler.top_p, sampler.min_p, seeds, streams, step=t)
+            slp.append(lq)
         if forced is not None:
             idx = forced[:, t]
         if eos:
@@ -918,6 +970,8 @@ def greedy_decode(logits, step, cols, ids, lens, max_new_tokens, eos, pad, force
                lengths=lens.to(dev) + new.shape[1])
     if return_logits:
         out["logits"] = torch.stack(rows, 1)
+    if sampler is not None:
+        out["sample_logprob"] = torch.stack(slp, 1)
     return out
 
 
@@ -1733,8 +1787,8 @@ class LlamaLRP:
 
     @torch.no_grad()
     def generate(self, input_ids=None, max_new_tokens=1, lengths=None, eos_token_id=None, pad_token_id=None, graph=False, return_logits=False,
-                 inputs_embeds=None, force_tokens=None):
-        """Greedy continuation of input_ids [B, S] on the resident weights, forward only, with a KV cache:
+                 inputs_embeds=None, force_tokens=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, seed=None):
+        """Continuation of input_ids [B, S] on the resident weights, forward only, with a KV cache, greedy by default:
         -> dict(sequences int64 [B, S + T'], new_tokens int64 [B, T'], n_new int64 [B], logit / logprob fp32 [B, T'] = the step's logit and
         log-probability of new_tokens[b, t], lengths int64 [B] = the input lengths + T'[, logits fp32 [B, T', V] with return_logits]).
         The prefill is the forward explain() runs; every layer's rotated K and its V are copied into caches [L, B, cap, nk d] of the arena,
@@ -1750,12 +1804,20 @@ class LlamaLRP:
         force_tokens int [B, max_new_tokens] (optional): teacher forcing -- token t of the continuation is force_tokens[b, t] in place of the
         arg-max (logit / logprob are then the model's values of the given answer: scoring it through the cache).
         weight_format="mxfp4" bf16 engines read the layers' codes in place at B <= 128 (ops.linear_stream_fwd_q; a matrix the kernel does not
-        serve is dequantised once per token).  Greedy only: no sampling, beam search or repetition penalty.
+        serve is dequantised once per token).
+        do_sample=True: token t is drawn by lrp_sample_rows from step t's logits in place of the arg-max -- temperature
+        > 0, top_k (0: off; ties at the k-th logit are kept), top_p in (0, 1] (1: off), min_p in [0, 1] (0: off), applied in HF's order; seed
+        is required: an int (prompt b draws from Philox stream b of that seed) or a list of B ints (prompt b draws from its own seed: its
+        continuation does not depend on the batch).  Same seed, same tokens, eager or graph.  logit / logprob stay the model's untempered values
+        of the drawn tokens (what explain_generated explains); the dict gains sample_logprob [B, T'], the log-probability under the
+        temperature and the filters.  No beam search, repetition penalty or per-prompt settings.
         ValueError before any kernel runs: inputs_embeds, max_new_tokens < 1, S + max_new_tokens > max_seq, bad lengths, an eos_token_id,
-        pad_token_id or forced token outside [0, vocab)."""
+        pad_token_id or forced token outside [0, vocab), and what sample_request refuses (a sampling argument without do_sample, do_sample
+        without seed or with force_tokens, a setting outside its range)."""
         c = self.cfg
         ids, lens, eos, pad = generate_request(input_ids, inputs_embeds, max_new_tokens, lengths, eos_token_id, pad_token_id, c["vocab"], self.max_seq)
         B, S = ids.shape
+        sampler = sample_request(do_sample, temperature, top_k, top_p, min_p, seed, B, force_tokens)
         dev, ar, L, nkd, nq, nk, d = self.device, self._arena, len(self.layers), c["n_kv"] * c["head_dim"], c["n_heads"], c["n_kv"], c["head_dim"]
         cap = S + max_new_tokens
         forced = force_request(force_tokens, B, max_new_tokens, c["vocab"], dev)
@@ -1773,18 +1835,21 @@ class LlamaLRP:
             step = lambda tok, pos: self._graphs(("decode", B, cap, self.mode), lambda t_, p_: self._decode_step(t_, p_, lo, kc, vc, ws), tok, pos)      # noqa: E731
         else:
             step = lambda tok, pos: self._decode_step(tok, pos, lo, kc, vc, ws)      # noqa: E731
-        return greedy_decode(fw["logits"], step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits)
+        return greedy_decode(fw["logits"], step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits, sampler=sampler)
 
     @torch.no_grad()
     def explain_generated(self, input_ids=None, max_new_tokens=1, lengths=None, eos_token_id=None, pad_token_id=None, graph=False,
-                          objective="logprob", position_weights=None, **readout_kw):
-        """Prompt in, the model's own answer and its attribution out, on one resident copy of the weights: generate(), then
+                          objective="logprob", position_weights=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0,
+                          seed=None, **readout_kw):
+        """Prompt in, the model's own answer and its attribution out, on one resident copy of the weights: generate() (greedy, or sampled with
+        do_sample=True and generate()'s sampling keywords), then
         explain(sequences, lengths=out["lengths"], positions=[S - 1 .. S + T' - 2], position_weights=w, objective=objective, **readout_kw) --
         row S - 1 + t predicts new token t, so the default targets of positions ARE the generated tokens.  w[b, t] = 1 for t < n_new[b], else 0
         (the slots after an EOS are the zero-weight spare slots positions defines); position_weights="mean": 1 / n_new[b] instead; or an
         explicit fp32 [B, T'].  The last column is no explained row: R_tok is exactly 0 there, as at pads.  -> explain's dict plus sequences,
         new_tokens, n_new.  graph applies to the generation; per_position=True and every read-out keyword pass through to explain()."""
-        out = self.generate(input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph=graph)
+        out = self.generate(input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph=graph, do_sample=do_sample,
+                            temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, seed=seed)
         positions, w = generated_span(out, position_weights)
         res = self.explain(out["sequences"], lengths=out["lengths"], positions=positions, position_weights=w, objective=objective, **readout_kw)
         res.update(sequences=out["sequences"], new_tokens=out["new_tokens"], n_new=out["n_new"])

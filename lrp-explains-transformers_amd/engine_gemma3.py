@@ -20,7 +20,7 @@ import torch
 from . import ops
 from .engine import (EFFICIENT, Arena, AttnMapSink, GraphCache, HeadSink, attn_map_request, explain_inputs, explanation, force_request, fused_layout,
                      generate_request, generated_span, greedy_decode, head_fwd, head_request, latent_request, pack_flat, pitch_pad,
-                     position_request, put_gate_up, put_rows, rope_tables, top_attn_operands)
+                     position_request, put_gate_up, put_rows, rope_tables, sample_request, top_attn_operands)
 
 _STATIC_ROPE = ("default", "linear")
 
@@ -598,17 +598,20 @@ class Gemma3LRP:
 
     @torch.no_grad()
     def generate(self, input_ids=None, max_new_tokens=1, lengths=None, eos_token_id=None, pad_token_id=None, graph=False, return_logits=False,
-                 inputs_embeds=None, force_tokens=None):
-        """Greedy continuation of input_ids [B, S] on the resident weights, forward only, with a KV cache: LlamaLRP.generate's signature,
+                 inputs_embeds=None, force_tokens=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, seed=None):
+        """Continuation of input_ids [B, S] on the resident weights, forward only, with a KV cache, greedy by default: LlamaLRP.generate's signature,
         returned dict (sequences, new_tokens, n_new, logit, logprob, lengths[, logits]) and EOS / pad / force_tokens / lengths behaviour
         (DESIGN.md sections 21 and 23).  The prefill is the forward explain() runs; every layer's normed, rotated K and its V are copied into
         caches [L, B, cap, nk d] of the arena, cap = S + max_new_tokens <= max_seq (sliding layers keep all cap rows: no ring buffer); the
         first new token is the lrp_argmax_rows of the prefill's logits, each further one costs one _decode_step.  graph=True: the step is
-        captured once per (B, cap) and replayed, bitwise the eager result.  Greedy only.  ValueError before any kernel runs: inputs_embeds,
-        max_new_tokens < 1, S + max_new_tokens > max_seq, bad lengths, an eos_token_id, pad_token_id or forced token outside [0, vocab)."""
+        captured once per (B, cap) and replayed, bitwise the eager result.  do_sample=True with temperature / top_k / top_p / min_p / seed: the
+        seeded sampling of LlamaLRP.generate (the dict gains sample_logprob).  ValueError before any kernel runs:
+        inputs_embeds, max_new_tokens < 1, S + max_new_tokens > max_seq, bad lengths, an eos_token_id, pad_token_id or forced token outside
+        [0, vocab), and what sample_request refuses."""
         c = self.cfg
         ids, lens, eos, pad = generate_request(input_ids, inputs_embeds, max_new_tokens, lengths, eos_token_id, pad_token_id, c["vocab"], self.max_seq)
         B, S = ids.shape
+        sampler = sample_request(do_sample, temperature, top_k, top_p, min_p, seed, B, force_tokens)
         dev, ar, L, nq, nk, d = self.device, self._arena, len(self.layers), c["n_heads"], c["n_kv"], c["head_dim"]
         nkd, cap = nk * d, S + max_new_tokens
         forced = force_request(force_tokens, B, max_new_tokens, c["vocab"], dev)
@@ -626,15 +629,17 @@ class Gemma3LRP:
             step = lambda tok, pos: self._graphs(("decode", B, cap), lambda t_, p_: self._decode_step(t_, p_, lo, kc, vc, ws), tok, pos)      # noqa: E731
         else:
             step = lambda tok, pos: self._decode_step(tok, pos, lo, kc, vc, ws)      # noqa: E731
-        return greedy_decode(fw["logits"], step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits)
+        return greedy_decode(fw["logits"], step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits, sampler=sampler)
 
     @torch.no_grad()
     def explain_generated(self, input_ids=None, max_new_tokens=1, lengths=None, eos_token_id=None, pad_token_id=None, graph=False,
-                          objective="logprob", position_weights=None, **readout_kw):
-        """generate(), then explain(sequences, lengths=out["lengths"], positions=[S - 1 .. S + T' - 2], position_weights=w,
+                          objective="logprob", position_weights=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0,
+                          seed=None, **readout_kw):
+        """generate() (greedy, or sampled with do_sample=True and generate()'s sampling keywords), then explain(sequences, lengths=out["lengths"], positions=[S - 1 .. S + T' - 2], position_weights=w,
         objective=objective, **readout_kw) with the weight rules of LlamaLRP.explain_generated (1 for t < n_new[b] else 0; "mean";
         or explicit) -> explain's dict plus sequences, new_tokens, n_new.  The last column is no explained row: R_tok is exactly 0 there"""
-        out = self.generate(input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph=graph)
+        out = self.generate(input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph=graph, do_sample=do_sample,
+                            temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, seed=seed)
         positions, w = generated_span(out, position_weights)
         res = self.explain(out["sequences"], lengths=out["lengths"], positions=positions, position_weights=w, objective=objective, **readout_kw)
         res.update(sequences=out["sequences"], new_tokens=out["new_tokens"], n_new=out["n_new"])

@@ -1113,6 +1113,39 @@ def span_seed(logits, idx, w=None, rstd=None, objective="logit", seed=None, seed
     return logit, logprob, rs, seed
 
 
+def sample_rows(logits, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, seeds=None, streams=None, step=0, u=None):
+    """one sampled column per row of fp32 logits [B, V] (unit column stride, any row pitch), one launch (include/lrp_hip_sample.h):
+    -> (idx int32 [B], sample_logprob fp32 [B] = log(q_idx / Z), n_kept int32 [B], u fp32 [B] = the uniform used).  temperature > 0;
+    top_k >= 1 (0 or >= V: off; 1: the arg-max); top_p in (0, 1) (>= 1: off); min_p in (0, 1] (0: off).  The uniform of row b is u[b] when
+    u (fp32 [B]) is given, else Philox4x32-10 keyed by seeds[b] (int64 [B]) at counter (step, streams[b] (int32 [B]; None: 0), 0, 0).
+    Fixed-point integer masses: bitwise repeatable, a row's result depends on that row only."""
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[1] < 1:
+        raise ValueError(f"sample_rows: logits {tuple(logits.shape)} must be [B, V >= 1] with contiguous rows")
+    B, V = logits.shape
+    pl = p(logits)                      # (device tensors only: raises before anything is allocated)
+    f32(logits, u)
+    if seeds is None and u is None:
+        raise ValueError("sample_rows: pass seeds (int64 [B]) or u (fp32 [B])")
+    for name, t, want in (("seeds", seeds, torch.int64), ("streams", streams, torch.int32), ("u", u, torch.float32)):
+        if t is not None:
+            if not torch.is_tensor(t) or t.dtype != want:
+                raise TypeError(f"sample_rows: {name} must be a {want} tensor")
+            if t.numel() != B or not t.is_contiguous() or t.device != logits.device:
+                raise ValueError(f"sample_rows: {name} must be a contiguous [{B}] tensor on {logits.device}")
+    if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0 or isinstance(step, bool) or not isinstance(step, int) or step < 0:
+        raise ValueError(f"sample_rows: top_k and step must be integers >= 0, got {top_k!r}, {step!r}")
+    temperature, top_p, min_p = float(temperature), float(top_p), float(min_p)
+    if not (0.0 < temperature < float("inf")) or not top_p > 0.0 or not 0.0 <= min_p <= 1.0:
+        raise ValueError(f"sample_rows: temperature > 0 and finite, top_p > 0, min_p in [0, 1]; got {temperature}, {top_p}, {min_p}")
+    idx, n_kept = (torch.empty(B, device=logits.device, dtype=torch.int32) for _ in range(2))
+    slp, u_out = (torch.empty(B, device=logits.device, dtype=torch.float32) for _ in range(2))
+    if B == 0:                          # (empty tensors have no address to hand over)
+        return idx, slp, n_kept, u_out
+    check(lib.lrp_sample_rows(pl, logits.stride(0) if B > 1 else max(logits.stride(0), V), B, V, temperature, min(top_k, 2 ** 31 - 1), top_p, min_p,
+                              p(seeds), p(streams), step, p(u), p(idx), p(slp), p(n_kept), p(u_out), stream()), "lrp_sample_rows")
+    return idx, slp, n_kept, u_out
+
+
 SMALLM_MAX = 16          # rows the W-streaming small-M kernels serve (above: the skinny split-K path, then the MFMA GEMM)
 
 
