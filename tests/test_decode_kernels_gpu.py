@@ -4,13 +4,9 @@ ops.rope_fwd on the same rows, with the cache untouched everywhere else and for 
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+from tests.decode_ref import BAR, DEV, DTYPES, make_case, reference
 
-DEV = "cuda"
-DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
-# fp32: the project's fp32 bar at a small multiple of the accumulation noise (sums of <= 3 SLAB + 5 terms in fp32: ~1e-6).  bf16: against fp64
-# on the bf16-ROUNDED operands the only rounding between the fp32 accumulators and the store is one bf16 rounding, 2^-9; twice that
-BAR = {"fp32": 1e-5, "bf16": 2.0 ** -8}
+pytestmark = pytest.mark.gpu
 
 
 def slab():
@@ -21,34 +17,6 @@ def slab():
 def lives():
     s = slab()
     return (1, 2, s - 1, s, s + 1, 3 * s + 5)
-
-
-def reference(q, kc, vc, lo, n, Hq, Hkv, d, scale):
-    """fp64 softmax attention of one query row per (prompt, head) over keys lo[b] .. n - 1 of the (already rounded) operands -> [B, Hq d]"""
-    B, rep = q.shape[0], Hq // Hkv
-    out = torch.zeros(B, Hq, d, dtype=torch.float64)
-    q64, k64, v64 = q.double().cpu().view(B, Hq, d), kc.double().cpu(), vc.double().cpu()
-    for b in range(B):
-        l0 = min(max(int(lo[b]), 0), n - 1)
-        k = k64[b, l0:n].view(n - l0, Hkv, d).repeat_interleave(rep, 1)
-        v = v64[b, l0:n].view(n - l0, Hkv, d).repeat_interleave(rep, 1)
-        p = torch.softmax(scale * torch.einsum("hd,jhd->hj", q64[b], k), -1)
-        out[b] = torch.einsum("hj,jhd->hd", p, v)
-    return out.view(B, Hq * d)
-
-
-def make_case(dtype, B, n, cap, Hq, Hkv, d, lo, seed):
-    """operands with every cache row outside [lo[b], n - 1] NaN, and the same live rows in a cache of another capacity"""
-    g = torch.Generator().manual_seed(seed)
-    q = torch.randn(B, Hq * d, generator=g).to(dtype)
-    k = torch.randn(B, n, Hkv * d, generator=g).to(dtype)
-    v = torch.randn(B, n, Hkv * d, generator=g).to(dtype)
-    kc = torch.full((B, cap, Hkv * d), float("nan"), dtype=dtype)
-    vc = torch.full((B, cap, Hkv * d), float("nan"), dtype=dtype)
-    for b in range(B):
-        kc[b, lo[b]:n] = k[b, lo[b]:]
-        vc[b, lo[b]:n] = v[b, lo[b]:]
-    return q.to(DEV), kc.to(DEV), vc.to(DEV)
 
 
 @pytest.mark.parametrize("heads", [(4, 4), (8, 2), (8, 1)], ids=lambda h: f"h{h[0]}kv{h[1]}")

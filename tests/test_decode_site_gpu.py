@@ -4,10 +4,12 @@ attn_decode against fp64 with its bitwise invariants, decode_rope_append against
 import pytest
 import torch
 
+from tests.decode_ref import BAR, DEV, DTYPES, bits
+from tests.decode_ref import make_case as attn_case
+from tests.decode_ref import reference as attn_reference
+
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda"
-DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
 # d == one 16-byte vector (fp32 4, bf16 8): both composed kernels accept it, and d / 2 is then NOT a whole number of vectors (the rotate-half
 # partner sits inside the lane's own vector)
 ONE_VECTOR = {"fp32": 4, "bf16": 8}
@@ -18,11 +20,6 @@ EPS = 1e-6
 def ops():
     import lxt_amd.ops as ops
     return ops
-
-
-def bits(t):
-    """the storage bits of a tensor: NaN sentinels compare equal to themselves"""
-    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int16)
 
 
 def site_case(dtype, B, nq, nk, d, cap, rows, seed):
@@ -101,37 +98,8 @@ def test_site_kernel_refuses_what_a_composed_kernel_refuses(ops):
 
 
 # ---- the two kernels of csrc/decode.hip at d = 256 -------------------------------------------------------------------------------------
-# fp32: the project's fp32 bar at a small multiple of the accumulation noise; bf16: on the bf16-ROUNDED operands the only rounding between the
-# fp32 accumulators and the store is one bf16 rounding, 2^-9; twice that
-BAR = {"fp32": 1e-5, "bf16": 2.0 ** -8}
+# the bars: tests/decode_ref.py
 LIVES = (1, 63, 64, 65, 197)
-
-
-def attn_reference(q, kc, vc, lo, n, Hq, Hkv, d, scale):
-    B, rep = q.shape[0], Hq // Hkv
-    out = torch.zeros(B, Hq, d, dtype=torch.float64)
-    q64, k64, v64 = q.double().cpu().view(B, Hq, d), kc.double().cpu(), vc.double().cpu()
-    for b in range(B):
-        l0 = min(max(int(lo[b]), 0), n - 1)
-        k = k64[b, l0:n].view(n - l0, Hkv, d).repeat_interleave(rep, 1)
-        v = v64[b, l0:n].view(n - l0, Hkv, d).repeat_interleave(rep, 1)
-        p = torch.softmax(scale * torch.einsum("hd,jhd->hj", q64[b], k), -1)
-        out[b] = torch.einsum("hj,jhd->hd", p, v)
-    return out.view(B, Hq * d)
-
-
-def attn_case(dtype, B, n, cap, Hq, Hkv, d, lo, seed):
-    """operands with every cache row outside [lo[b], n - 1] NaN; the same live rows whatever cap is"""
-    g = torch.Generator().manual_seed(seed)
-    q = torch.randn(B, Hq * d, generator=g).to(dtype)
-    k = torch.randn(B, n, Hkv * d, generator=g).to(dtype)
-    v = torch.randn(B, n, Hkv * d, generator=g).to(dtype)
-    kc = torch.full((B, cap, Hkv * d), float("nan"), dtype=dtype)
-    vc = torch.full((B, cap, Hkv * d), float("nan"), dtype=dtype)
-    for b in range(B):
-        kc[b, lo[b]:n] = k[b, lo[b]:]
-        vc[b, lo[b]:n] = v[b, lo[b]:]
-    return q.to(DEV), kc.to(DEV), vc.to(DEV)
 
 
 @pytest.mark.parametrize("heads", [(8, 4), (4, 1)], ids=lambda h: f"h{h[0]}kv{h[1]}")
