@@ -726,12 +726,13 @@ class HeadSink:
 ATTN_MAP_SUM = "sum"
 
 
-def attn_map_request(attn_map, nL, nq, d, dtype, mode):
+def attn_map_request(attn_map, nL, nq, d, dtype, mode, bf16_dims=(64, 128)):
     """explain(attn_map=...) -> (want_sum, pairs): "sum" asks for the token-to-token attention relevance summed over the query heads of every
     layer, a (layer, head) pair for the map of one query head; an iterable may mix both, repeated entries count once and the pairs keep the
     order of their first mention.  None -> (False, ()).  Raises ValueError before a kernel of the model runs: an unknown name, a non-iterable,
-    a pair outside [0, nL) x [0, nq) (negative indices are not wrapped), a head dim or dtype lrp_attn_relmap does not serve (bf16: 64 or 128;
-    fp32: a multiple of 4 up to 256), or the explicit placement (its Gho carries the eps_pv ratio: a different quantity, pinned by no fixture)"""
+    a pair outside [0, nL) x [0, nq) (negative indices are not wrapped), a head dim or dtype the caller's map kernel does not serve (bf16:
+    bf16_dims -- lrp_attn_relmap's 64 and 128, the Gemma-3 drivers add lrp_attn_relmap_d256's 256; fp32: a multiple of 4 up to 256), or the
+    explicit placement (its Gho carries the eps_pv ratio: a different quantity, pinned by no fixture)"""
     if attn_map is None:
         return False, ()
     if isinstance(attn_map, str):
@@ -759,7 +760,7 @@ def attn_map_request(attn_map, nL, nq, d, dtype, mode):
     if want_sum or pairs:
         if mode != "efficient":
             raise ValueError(f"attn_map: token-to-token maps are defined for the efficient placement only, not mode={mode!r}")
-        ok = isinstance(d, int) and ((dtype == torch.bfloat16 and d in (64, 128)) or (dtype == torch.float32 and 1 <= d <= 256 and d % 4 == 0))
+        ok = isinstance(d, int) and ((dtype == torch.bfloat16 and d in bf16_dims) or (dtype == torch.float32 and 1 <= d <= 256 and d % 4 == 0))
         if not ok:
             raise ValueError(f"attn_map: no kernel for head dim {d} in {dtype} (bf16: 64 or 128; fp32: a multiple of 4 up to 256)")
     return want_sum, tuple(pairs)
@@ -1023,6 +1024,155 @@ def explanation(emb, G, idx, logits, B, S, return_G=False):
     if return_G:
         out["G_emb"], out["emb"] = G.view(B, S, -1).clone(), emb.view(B, S, -1)
     return out
+
+
+def readout_outputs(out, B, S, layer_R, lat, want_layer_R, want_trace, hs, am, device, span_rows=None):
+    """the read-outs of one explanation added to explain()'s dict under LlamaLRP.explain's names (README, DESIGN.md section 12 - 12.2);
+    layer_R: [rel_last [B], per-token rows [M] from the top boundary down to the embedding] or None.  span_rows int64 [B T]
+    (explain(positions=...)): rel_last has one entry per explained row; they are placed at their columns (distinct rows: a copy, exactly
+    0 elsewhere), so a prompt's head sum is the same fixed-order row sum as every other layer's and R_trace[L].sum(-1) IS layer_R[L]"""
+    if span_rows is not None and (want_layer_R or want_trace):
+        head_rows = torch.zeros(B * S, device=device, dtype=torch.float32).index_copy_(0, span_rows, layer_R[0]).view(B, S)
+    if want_layer_R:
+        rows = [layer_R[0] if span_rows is None else head_rows.sum(1)] + [r.view(B, S).sum(1) for r in layer_R[1:]]
+        out["layer_R"] = torch.stack(rows[::-1], 0)          # [L+1, B], index 0 = embedding
+    if want_trace:
+        # the per-token rows layer_R sums: index l = the input of layer l (l = 0: R_tok itself), index L = the head's explained rows
+        nL = len(layer_R) - 1
+        trace = torch.zeros(nL + 1, B, S, device=device, dtype=torch.float32)
+        trace[0] = out["R_tok"]
+        for li in range(1, nL):
+            trace[li] = layer_R[nL - li].view(B, S)
+        if span_rows is None:
+            trace[nL, :, S - 1] = layer_R[0]
+        else:
+            trace[nL] = head_rows
+        out["R_trace"] = trace
+    out.update(lat)
+    if hs is not None:
+        out.update({"R_head_" + n: t for n, t in hs.out.items()})
+        if "out" in hs.out:
+            out["R_head"] = hs.out["out"].sum(-1)
+    if am is not None:
+        if am.total is not None:
+            out["R_attn"] = am.total
+        if am.per_head is not None:
+            out["R_attn_heads"], out["attn_map_heads"] = am.per_head, list(am.pairs)
+    return out
+
+
+def head_seed_bwd(ar, fw, idx, norm, lm_head, eps_lin, w_offset=0.0, seed=None):
+    """LM head eps rule + final-norm identity rule ((w + w_offset) rstd, the rstd detached) on the explained row of each prompt -> Gh_last
+    [R, H], the gradient at h_L.  fw["span"] (explain(positions=...)): the same on the R = B T explained rows in slot order -- lrp_span_seed
+    leaves span["logit"] / span["logprob"], the row scale w (*) rstd_f of the one-hot route ("logit"), or the dense seed w (delta - softmax)
+    in the engine dtype ("logprob": the route of seed=, without its casts).  seed [B, V]: a dense seed over the last-position logits
+    (contrastive explanations): a gradient where eps_lin = 0, else a relevance (coef = R / (z + eps)); G_xn = coef @ W_lm (ops.linear_dgrad:
+    W streamed once from its stored layout), then the final norm's row scale"""
+    R, H, span = fw["last"].shape[0], lm_head.shape[1], fw.get("span")
+    if span is not None:
+        dense = span["objective"] == "logprob"
+        sd = ar.new("span_seed", R, lm_head.shape[0]) if dense else None
+        span["logit"], span["logprob"], rs, _ = ops.span_seed(fw["logits"], idx, span["w"], fw["rstd_f"], span["objective"], seed=sd,
+                                                              logit=ar.f32("span_logit", R), logprob=ar.f32("span_logprob", R),
+                                                              rs=ar.f32("span_rs", R))
+        if not dense:
+            return ops.head_seed(lm_head, fw["logits"], idx, norm, rs, ar.new("Gh_last", R, H), w_offset, eps_lin)
+        coef = sd
+    elif seed is None:
+        return ops.head_seed(lm_head, fw["logits"], idx, norm, fw["rstd_f"], ar.new("Gh_last", R, H), w_offset, eps_lin)
+    else:
+        coef = seed.to(device=ar.device, dtype=torch.float32).reshape(R, -1).contiguous()
+        if eps_lin != 0.0:
+            coef = ops.eps_scale(coef, fw["logits"], 1.0, eps_lin, relevance=True)
+        coef = coef.to(ar.dtype)
+    g_xn = ops.linear_dgrad(coef, lm_head, out_dtype=torch.float32)
+    return ops.head_norm_bwd(g_xn, norm, fw["rstd_f"], ar.new("Gh_last", R, H), w_offset)
+
+
+def explain_pipeline(drv, forward, backward, emb, B, S, idx, attn_scale, rope_scale=1.0, return_G=False, layer_relevance=False,
+                     latent=frozenset(), heads=frozenset(), attn_map=(False, ()), span=None):
+    """forward + backward + read-outs of one explanation on the current stream, the one sequence behind LlamaLRP._run and
+    Gemma3LRP.explain_emb -> (explain()'s dict, G at the embedding).  Library launches only, no host synchronisation (capturable); with no
+    request the buffers, the launches and every output are those of the plain call.  What differs between the drivers is handed in:
+      forward(**rows) -> the driver's forward state (rows=span.rows for a span: the explained rows, the top layer then runs dense);
+      backward(fw, idx, layer_relevance, latent, heads, attn_map) -> (G, layer_R rows or None, dict of the token-summed read-outs);
+      attn_scale, rope_scale: the softmax scale the AttnMapSink applies and the HeadSink's 1 / s^2 of rotary tables with a post-scale.
+    idx int32 [B] or None (the arg-max of the explained row; a dense seed explains no single logit, idx / logit then report the arg-max for
+    convenience); latent / heads / attn_map: CHECKED requests; span: a SpanRequest (position_request) or None."""
+    c, nL, dev = drv.cfg, len(drv.layers), drv.device
+    fw = forward(**({} if span is None else dict(rows=span.rows)))
+    if span is not None:
+        T, idx = span.T, span.idx
+        if span.auto is not None:          # the slots at column S - 1 without a target: that row's arg-max (a row copy, no arithmetic)
+            idx.index_copy_(0, span.auto, ops.argmax_rows(fw["logits"])[0].index_select(0, span.auto))
+        fw["span"] = sp = dict(w=span.w, objective=span.objective)
+        head = lambda: dict(idx=idx.view(B, T), logit=sp["logit"].view(B, T).clone(), logprob=sp["logprob"].view(B, T).clone())      # noqa: E731
+        if span.per_position:
+            # T backward passes over the SAME forward state, pass t seeded at slot t alone (the other slots' weights are 0, so their rows of
+            # the gradient are exactly 0): the backward writes temporaries and gradient buffers only, never a buffer the forward stashed
+            # (logit / logprob do not depend on the weights; one more head pass is not run for them)
+            each = torch.empty(B, T, S, device=dev, dtype=torch.float32)
+            for t in range(T):
+                sp["w"] = span.w_each[t]
+                G = backward(fw, idx, False, frozenset(), None, None)[0]
+                each[:, t] = ops.readout(emb, G).view(B, S)
+            return dict(head(), R_tok_each=each, R_tok=each.sum(1)), G
+    elif idx is None:
+        idx, _ = ops.argmax_rows(fw["logits"])
+    hs = HeadSink(heads, nL, B, S, c["n_heads"], c["head_dim"], dev, rope_scale) if heads else None
+    am = AttnMapSink(attn_map, nL, B, S, c["n_heads"], c["n_kv"], c["head_dim"], attn_scale, dev) if attn_map[0] or attn_map[1] else None
+    G, layer_R, lat = backward(fw, idx, layer_relevance or "trace" in latent, latent, hs, am)
+    if span is None:
+        out = explanation(emb, G, idx, fw["logits"], B, S, return_G)
+    else:          # (no logits: R V fp32 is hundreds of MB at a 128 k vocabulary)
+        out = dict(head(), R_tok=ops.readout(emb, G).view(B, S))
+        if return_G:
+            out["G_emb"], out["emb"] = G.view(B, S, -1).clone(), emb.view(B, S, -1)
+    return readout_outputs(out, B, S, layer_R, lat, layer_relevance, "trace" in latent, hs, am, dev, None if span is None else span.rows), G
+
+
+def generate_cached(drv, embed, prefill_kv, graph_key, input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph, return_logits,
+                    inputs_embeds, force_tokens, do_sample, temperature, top_k, top_p, min_p, seed):
+    """the body of the drivers' generate() (its arguments and its dict): the requests, the prefill -- the forward explain() runs --, the KV
+    caches [L, B, cap, nk d] of the arena with the prefill's rows copied in, cap = S + max_new_tokens, and the token loop on
+    drv._decode_step, eager or one GraphCache graph per graph_key(B, cap).  The driver supplies that key, embed(ids [n]) -> its embedding
+    rows [n, H] and prefill_kv(st) -> (rotated K rows [B S, nk d], V rows) of one layer's forward stash.  Every ValueError is raised before
+    a kernel runs and before the driver's device, arena or weights are looked at"""
+    c = drv.cfg
+    ids, lens, eos, pad = generate_request(input_ids, inputs_embeds, max_new_tokens, lengths, eos_token_id, pad_token_id, c["vocab"], drv.max_seq)
+    B, S = ids.shape
+    sampler = sample_request(do_sample, temperature, top_k, top_p, min_p, seed, B, force_tokens)
+    dev, ar, L, nkd, nq, d = drv.device, drv._arena, len(drv.layers), c["n_kv"] * c["head_dim"], c["n_heads"], c["head_dim"]
+    cap = S + max_new_tokens
+    forced = force_request(force_tokens, B, max_new_tokens, c["vocab"], dev)
+    _, _, _, row_iv, _ = explain_inputs(ids, None, None if lengths is None else lens, None, c["vocab"], drv.max_seq, drv.dtype, dev)
+    ids = ids.to(dev)
+    fw = drv.forward(embed(ids.reshape(-1)), B, S, row_iv)
+    kc, vc = ar.new("kcache", L, B, cap, nkd), ar.new("vcache", L, B, cap, nkd)
+    for li, st in enumerate(fw["stash"]):
+        k, v = prefill_kv(st)
+        kc[li, :, :S].copy_(k.view(B, S, nkd))
+        vc[li, :, :S].copy_(v.view(B, S, nkd))
+    lo = ar.get("dec_lo", (B,), torch.int32).copy_(S - lens)
+    ws = ar.get("dec_ws", (ops.attn_decode_ws(B, nq, d, cap),), torch.uint8)
+    cols = torch.arange(S, cap, device=dev, dtype=torch.int32)          # cols[t - 1: t]: the column of step t's input token
+    if graph:
+        step = lambda tok, pos: drv._graphs(graph_key(B, cap), lambda t_, p_: drv._decode_step(t_, p_, lo, kc, vc, ws), tok, pos)      # noqa: E731
+    else:
+        step = lambda tok, pos: drv._decode_step(tok, pos, lo, kc, vc, ws)      # noqa: E731
+    return greedy_decode(fw["logits"], step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits, sampler=sampler)
+
+
+def explain_answer(drv, input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph, objective, position_weights, do_sample,
+                   temperature, top_k, top_p, min_p, seed, readout_kw):
+    """the body of the drivers' explain_generated(): drv.generate(), then drv.explain() on the rows that predict the new tokens
+    (generated_span) -> explain's dict plus sequences, new_tokens, n_new"""
+    out = drv.generate(input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph=graph, do_sample=do_sample,
+                       temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, seed=seed)
+    positions, w = generated_span(out, position_weights)
+    res = drv.explain(out["sequences"], lengths=out["lengths"], positions=positions, position_weights=w, objective=objective, **readout_kw)
+    res.update(sequences=out["sequences"], new_tokens=out["new_tokens"], n_new=out["n_new"])
+    return res
 
 
 class LlamaLRP:
@@ -1333,40 +1483,16 @@ class LlamaLRP:
         top = bool(stash) and stash[-1].get("top", False)
         return dict(stash=stash, last=last, row_iv=row_iv, **head_fwd(ar, h_prev, branch, top, last, self.norm, self.lm_head, c["rms_eps"]))
 
-    def _head_bwd(self, fw, idx, B, seed, layer_relevance):
+    def _head_bwd(self, fw, idx, seed, layer_relevance):
         """LM head eps rule + final-norm identity rule on the single explained row of each prompt, then add2 at h_L = h1 + dn and the eps scale
         of the last down_proj, still one row per prompt -> (Gh_last, Gs_last, A_last, rel_last or None).  fw["span"] (explain(positions=...)):
         the same on the R = B T explained rows, seeded by lrp_span_seed"""
-        E, H, dev, dt, ar = self.eps, self.cfg["hidden"], self.device, self.dtype, self._arena
-        span = fw.get("span")
-        if span is not None:
-            # R = B T explained rows in slot order (B below is R): lrp_span_seed leaves logit / logprob, the row scale w (*) rstd_f of the one-hot
-            # route ("logit"), or the dense seed w (delta - softmax) in the engine dtype ("logprob": the route of seed=, without its casts)
-            B = fw["last"].shape[0]
-            dense = span["objective"] == "logprob"
-            sd = ar.new("span_seed", B, self.lm_head.shape[0]) if dense else None
-            span["logit"], span["logprob"], rs, _ = ops.span_seed(fw["logits"], idx, span["w"], fw["rstd_f"], span["objective"], seed=sd,
-                                                                  logit=ar.f32("span_logit", B), logprob=ar.f32("span_logprob", B),
-                                                                  rs=ar.f32("span_rs", B))
-            if dense:
-                g_xn = ops.linear_dgrad(sd, self.lm_head, out_dtype=torch.float32)
-                Gh_last = ops.head_norm_bwd(g_xn, self.norm, fw["rstd_f"], ar.new("Gh_last", B, H))
-            else:
-                Gh_last = ops.head_seed(self.lm_head, fw["logits"], idx, self.norm, rs, ar.new("Gh_last", B, H), 0.0, E["lin"])
-        elif seed is None:
-            Gh_last = ops.head_seed(self.lm_head, fw["logits"], idx, self.norm, fw["rstd_f"], ar.new("Gh_last", B, H), 0.0, E["lin"])
-        else:
-            # dense seed over the last-position logits (contrastive explanations): gradient in efficient mode, relevance
-            # in explicit mode (coef = R / (z + eps)); G_xn = coef @ W_lm (ops.linear_dgrad: W streamed once from its stored layout),
-            # then the final norm's identity rule (row scale, rmsnorm_bwd_add2 without a residual)
-            coef = seed.to(device=dev, dtype=torch.float32).reshape(B, -1).contiguous()
-            if E["lin"] != 0.0:
-                coef = ops.eps_scale(coef, fw["logits"], 1.0, E["lin"], relevance=True)
-            g_xn = ops.linear_dgrad(coef.to(dt), self.lm_head, out_dtype=torch.float32)
-            Gh_last = ops.head_norm_bwd(g_xn, self.norm, fw["rstd_f"], ar.new("Gh_last", B, H))
+        E, H, ar = self.eps, self.cfg["hidden"], self._arena
+        Gh_last = head_seed_bwd(ar, fw, idx, self.norm, self.lm_head, E["lin"], seed=seed)
+        R = Gh_last.shape[0]
         # add2 at h_L = h1 + dn and the eps scale of the last down_proj, still one row per prompt
-        Gs_last, A_last = ar.new("Gs_last", B, H), ar.new("A_last", B, H)
-        rel_last = ar.f32("rel_last", B) if layer_relevance else None
+        Gs_last, A_last = ar.new("Gs_last", R, H), ar.new("A_last", R, H)
+        rel_last = ar.f32("rel_last", R) if layer_relevance else None
         ops.rmsnorm_bwd_add2(Gh_last, None, None, None, fw["hL_last"], fw["dn_last"], Gs_last, A_last, rel_last,
                              0.0, E["add"], E["lin"])
         return Gh_last, Gs_last, A_last, rel_last
@@ -1383,7 +1509,7 @@ class LlamaLRP:
         nqk, nqkv = (nq + nk) * d, (nq + 2 * nk) * d
         scale = d ** -0.5
         ar = self._arena
-        Gh_last, Gs_last, A_last, rel_last = self._head_bwd(fw, idx, B, seed, layer_relevance)
+        Gh_last, Gs_last, A_last, rel_last = self._head_bwd(fw, idx, seed, layer_relevance)
         nL, lat = len(self.layers), {}
         if "resid" in latent:          # index L: the head's explained rows, the gradient rel_last is formed from (S = 1)
             lat["R_resid"] = torch.empty(nL + 1, B, H, device=dev, dtype=torch.float32)
@@ -1588,75 +1714,14 @@ class LlamaLRP:
         """forward + backward + read-out on the current stream: library launches only, no host synchronisation (capturable); opts: further
         keywords of a subclass's forward / backward (Qwen3MoeLRP: experts); span: a SpanRequest (explain(positions=...))"""
         if emb is None:
-            emb = self.embed.index_select(0, input_ids.reshape(-1))
+            emb = self._embed(input_ids.reshape(-1))
         wsink = self._weight_sink(weights, weights_out) if weights[0] else None
-        fw = self.forward(emb, B, S, row_iv, keep_m="mlp" in latent or "down" in weights[0], **opts, **({} if span is None else dict(rows=span.rows)))
-        if span is not None:
-            idx = span.idx
-            if span.auto is not None:          # the slots at column S - 1 without a target: that row's arg-max (a row copy, no arithmetic)
-                idx.index_copy_(0, span.auto, ops.argmax_rows(fw["logits"])[0].index_select(0, span.auto))
-            fw["span"] = dict(w=span.w, objective=span.objective)
-        if span is not None and span.per_position:
-            # T backward passes over the SAME forward state, pass t seeded at slot t alone (the other slots' weights are 0, so their rows of
-            # the gradient are exactly 0): the backward writes temporaries and gradient buffers only, never a buffer the forward stashed
-            each = torch.empty(B, span.T, S, device=self.device, dtype=torch.float32)
-            for t in range(span.T):
-                fw["span"]["w"] = span.w_each[t]
-                G, _, _ = self.backward(fw, emb, idx, B, S)
-                each[:, t] = ops.readout(emb, G).view(B, S)
-            fw["span"]["w"] = span.w          # (logit / logprob do not depend on the weights; one more head pass is not run for them)
-            return dict(idx=idx.view(B, span.T), logit=fw["span"]["logit"].view(B, span.T).clone(),
-                        logprob=fw["span"]["logprob"].view(B, span.T).clone(), R_tok_each=each, R_tok=each.sum(1))
-        if idx is None:
-            # (a dense seed explains no single logit; idx / logit then report the arg-max for convenience)
-            idx, _ = ops.argmax_rows(fw["logits"])
-        hs = None
-        if heads:
-            c = self.cfg
-            hs = HeadSink(heads, len(self.layers), B, S, c["n_heads"], c["head_dim"], self.device, float(c.get("attention_scaling", 1.0)) ** -2)
-        am = None
-        if attn_map[0] or attn_map[1]:
-            c = self.cfg
-            am = AttnMapSink(attn_map, len(self.layers), B, S, c["n_heads"], c["n_kv"], c["head_dim"], self.meta[-1], self.device)
-        if wsink is not None:
-            opts = dict(opts, weights=wsink)
-        G, layer_R, lat = self.backward(fw, emb, idx, B, S, layer_relevance or "trace" in latent, seed=seed, latent=latent, heads=hs, attn_map=am, **opts)
-        if span is None:
-            out = explanation(emb, G, idx, fw["logits"], B, S, return_G)
-        else:          # (no logits: R V fp32 is hundreds of MB at a 128 k vocabulary)
-            out = dict(idx=idx.view(B, span.T), logit=fw["span"]["logit"].view(B, span.T).clone(),
-                       logprob=fw["span"]["logprob"].view(B, span.T).clone(), R_tok=ops.readout(emb, G).view(B, S))
-            if return_G:
-                out["G_emb"], out["emb"] = G.view(B, S, -1).clone(), emb.view(B, S, -1)
-        if span is not None and (layer_relevance or "trace" in latent):
-            # the head's rows, one per explained row, at their columns (distinct rows: a copy, exactly 0 elsewhere); a prompt's sum is then the
-            # same fixed-order row sum as every other layer's, and R_trace[L].sum(-1) IS layer_R[L]
-            head_rows = torch.zeros(B * S, device=self.device, dtype=torch.float32).index_copy_(0, span.rows, layer_R[0]).view(B, S)
-        if layer_relevance:
-            rows = [head_rows.sum(1) if span is not None else layer_R[0]] + [r.view(B, S).sum(1) for r in layer_R[1:]]
-            out["layer_R"] = torch.stack(rows[::-1], 0)          # [L+1, B], index 0 = embedding
-        if "trace" in latent:
-            # the per-token rows layer_R sums: index l = the input of layer l (l = 0: R_tok itself), index L = the head's explained rows
-            nL = len(layer_R) - 1
-            trace = torch.zeros(nL + 1, B, S, device=self.device, dtype=torch.float32)
-            trace[0] = out["R_tok"]
-            for li in range(1, nL):
-                trace[li] = layer_R[nL - li].view(B, S)
-            if span is None:
-                trace[nL, :, S - 1] = layer_R[0]
-            else:
-                trace[nL] = head_rows
-            out["R_trace"] = trace
-        out.update(lat)
-        if hs is not None:
-            out.update({"R_head_" + n: t for n, t in hs.out.items()})
-            if "out" in hs.out:
-                out["R_head"] = hs.out["out"].sum(-1)
-        if am is not None:
-            if am.total is not None:
-                out["R_attn"] = am.total
-            if am.per_head is not None:
-                out["R_attn_heads"], out["attn_map_heads"] = am.per_head, list(am.pairs)
+        keep_m, bopts = "mlp" in latent or "down" in weights[0], opts if wsink is None else dict(opts, weights=wsink)
+        out, _ = explain_pipeline(self, lambda **rows: self.forward(emb, B, S, row_iv, keep_m=keep_m, **opts, **rows),
+                                  lambda fw, i, want_R, lat, hs, am: self.backward(fw, emb, i, B, S, want_R, seed=seed, latent=lat, heads=hs,
+                                                                                   attn_map=am, **bopts),
+                                  emb, B, S, idx, self.meta[-1], float(self.cfg.get("attention_scaling", 1.0)) ** -2, return_G, layer_relevance,
+                                  latent, heads, attn_map, span)
         if wsink is not None:
             out["R_W"], out["weight_layers"] = wsink.out, list(wsink.layers)
         return out
@@ -1736,6 +1801,15 @@ class LlamaLRP:
                             lambda ids, idx_: self._run(ids, None, B, S, None, idx_, layer_relevance, False, None, lat, hd, am), input_ids, idx)
 
     # --------------------------------------------------------------------------------------------- generation
+    def _embed(self, ids):
+        """the embedding rows [n, H] of token ids [n] on the device"""
+        return self.embed.index_select(0, ids)
+
+    def _prefill_kv(self, st):
+        """(rotated K rows, V rows) [B S, nk d] of one layer's forward stash: what generate() copies into the caches"""
+        nq, nk, d = self.meta[:3]
+        return st["qkr"][:, nq * d:], st["qkv"][:, (nq + nk) * d:]
+
     def _decode_step(self, tok, pos, lo, kc, vc, ws):
         """one new token per prompt through every layer on B rows: the sparse top layer's launch sequence (embedding rows, norm, qkv, o
         projection, norm, gated MLP, down projection: the weight-streaming Linears), with lrp_decode_rope_append and lrp_attn_decode in place of
@@ -1814,28 +1888,9 @@ class LlamaLRP:
         ValueError before any kernel runs: inputs_embeds, max_new_tokens < 1, S + max_new_tokens > max_seq, bad lengths, an eos_token_id,
         pad_token_id or forced token outside [0, vocab), and what sample_request refuses (a sampling argument without do_sample, do_sample
         without seed or with force_tokens, a setting outside its range)."""
-        c = self.cfg
-        ids, lens, eos, pad = generate_request(input_ids, inputs_embeds, max_new_tokens, lengths, eos_token_id, pad_token_id, c["vocab"], self.max_seq)
-        B, S = ids.shape
-        sampler = sample_request(do_sample, temperature, top_k, top_p, min_p, seed, B, force_tokens)
-        dev, ar, L, nkd, nq, nk, d = self.device, self._arena, len(self.layers), c["n_kv"] * c["head_dim"], c["n_heads"], c["n_kv"], c["head_dim"]
-        cap = S + max_new_tokens
-        forced = force_request(force_tokens, B, max_new_tokens, c["vocab"], dev)
-        _, _, _, row_iv, _ = explain_inputs(ids, None, None if lengths is None else lens, None, c["vocab"], self.max_seq, self.dtype, dev)
-        ids = ids.to(dev)
-        fw = self.forward(self.embed.index_select(0, ids.reshape(-1)), B, S, row_iv)
-        kc, vc = ar.new("kcache", L, B, cap, nkd), ar.new("vcache", L, B, cap, nkd)
-        for li, st in enumerate(fw["stash"]):
-            kc[li, :, :S].copy_(st["qkr"][:, nq * d:].view(B, S, nkd))
-            vc[li, :, :S].copy_(st["qkv"][:, (nq + nk) * d:].view(B, S, nkd))
-        lo = ar.get("dec_lo", (B,), torch.int32).copy_(S - lens)
-        ws = ar.get("dec_ws", (ops.attn_decode_ws(B, nq, d, cap),), torch.uint8)
-        cols = torch.arange(S, cap, device=dev, dtype=torch.int32)          # cols[t - 1: t]: the column of step t's input token
-        if graph:
-            step = lambda tok, pos: self._graphs(("decode", B, cap, self.mode), lambda t_, p_: self._decode_step(t_, p_, lo, kc, vc, ws), tok, pos)      # noqa: E731
-        else:
-            step = lambda tok, pos: self._decode_step(tok, pos, lo, kc, vc, ws)      # noqa: E731
-        return greedy_decode(fw["logits"], step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits, sampler=sampler)
+        return generate_cached(self, self._embed, self._prefill_kv, lambda B, cap: ("decode", B, cap, self.mode), input_ids, max_new_tokens,
+                               lengths, eos_token_id, pad_token_id, graph, return_logits, inputs_embeds, force_tokens, do_sample, temperature,
+                               top_k, top_p, min_p, seed)
 
     @torch.no_grad()
     def explain_generated(self, input_ids=None, max_new_tokens=1, lengths=None, eos_token_id=None, pad_token_id=None, graph=False,
@@ -1848,9 +1903,5 @@ class LlamaLRP:
         (the slots after an EOS are the zero-weight spare slots positions defines); position_weights="mean": 1 / n_new[b] instead; or an
         explicit fp32 [B, T'].  The last column is no explained row: R_tok is exactly 0 there, as at pads.  -> explain's dict plus sequences,
         new_tokens, n_new.  graph applies to the generation; per_position=True and every read-out keyword pass through to explain()."""
-        out = self.generate(input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph=graph, do_sample=do_sample,
-                            temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, seed=seed)
-        positions, w = generated_span(out, position_weights)
-        res = self.explain(out["sequences"], lengths=out["lengths"], positions=positions, position_weights=w, objective=objective, **readout_kw)
-        res.update(sequences=out["sequences"], new_tokens=out["new_tokens"], n_new=out["n_new"])
-        return res
+        return explain_answer(self, input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph, objective, position_weights,
+                              do_sample, temperature, top_k, top_p, min_p, seed, readout_kw)

@@ -18,9 +18,9 @@ activations live in the same tagged arena as the Llama driver's.
 import torch
 
 from . import ops
-from .engine import (EFFICIENT, Arena, AttnMapSink, GraphCache, HeadSink, attn_map_request, explain_inputs, explanation, force_request, fused_layout,
-                     generate_request, generated_span, greedy_decode, head_fwd, head_request, latent_request, pack_flat, pitch_pad,
-                     position_request, put_gate_up, put_rows, rope_tables, sample_request, top_attn_operands)
+from .engine import (EFFICIENT, Arena, GraphCache, attn_map_request, explain_answer, explain_inputs, explain_pipeline, fused_layout,
+                     generate_cached, head_fwd, head_request, head_seed_bwd, latent_request, pack_flat, pitch_pad, position_request, put_gate_up,
+                     put_rows, rope_tables, top_attn_operands)
 
 _STATIC_ROPE = ("default", "linear")
 
@@ -85,45 +85,8 @@ def weights_from_hf(model):
 
 def gemma_attn_map_request(attn_map, nL, nq, d, dtype, mode="efficient"):
     """engine.attn_map_request for the Gemma-3 drivers: the same forms, checks and ValueErrors, and bf16 at d = 256 is served as well
-    (lrp_attn_relmap_d256).  That one case is validated at d = 128, a head dim the shared parser accepts in bf16: every other check of it
-    (names, pairs, the placement) does not look at d"""
-    if dtype == torch.bfloat16 and isinstance(d, int) and d == 256:
-        d = 128
-    return attn_map_request(attn_map, nL, nq, d, dtype, mode)
-
-
-def readout_outputs(out, B, S, layer_R, lat, want_layer_R, want_trace, hs, am, device, span_rows=None):
-    """the read-outs of one explanation added to explain()'s dict under LlamaLRP.explain's names (README, DESIGN.md section 12 - 12.2);
-    layer_R: [rel_last [B], per-token rows [M] from the top boundary down to the embedding] or None.  span_rows int64 [B T]
-    (explain(positions=...)): rel_last has one entry per explained row; they are placed at their columns (distinct rows: a copy, exactly
-    0 elsewhere), so a prompt's head sum is the same fixed-order row sum as every other layer's and R_trace[L].sum(-1) IS layer_R[L]"""
-    if span_rows is not None and (want_layer_R or want_trace):
-        head_rows = torch.zeros(B * S, device=device, dtype=torch.float32).index_copy_(0, span_rows, layer_R[0]).view(B, S)
-    if want_layer_R:
-        rows = [layer_R[0] if span_rows is None else head_rows.sum(1)] + [r.view(B, S).sum(1) for r in layer_R[1:]]
-        out["layer_R"] = torch.stack(rows[::-1], 0)          # [L+1, B], index 0 = embedding
-    if want_trace:
-        nL = len(layer_R) - 1
-        trace = torch.zeros(nL + 1, B, S, device=device, dtype=torch.float32)
-        trace[0] = out["R_tok"]
-        for li in range(1, nL):
-            trace[li] = layer_R[nL - li].view(B, S)
-        if span_rows is None:
-            trace[nL, :, S - 1] = layer_R[0]
-        else:
-            trace[nL] = head_rows
-        out["R_trace"] = trace
-    out.update(lat)
-    if hs is not None:
-        out.update({"R_head_" + n: t for n, t in hs.out.items()})
-        if "out" in hs.out:
-            out["R_head"] = hs.out["out"].sum(-1)
-    if am is not None:
-        if am.total is not None:
-            out["R_attn"] = am.total
-        if am.per_head is not None:
-            out["R_attn_heads"], out["attn_map_heads"] = am.per_head, list(am.pairs)
-    return out
+    (lrp_attn_relmap_d256)"""
+    return attn_map_request(attn_map, nL, nq, d, dtype, mode, bf16_dims=(64, 128, 256))
 
 
 class Gemma3LRP:
@@ -311,34 +274,19 @@ class Gemma3LRP:
         return causal, cache[win]
 
     def backward(self, fw, idx, B, S, layer_relevance=False, latent=frozenset(), heads=None, attn_map=None):
-        """-> G at the embedding; with any read-out asked for -> (G, layer_R rows or None, dict of the token-summed latent read-outs), as
-        LlamaLRP.backward.  layer_relevance / "resid" need forward(keep_h=True), "mlp" forward(keep_m=True); heads: a HeadSink, attn_map: an
-        AttnMapSink (None: nothing is launched)"""
+        """-> (G at the embedding, layer_R rows or None, dict of the token-summed latent read-outs), as LlamaLRP.backward.  layer_relevance /
+        "resid" need forward(keep_h=True), "mlp" forward(keep_m=True); heads: a HeadSink, attn_map: an AttnMapSink (None: nothing is launched)"""
         c, E = self.cfg, self.eps
         H, I, d, nq, nk = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"]
         M, rep = B * S, nq // nk
         nqd, nkd, nqkv = nq * d, nk * d, (nq + 2 * nk) * d
         ar = self._arena
         nL, dev = len(self.layers), self.device
-        plain = not (layer_relevance or latent or heads is not None or attn_map is not None)
         lat, layer_R, iv_cache = {}, None, {}
-        # LM head (gradient of the explained logit) + final (1 + w) norm on the one explained row of each prompt, scattered into [M, H]
-        span, R = fw.get("span"), fw["last"].shape[0]
-        if span is None:
-            Gh_last = ops.head_seed(self.lm_head, fw["logits"], idx, self.norm, fw["rstd_f"], ar.new("Gh_last", B, H), 1.0, E["lin"])
-        else:
-            # R = B T explained rows in slot order: lrp_span_seed leaves logit / logprob, the row scale w (*) rstd_f of the one-hot route
-            # ("logit"), or the dense seed w (delta - softmax) in the engine dtype ("logprob"), as LlamaLRP._head_bwd
-            dense = span["objective"] == "logprob"
-            sd = ar.new("span_seed", R, self.lm_head.shape[0]) if dense else None
-            span["logit"], span["logprob"], rs, _ = ops.span_seed(fw["logits"], idx, span["w"], fw["rstd_f"], span["objective"], seed=sd,
-                                                                  logit=ar.f32("span_logit", R), logprob=ar.f32("span_logprob", R),
-                                                                  rs=ar.f32("span_rs", R))
-            if dense:
-                g_xn = ops.linear_dgrad(sd, self.lm_head, out_dtype=torch.float32)
-                Gh_last = ops.head_norm_bwd(g_xn, self.norm, fw["rstd_f"], ar.new("Gh_last", R, H), 1.0)
-            else:
-                Gh_last = ops.head_seed(self.lm_head, fw["logits"], idx, self.norm, rs, ar.new("Gh_last", R, H), 1.0, E["lin"])
+        # LM head (gradient of the explained logit) + final (1 + w) norm on the explained rows (one per prompt, or a span's R = B T: shared with
+        # LlamaLRP, engine.head_seed_bwd), scattered into [M, H]
+        R = fw["last"].shape[0]
+        Gh_last = head_seed_bwd(ar, fw, idx, self.norm, self.lm_head, E["lin"], 1.0)
         top = bool(fw["stash"]) and fw["stash"][-1].get("top", False)
         Gs = None if top else ar.zeros(("Gs", len(self.layers) & 1), M, H).index_copy_(0, fw["last"], Gh_last)       # gradient w.r.t. h_L = h1 + pff
         if layer_relevance:          # index L: the head's explained rows (S = 1)
@@ -447,7 +395,7 @@ class Gemma3LRP:
                 layer_R.append(ops.readout(st["h"], Gs, out=ar.f32(("rel", li), M)))
             if "resid" in latent:
                 ops.colsum_dot(st["h"], Gs, B, S, out=lat["R_resid"][li])
-        return Gs if plain else (Gs, layer_R, lat)
+        return Gs, layer_R, lat
 
     # ---------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -462,56 +410,10 @@ class Gemma3LRP:
         """forward + backward + read-outs on prepared embeddings and CHECKED requests (readout_requests) -> (explain()'s dict, G at the embedding);
         with no request the buffers, the launches and every output are those of the plain call.  span: a SpanRequest
         (engine.position_request, explain(positions=...)); None: nothing of it is touched"""
-        c = self.cfg
-        want_R = layer_relevance or "trace" in lat
-        if span is not None:
-            return self._explain_span(emb, B, S, row_iv, span, return_G, layer_relevance, lat, hd, am)
-        fw = self.forward(emb, B, S, row_iv, keep_h=want_R or "resid" in lat, keep_m="mlp" in lat)
-        if idx is None:
-            idx, _ = ops.argmax_rows(fw["logits"])
-        if not (want_R or lat or hd or am[0] or am[1]):
-            G = self.backward(fw, idx, B, S)
-            return explanation(emb, G, idx, fw["logits"], B, S, return_G), G
-        nL = len(self.layers)
-        hs = HeadSink(hd, nL, B, S, c["n_heads"], c["head_dim"], self.device) if hd else None
-        ams = AttnMapSink(am, nL, B, S, c["n_heads"], c["n_kv"], c["head_dim"], c["scale"], self.device) if am[0] or am[1] else None
-        G, layer_R, sums = self.backward(fw, idx, B, S, want_R, lat, hs, ams)
-        out = explanation(emb, G, idx, fw["logits"], B, S, return_G)
-        return readout_outputs(out, B, S, layer_R, sums, layer_relevance, "trace" in lat, hs, ams, self.device), G
-
-    def _explain_span(self, emb, B, S, row_iv, span, return_G, layer_relevance, lat, hd, am):
-        """explain_emb for an answer span: the forward with the dense top layer and the head on the R = B T explained
-        rows, then one backward seeded by lrp_span_seed (per_position: T backwards over the same forward state, pass t seeded at slot t
-        alone -- the backward writes gradient buffers and temporaries only, never a buffer the forward stashed)"""
-        c, T = self.cfg, span.T
-        want_R = layer_relevance or "trace" in lat
-        fw = self.forward(emb, B, S, row_iv, keep_h=want_R or "resid" in lat, keep_m="mlp" in lat, rows=span.rows)
-        idx = span.idx
-        if span.auto is not None:          # the slots at column S - 1 without a target: that row's arg-max (a row copy, no arithmetic)
-            idx.index_copy_(0, span.auto, ops.argmax_rows(fw["logits"])[0].index_select(0, span.auto))
-        fw["span"] = sp = dict(w=span.w, objective=span.objective)
-        head = lambda: dict(idx=idx.view(B, T), logit=sp["logit"].view(B, T).clone(), logprob=sp["logprob"].view(B, T).clone())      # noqa: E731
-        if span.per_position:
-            each = torch.empty(B, T, S, device=self.device, dtype=torch.float32)
-            for t in range(T):
-                sp["w"] = span.w_each[t]
-                G = self.backward(fw, idx, B, S)
-                each[:, t] = ops.readout(emb, G).view(B, S)
-            return dict(head(), R_tok_each=each, R_tok=each.sum(1)), G
-        plain = not (want_R or lat or hd or am[0] or am[1])
-        nL, hs, ams, layer_R, sums = len(self.layers), None, None, None, {}
-        if plain:
-            G = self.backward(fw, idx, B, S)
-        else:
-            hs = HeadSink(hd, nL, B, S, c["n_heads"], c["head_dim"], self.device) if hd else None
-            ams = AttnMapSink(am, nL, B, S, c["n_heads"], c["n_kv"], c["head_dim"], c["scale"], self.device) if am[0] or am[1] else None
-            G, layer_R, sums = self.backward(fw, idx, B, S, want_R, lat, hs, ams)
-        out = dict(head(), R_tok=ops.readout(emb, G).view(B, S))          # (no logits: R V fp32 is hundreds of MB at a 262 k vocabulary)
-        if return_G:
-            out["G_emb"], out["emb"] = G.view(B, S, -1).clone(), emb.view(B, S, -1)
-        if plain:
-            return out, G
-        return readout_outputs(out, B, S, layer_R, sums, layer_relevance, "trace" in lat, hs, ams, self.device, span.rows), G
+        keep_h = layer_relevance or "trace" in lat or "resid" in lat
+        return explain_pipeline(self, lambda **rows: self.forward(emb, B, S, row_iv, keep_h=keep_h, keep_m="mlp" in lat, **rows),
+                                lambda fw, i, *readouts: self.backward(fw, i, B, S, *readouts), emb, B, S, idx, self.cfg["scale"],
+                                return_G=return_G, layer_relevance=layer_relevance, latent=lat, heads=hd, attn_map=am, span=span)
 
     @torch.no_grad()
     def explain(self, input_ids=None, inputs_embeds=None, target=None, return_G=False, lengths=None, layer_relevance=False, latent=None,
@@ -542,10 +444,18 @@ class Gemma3LRP:
         B, S, emb, row_iv, idx = explain_inputs(input_ids, inputs_embeds, lengths, target, self.cfg["vocab"], self.max_seq, self.dtype,
                                                 self.device)
         if emb is None:
-            emb = self.embed.index_select(0, input_ids.to(self.device).reshape(-1)) * self.embed_scale.to(self.device)
+            emb = self._embed(input_ids.to(self.device).reshape(-1))
         return self.explain_emb(emb, B, S, row_iv, idx, return_G, layer_relevance, lat, hd, am, span)[0]
 
     # --------------------------------------------------------------------------------------------- generation
+    def _embed(self, ids):
+        """the embedding rows [n, H] of token ids [n] on the device, times embed_scale (HF's scaled embeddings)"""
+        return self.embed.index_select(0, ids) * self.embed_scale.to(self.device)
+
+    def _prefill_kv(self, st):
+        """(normed, rotated K rows, V rows) [B S, nk d] of one layer's forward stash: what generate() copies into the caches"""
+        return st["kr"], st["qkv"][:, (self.cfg["n_heads"] + self.cfg["n_kv"]) * self.cfg["head_dim"]:]
+
     def _decode_step(self, tok, pos, lo, kc, vc, ws):
         """one new token per prompt through every layer on B rows (LlamaLRP._decode_step for Gemma-3): embedding rows times embed_scale, then
         per layer the input norm, the QKV Linear, lrp_decode_qknorm_rope_append (both head norms, RoPE with the layer type's table and the
@@ -608,28 +518,9 @@ class Gemma3LRP:
         seeded sampling of LlamaLRP.generate (the dict gains sample_logprob).  ValueError before any kernel runs:
         inputs_embeds, max_new_tokens < 1, S + max_new_tokens > max_seq, bad lengths, an eos_token_id, pad_token_id or forced token outside
         [0, vocab), and what sample_request refuses."""
-        c = self.cfg
-        ids, lens, eos, pad = generate_request(input_ids, inputs_embeds, max_new_tokens, lengths, eos_token_id, pad_token_id, c["vocab"], self.max_seq)
-        B, S = ids.shape
-        sampler = sample_request(do_sample, temperature, top_k, top_p, min_p, seed, B, force_tokens)
-        dev, ar, L, nq, nk, d = self.device, self._arena, len(self.layers), c["n_heads"], c["n_kv"], c["head_dim"]
-        nkd, cap = nk * d, S + max_new_tokens
-        forced = force_request(force_tokens, B, max_new_tokens, c["vocab"], dev)
-        _, _, _, row_iv, _ = explain_inputs(ids, None, None if lengths is None else lens, None, c["vocab"], self.max_seq, self.dtype, dev)
-        ids = ids.to(dev)
-        fw = self.forward(self.embed.index_select(0, ids.reshape(-1)) * self.embed_scale.to(dev), B, S, row_iv)
-        kc, vc = ar.new("kcache", L, B, cap, nkd), ar.new("vcache", L, B, cap, nkd)
-        for li, st in enumerate(fw["stash"]):
-            kc[li, :, :S].copy_(st["kr"].view(B, S, nkd))
-            vc[li, :, :S].copy_(st["qkv"][:, (nq + nk) * d:].view(B, S, nkd))
-        lo = ar.get("dec_lo", (B,), torch.int32).copy_(S - lens)
-        ws = ar.get("dec_ws", (ops.attn_decode_ws(B, nq, d, cap),), torch.uint8)
-        cols = torch.arange(S, cap, device=dev, dtype=torch.int32)          # cols[t - 1: t]: the column of step t's input token
-        if graph:
-            step = lambda tok, pos: self._graphs(("decode", B, cap), lambda t_, p_: self._decode_step(t_, p_, lo, kc, vc, ws), tok, pos)      # noqa: E731
-        else:
-            step = lambda tok, pos: self._decode_step(tok, pos, lo, kc, vc, ws)      # noqa: E731
-        return greedy_decode(fw["logits"], step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits, sampler=sampler)
+        return generate_cached(self, self._embed, self._prefill_kv, lambda B, cap: ("decode", B, cap), input_ids, max_new_tokens, lengths,
+                               eos_token_id, pad_token_id, graph, return_logits, inputs_embeds, force_tokens, do_sample, temperature, top_k, top_p,
+                               min_p, seed)
 
     @torch.no_grad()
     def explain_generated(self, input_ids=None, max_new_tokens=1, lengths=None, eos_token_id=None, pad_token_id=None, graph=False,
@@ -638,9 +529,5 @@ class Gemma3LRP:
         """generate() (greedy, or sampled with do_sample=True and generate()'s sampling keywords), then explain(sequences, lengths=out["lengths"], positions=[S - 1 .. S + T' - 2], position_weights=w,
         objective=objective, **readout_kw) with the weight rules of LlamaLRP.explain_generated (1 for t < n_new[b] else 0; "mean";
         or explicit) -> explain's dict plus sequences, new_tokens, n_new.  The last column is no explained row: R_tok is exactly 0 there"""
-        out = self.generate(input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph=graph, do_sample=do_sample,
-                            temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, seed=seed)
-        positions, w = generated_span(out, position_weights)
-        res = self.explain(out["sequences"], lengths=out["lengths"], positions=positions, position_weights=w, objective=objective, **readout_kw)
-        res.update(sequences=out["sequences"], new_tokens=out["new_tokens"], n_new=out["n_new"])
-        return res
+        return explain_answer(self, input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph, objective, position_weights,
+                              do_sample, temperature, top_k, top_p, min_p, seed, readout_kw)

@@ -434,7 +434,7 @@ class Qwen3MoeLRP(Q.QwenLRP):
         c, ar, dev, dt = self.cfg, self._arena, self.device, self.dtype
         H, I, d, nq, nk, Ne, k = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"], c["n_experts"], c["top_k"]
         M, rep, nqk, nqkv, scale = B * S, nq // nk, (nq + nk) * d, (nq + 2 * nk) * d, d ** -0.5
-        Gh_last, Gs_last, _, rel_last = self._head_bwd(fw, idx, B, seed, layer_relevance)
+        Gh_last, Gs_last, _, rel_last = self._head_bwd(fw, idx, seed, layer_relevance)
         nL, lat = len(self.layers), {}
         if "resid" in latent:
             lat["R_resid"] = torch.empty(nL + 1, B, H, device=dev, dtype=torch.float32)
