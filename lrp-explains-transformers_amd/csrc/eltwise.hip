@@ -238,6 +238,31 @@ __global__ void gated_bwd_kernel(const T* Gm, const T* g, const T* u, T* Ag, T* 
     }
 }
 
+// CP-LRP on the interleaved gate/up output (ref lxt/efficient/patches.py:228-280: gate_proj(x) detached, plain activation, no
+// divide_gradient): the up slots of Agu take act(g) * Gm with act(g) rounded to T as the forward's gated_fwd_kernel rounds it, the gate slots
+// exact zeros.  One chunk of W intermediate indices per thread-iteration: one load of Gm and of g, two stores.
+template <typename T, int W>
+__global__ void gated_cp_bwd_il_kernel(const T* Gm, const T* gu, T* Agu, int M, int I, int64_t ldgm, int64_t ldgu, int64_t ldagu, int act) {
+    const int cpr = I / W;
+    const int64_t total = (int64_t)M * cpr;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i / cpr;
+        const int c = (int)(i - r * cpr) * W;
+        const int cg = (c / LRP_GATED_IL) * 2 * LRP_GATED_IL + (c % LRP_GATED_IL);
+        Chunk<T, W> gm, a, og, ou;
+        gm.load(Gm + r * ldgm + c);
+        a.load(gu + r * ldgu + cg);
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            const float y = to_f32(from_f32<T>(act_apply_t<sizeof(T) == 2>(a.v[k], act)));
+            og.v[k] = 0.f;
+            ou.v[k] = y * gm.v[k];
+        }
+        og.store(Agu + r * ldagu + cg);
+        ou.store(Agu + r * ldagu + cg + LRP_GATED_IL);
+    }
+}
+
 // W consecutive fp32 table entries (16-byte loads when W is a multiple of 4: the tables are fp32 [seq, d], d even,
 // c a multiple of W, so the address is 16-byte aligned whenever d % 4 == 0 -- checked by the host)
 template <int W> LRP_DEVICE void load_tab(float (&t)[W], const float* p) {
@@ -557,6 +582,23 @@ extern "C" int lrp_gated_act_bwd_il(const void* Gm, const void* gu, void* Agu, i
     const size_t es = dtype == LRP_F32 ? 4 : 2;
     return gated_bwd_launch(Gm, gu, gu ? (const char*)gu + 32 * es : nullptr, Agu, Agu ? (char*)Agu + 32 * es : nullptr, M, I, ldgm, ldgu, ldgu,
                             ldagu, ldagu, eps_g, eps_lin, act, LRP_GATED_IL, dtype, (hipStream_t)stream);
+}
+
+extern "C" int lrp_gated_cp_bwd_il(const void* Gm, const void* gu, void* Agu, int M, int I, int64_t ldgm, int64_t ldgu, int64_t ldagu, int act,
+                                   int dtype, void* stream) {
+    if (!Gm || !gu || !Agu || M < 0 || I < 0 || act < 0 || act > 3 || (I % LRP_GATED_IL)) return LRP_EINVAL;
+    if (dtype != LRP_F32 && dtype != LRP_BF16) return LRP_EINVAL;
+    if (ldgm < I || ldgu < 2 * (int64_t)I || ldagu < 2 * (int64_t)I) return LRP_ESHAPE;
+    const int epc = dtype == LRP_F32 ? 4 : 8;
+    if (!al16(Gm) || !al16(gu) || !al16(Agu) || !ld_ok(ldgm, epc) || !ld_ok(ldgu, epc) || !ld_ok(ldagu, epc)) return LRP_EALIGN;
+    if (M == 0 || I == 0) return LRP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    DISPATCH_T(dtype, {
+        constexpr int EPC = 16 / sizeof(T);                  // LRP_GATED_IL is a multiple of it: a chunk never straddles a block
+        hipLaunchKernelGGL((gated_cp_bwd_il_kernel<T, EPC>), dim3(grid_for((int64_t)M * I / EPC)), dim3(ENT), 0, st, (const T*)Gm, (const T*)gu,
+                           (T*)Agu, M, I, ldgm, ldgu, ldagu, act);
+    })
+    return lrp_check_launch();
 }
 
 extern "C" int lrp_rope_fwd(const void* x, void* xr, const float* cos_t, const float* sin_t, int rows,

@@ -31,6 +31,7 @@ import operator
 import torch
 
 from . import ops
+from .engine_cp import cp_layer_bwd, cp_request
 
 EXPLICIT = dict(lin=1e-8, add=1e-8, qk=1e-8, mask=1e-8, pv=1e-6, rope=1e-8, act=None)
 EFFICIENT = dict(lin=0.0, add=0.0, qk=0.0, mask=0.0, pv=0.0, rope=0.0, act=1e-10)
@@ -1180,7 +1181,8 @@ class LlamaLRP:
     layer are resident as MXFP4 codes + scales only (`flat_q`) and dequantised layer by layer into one scratch layer."""
 
     def __init__(self, cfg, W, dtype=torch.bfloat16, device="cuda", mode="efficient", max_seq=4096, sparse_top=True, fold_norm=None,
-                 weight_format=None):
+                 weight_format=None, rule="attnlrp"):
+        self.rule = cp_request(rule, mode, dtype=dtype, head_dim=cfg.get("head_dim"))
         self.weight_format = weight_format_request(weight_format, cfg)
         if not torch.cuda.is_available():
             raise RuntimeError("LlamaLRP needs a HIP device: the LRP kernels have no CPU fallback")
@@ -1384,11 +1386,21 @@ class LlamaLRP:
     def set_mode(self, mode):
         if mode not in ("explicit", "efficient"):
             raise ValueError(f"mode must be 'explicit' or 'efficient', got {mode!r}")
+        cp_request(getattr(self, "rule", "attnlrp"), mode)
         self.mode = mode
         self._graphs.clear()
         self.eps = dict(EXPLICIT if mode == "explicit" else EFFICIENT)
         # identity rule (*) gate Linear eps: act/(g+eps_lin) in explicit form, act/(g+1e-10) efficient
         self.eps_g = self.eps["lin"] if mode == "explicit" else self.eps["act"]
+
+    def set_rule(self, rule):
+        """"attnlrp" (the default: AttnLRP on every path, as without the keyword) or "cp" (CP-LRP, DESIGN.md section 25: q, k and the MLP's
+        gate detached; engine_cp.cp_layer_bwd is then every layer's backward).  The forward, the logits and generate() do not depend on it"""
+        cp_request(rule, self.mode, dtype=self.dtype, head_dim=self.cfg.get("head_dim"))
+        if rule == "cp" and type(self).forward is not LlamaLRP.forward:
+            raise ValueError(f'rule="cp" is served by the dense Llama / Qwen drivers, not by {type(self).__name__}')
+        self.rule = rule
+        self._graphs.clear()
 
     # ---------------------------------------------------------------------------------------------
     def release(self):
@@ -1396,10 +1408,12 @@ class LlamaLRP:
         self._arena = Arena(self.device, self.dtype)
         self._graphs.clear()
 
-    def forward(self, emb, B, S, row_iv=None, keep_m=False, rows=None):
+    def forward(self, emb, B, S, row_iv=None, keep_m=False, rows=None, cp=False):
         """keep_m: every dense layer's m (the down projection's input) in a buffer of its own, ("m", li), for the latent "mlp" read-out;
         the arithmetic is the same, only where m lands changes.  rows int64 [R] (explain(positions=...)): the explained rows of the
-        [B S, .] activations in place of each prompt's last one; the top layer then runs dense like every other layer"""
+        [B S, .] activations in place of each prompt's last one; the top layer then runs dense like every other layer.  cp: the forward a
+        CP-LRP backward reads (engine_cp): the same network with every layer's pre-activations gu stored -- no coefficient stash and no
+        fused layer (which stashes coefficients)"""
         c = self.cfg
         H, I, d, nq, nk = c["hidden"], c["inter"], c["head_dim"], c["n_heads"], c["n_kv"]
         M = B * S
@@ -1410,9 +1424,9 @@ class LlamaLRP:
         stash = []
         h_prev, branch = emb, None
         last = torch.arange(B, device=dev) * S + (S - 1) if rows is None else rows
-        coef = self._gated_coef(M)
+        coef = self._gated_coef(M) and not cp
         explicit = self.mode == "explicit"
-        nf = self._norm_fused(M, fwd_only=True) and ops.norm_fusion_part("fwd")          # K1n: the two norms + residual sums of a layer inside the GEMM epilogues around them
+        nf = not cp and self._norm_fused(M, fwd_only=True) and ops.norm_fusion_part("fwd")          # K1n: the two norms + residual sums of a layer inside the GEMM epilogues around them
         ready = None                      # (h, rstd1) of this layer, left by the previous layer's down-projection epilogue
         nL = len(self.layers)
         for li, Lw in enumerate(self.layers):
@@ -1556,6 +1570,14 @@ class LlamaLRP:
             hs = None if heads is None else heads.layer(li)
             am = None if attn_map is None else attn_map.layer(li)
             ws = None if weights is None else weights.layer(li)
+            if self.rule == "cp":
+                rel = ar.f32(("rel", li), M) if layer_relevance else None
+                Gs = Adn = cp_layer_bwd(self, li, st, Lw, None if st.get("top", False) else Gs, B, S, row_iv,
+                                        (Gs_last, A_last, last) if st.get("top", False) else None, Gm if "mlp" in latent else None, rel)
+                layer_R = layer_R + [rel] if layer_relevance else None
+                if "resid" in latent:
+                    ops.colsum_dot(st["h"], Gs, B, S, out=lat["R_resid"][li])
+                continue
             if full and not st.get("top", False):          # (Adn = Gs: eps = 0)
                 Gs = Adn = fused_layer_bwd(Gs, st, Lw, self.cos, self.sin, B, S, self.meta, self._alloc(li), row_iv, self._qk_norm(Lw), hs, am, ws)
                 layer_R = layer_R + [ops.readout(st["h"], Gs, out=ar.f32(("rel", li), M))] if layer_relevance else None
@@ -1717,6 +1739,8 @@ class LlamaLRP:
             emb = self._embed(input_ids.reshape(-1))
         wsink = self._weight_sink(weights, weights_out) if weights[0] else None
         keep_m, bopts = "mlp" in latent or "down" in weights[0], opts if wsink is None else dict(opts, weights=wsink)
+        if self.rule == "cp":
+            opts = dict(opts, cp=True)
         out, _ = explain_pipeline(self, lambda **rows: self.forward(emb, B, S, row_iv, keep_m=keep_m, **opts, **rows),
                                   lambda fw, i, want_R, lat, hs, am: self.backward(fw, emb, i, B, S, want_R, seed=seed, latent=lat, heads=hs,
                                                                                    attn_map=am, **bopts),
@@ -1777,6 +1801,7 @@ class LlamaLRP:
         R_tok_each [B, T, S] fp32, the answer x prompt map, and R_tok = R_tok_each.sum(1); no read-out keyword with it.
         Efficient placement only; not with seed or graph=True (ValueError, as for every bad position, weight, target or objective, raised
         before a kernel of the model runs).  Without positions nothing changes."""
+        cp_request(getattr(self, "rule", "attnlrp"), getattr(self, "mode", "efficient"), heads, attn_map, weights)
         wr = weight_request(weights, weight_layers, weights_out, self.cfg, len(getattr(self, "layers", ())), self.dtype,
                             getattr(self, "mode", "efficient"), graph)
         am = attn_map_request(attn_map, len(getattr(self, "layers", ())), self.cfg.get("n_heads", 0), self.cfg.get("head_dim"), self.dtype,
@@ -1797,7 +1822,7 @@ class LlamaLRP:
             return self._run(input_ids, emb, B, S, row_iv, idx, layer_relevance, return_G, seed, lat, hd, am, wr, weights_out, span=span)
         if emb is not None or lengths is not None or seed is not None or return_G:
             raise ValueError("graph=True takes input_ids only (no inputs_embeds / lengths / seed / return_G)")
-        return self._graphs((B, S, idx is not None, bool(layer_relevance), self.mode, tuple(sorted(lat)), tuple(sorted(hd)), am),
+        return self._graphs((B, S, idx is not None, bool(layer_relevance), self.mode, self.rule, tuple(sorted(lat)), tuple(sorted(hd)), am),
                             lambda ids, idx_: self._run(ids, None, B, S, None, idx_, layer_relevance, False, None, lat, hd, am), input_ids, idx)
 
     # --------------------------------------------------------------------------------------------- generation

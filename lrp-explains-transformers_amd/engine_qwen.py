@@ -80,10 +80,10 @@ class QwenLRP(E.LlamaLRP):
     (Qwen2) or qn, kn (Qwen3), and W has no "lm_head" when the embeddings are tied.  explain() is LlamaLRP.explain."""
 
     def __init__(self, cfg, W, dtype=torch.bfloat16, device="cuda", mode="efficient", max_seq=4096, sparse_top=True, fold_norm=None,
-                 weight_format=None):
+                 weight_format=None, rule="attnlrp"):
         cfg = dict(cfg, tied=bool(cfg.get("tied", "lm_head" not in W)))
         super().__init__(cfg, W, dtype=dtype, device=device, mode=mode, max_seq=max_seq, sparse_top=sparse_top, fold_norm=fold_norm,
-                         weight_format=weight_format)
+                         weight_format=weight_format, rule=rule)
 
     def set_mode(self, mode):
         if mode == "explicit":

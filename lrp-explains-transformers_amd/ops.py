@@ -453,6 +453,15 @@ def gated_act_bwd_il(Gm, gu, Agu, eps_g, eps_lin, act="silu"):
     return Agu
 
 
+def gated_cp_bwd_il(Gm, gu, Agu, act="silu"):
+    """CP-LRP through the gated MLP (the gate is detached): up slots of Agu = act(g) * Gm, gate slots = 0, interleaved layout of gated_act_bwd_il"""
+    M, I = Gm.shape
+    same(gu, Gm, Agu)
+    check(lib.lrp_gated_cp_bwd_il(p(Gm), p(gu), p(Agu), M, I, Gm.stride(0), gu.stride(0), Agu.stride(0), ACT[act], dt(gu), stream()),
+          "lrp_gated_cp_bwd_il")
+    return Agu
+
+
 GATED_FUSION = True      # module attribute (no environment knobs): False = GEMM + element-wise rule kernels, for A/B measurements and the
                          # fused-vs-unfused tests
 
@@ -1483,6 +1492,23 @@ def attn_bwd_dkv(q, k, v, q_t, Gho, Gho_t, lse, D, dk_h, dv_h, B, S, Hq, Hkv, d,
                                dv_h.stride(0), scale, eps_mask, eps_qk, int(causal), window, q_begin, *_iv(row_iv, B, S), dt(q), stream()),
           "lrp_attn_bwd_dkv")
     return dk_h, dv_h
+
+
+def attn_bwd_dv_ok(dtype, d):
+    """lrp_attn_bwd_dv serves (dtype, d): bf16 at d in {64, 96, 128}, fp32 at d in {16, 32, 64, 128}"""
+    return bool(dtype in _DT and lib.lrp_attn_bwd_dv_ok(_DT[dtype], d))
+
+
+def attn_bwd_dv(q, k, G, lse, dv, B, S, Hq, Hkv, d, scale, q_begin=0, row_iv=None, q_t=None, G_t=None):
+    """the CP-LRP attention backward (q, k detached): dv [B S, Hkv d] = sum over the GQA group of P^T G, causal, G the gradient of the attention
+    output as it is.  G_t: the head-transposed copy of G where attn_needs_transposed(q, d); q_t is accepted beside it (the operand list of
+    attn_bwd_dkv) and not read: no contraction of this kernel runs over Q^T."""
+    same(q, k, G, dv, q_t, G_t)
+    f32(lse)
+    check(lib.lrp_attn_bwd_dv(p(q), p(k), p(G), p(G_t), p(lse), p(dv), B, S, Hq, Hkv, d, q.stride(0), k.stride(0), G.stride(0),
+                              G_t.stride(2) if G_t is not None else 0, dv.stride(0), scale, q_begin, *_iv(row_iv, B, S), dt(q), stream()),
+          "lrp_attn_bwd_dv")
+    return dv
 
 
 def gqa_reduce(x, out, rows, Hkv, rep, d):
