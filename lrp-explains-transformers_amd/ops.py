@@ -1716,14 +1716,29 @@ def _moe_w(x, W):
     return False, (p(W),)
 
 
-def moe_gate_up_fwd(x, Wgu, plan, act="silu"):
+def _moe_buf(name, buf, rows, cols, like, dtype=None, pitched=True):
+    """an output buffer a caller hands to a MoE wrapper: [rows, cols] of `like`'s device and dtype (or `dtype`) with contiguous rows -- its
+    stride(0) is passed on as the pitch, so a [:, :cols] view of wider storage is served -- or contiguous where the kernel takes no pitch"""
+    dtype = like.dtype if dtype is None else dtype
+    if not torch.is_tensor(buf) or buf.dtype != dtype:
+        raise TypeError(f"{name}: must be a {dtype} tensor, got {buf.dtype if torch.is_tensor(buf) else type(buf).__name__}")
+    if buf.device != like.device:
+        raise TypeError(f"{name}: on {buf.device} next to operands on {like.device}")
+    if tuple(buf.shape) != (rows, cols) or (cols > 1 and buf.stride(1) != 1) or (not pitched and not buf.is_contiguous()):
+        raise ValueError(f"{name}: must be [{rows}, {cols}] with contiguous rows{'' if pitched else ' and no pitch'}, got {tuple(buf.shape)} with "
+                         f"strides {tuple(buf.stride())}")
+    return buf
+
+
+def moe_gate_up_fwd(x, Wgu, plan, act="silu", coef=None, m=None):
     """-> (coef [R, 2 I], m [R, I]) in plan-row order; x [T, H] rows are gathered through the plan inside the GEMM.  Wgu: the tensor
-    [E, 2 I, H] or a MoeQuantWeight of it (here and in the three GEMMs below: decoded inside the kernel, lrp_moe_*_q)"""
+    [E, 2 I, H] or a MoeQuantWeight of it (here and in the three GEMMs below: decoded inside the kernel, lrp_moe_*_q).  coef / m (here and
+    below: out, Agu, part, gw): a buffer to write into, rows may carry a pitch; only the first off[E] plan rows and no pad column are written"""
     E, I2, H = Wgu.shape
     I, R = I2 // 2, plan.rows
     q, wp = _moe_w(x, Wgu)
-    coef = torch.empty(R, 2 * I, device=x.device, dtype=x.dtype)
-    m = torch.empty(R, I, device=x.device, dtype=x.dtype)
+    coef = torch.empty(R, 2 * I, device=x.device, dtype=x.dtype) if coef is None else _moe_buf("moe_gate_up_fwd: coef", coef, R, 2 * I, x)
+    m = torch.empty(R, I, device=x.device, dtype=x.dtype) if m is None else _moe_buf("moe_gate_up_fwd: m", m, R, I, x)
     if q:
         _timed(2.0 * R * 2 * I * H, "moe_gate_up_fwd", lambda: lib.lrp_moe_gate_up_fwd_q(
             p(x), *wp, p(plan.buf), p(coef), p(m), plan.T, plan.k, plan.E, H, I, x.stride(0), coef.stride(0), m.stride(0), ACT[act],
@@ -1735,11 +1750,11 @@ def moe_gate_up_fwd(x, Wgu, plan, act="silu"):
     return coef, m
 
 
-def moe_down_fwd(m, Wd, plan):
+def moe_down_fwd(m, Wd, plan, out=None):
     """-> y [R, H] = m Wd[e]^T per plan row"""
     E, H, I = Wd.shape
     q, wp = _moe_w(m, Wd)
-    y = torch.empty(plan.rows, H, device=m.device, dtype=m.dtype)
+    y = torch.empty(plan.rows, H, device=m.device, dtype=m.dtype) if out is None else _moe_buf("moe_down_fwd: out", out, plan.rows, H, m)
     if q:
         _timed(2.0 * plan.rows * H * I, "moe_down_fwd", lambda: lib.lrp_moe_down_fwd_q(
             p(m), *wp, p(plan.buf), p(y), plan.T, plan.k, plan.E, H, I, m.stride(0), y.stride(0), dt(m), stream()), "lrp_moe_down_fwd_q")
@@ -1749,25 +1764,27 @@ def moe_down_fwd(m, Wd, plan):
     return y
 
 
-def moe_combine(rows, plan, w=None):
+def moe_combine(rows, plan, w=None, out=None):
     """-> out [T, H] = sum over live slots s of w[t, s] rows[row(t, s)] (w None: weight 1), fp32 accumulation in slot order"""
     H = rows.shape[1]
     same(rows, w)
-    out = torch.empty(plan.T, H, device=rows.device, dtype=rows.dtype)
+    out = torch.empty(plan.T, H, device=rows.device, dtype=rows.dtype) if out is None else _moe_buf("moe_combine: out", out, plan.T, H, rows)
     check(lib.lrp_moe_combine(p(rows), p(w), p(plan.buf), p(out), plan.T, plan.k, plan.E, H, rows.stride(0), out.stride(0), dt(rows),
                               stream()), "lrp_moe_combine")
     return out
 
 
-def moe_down_dgrad(G, Wd, coef, m, w, plan):
+def moe_down_dgrad(G, Wd, coef, m, w, plan, Agu=None, part=None, gw=None):
     """-> (Agu [R, 2 I] in [gate | up] order, G_w [T, k]) from the output gradient G [T, H] (gathered by token inside the GEMM)"""
     E, H, I = Wd.shape
     q, wp = _moe_w(G, Wd)
     same(G, coef, m, w)
     R = plan.rows
-    Agu = torch.empty(R, 2 * I, device=G.device, dtype=G.dtype)
-    part = torch.empty(R, I // 128, device=G.device, dtype=torch.float32)
-    gw = torch.empty(plan.T, plan.k, device=G.device, dtype=G.dtype)
+    Agu = torch.empty(R, 2 * I, device=G.device, dtype=G.dtype) if Agu is None else _moe_buf("moe_down_dgrad: Agu", Agu, R, 2 * I, G)
+    part = (torch.empty(R, I // 128, device=G.device, dtype=torch.float32) if part is None
+            else _moe_buf("moe_down_dgrad: part", part, R, I // 128, G, dtype=torch.float32, pitched=False))
+    gw = (torch.empty(plan.T, plan.k, device=G.device, dtype=G.dtype) if gw is None
+          else _moe_buf("moe_down_dgrad: gw", gw, plan.T, plan.k, G, pitched=False))
     fn, name = (lib.lrp_moe_down_dgrad_q, "lrp_moe_down_dgrad_q") if q else (lib.lrp_moe_down_dgrad, "lrp_moe_down_dgrad")
     _timed(2.0 * R * H * I, "moe_down_dgrad", lambda: fn(
         p(G), *wp, p(coef), p(m), p(w), p(plan.buf), p(Agu), p(part), plan.T, plan.k, plan.E, H, I, G.stride(0), coef.stride(0),
@@ -1776,11 +1793,11 @@ def moe_down_dgrad(G, Wd, coef, m, w, plan):
     return Agu, gw
 
 
-def moe_gate_up_dgrad(Agu, Wgu, plan):
+def moe_gate_up_dgrad(Agu, Wgu, plan, out=None):
     """-> per-row G_x [R, H] = Agu Wgu[e] (NN on the stored weight)"""
     E, I2, H = Wgu.shape
     q, wp = _moe_w(Agu, Wgu)
-    gx = torch.empty(plan.rows, H, device=Agu.device, dtype=Agu.dtype)
+    gx = torch.empty(plan.rows, H, device=Agu.device, dtype=Agu.dtype) if out is None else _moe_buf("moe_gate_up_dgrad: out", out, plan.rows, H, Agu)
     fn, name = (lib.lrp_moe_gate_up_dgrad_q, "lrp_moe_gate_up_dgrad_q") if q else (lib.lrp_moe_gate_up_dgrad, "lrp_moe_gate_up_dgrad")
     _timed(2.0 * plan.rows * I2 * H, "moe_gate_up_dgrad", lambda: fn(
         p(Agu), *wp, p(plan.buf), p(gx), plan.T, plan.k, plan.E, H, I2 // 2, Agu.stride(0), gx.stride(0), dt(Agu), stream()), name)

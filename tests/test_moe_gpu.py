@@ -135,8 +135,11 @@ def test_gelu_tanh_experts():
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_deterministic_and_row_independent(dtype):
-    """two runs are bit-identical; a token's output and gradients do not change by a bit when other tokens are appended (every expert's row
-    count and every tile position change) -- what keeps prompts batch-invariant"""
+    """two runs are bit-identical; a token's output and gradients do not change by a bit when other tokens are appended or prepended -- what
+    keeps prompts batch-invariant.  Appended tokens (the first 300 of 700 kept) change every expert's row count and so every expert's first
+    plan row p0, but the plan is a stable sort: a kept token keeps its row index inside its expert, and with it its M tile and its MFMA row.
+    Dropping the LEADING tokens (the last 300 kept) moves the kept rows inside their experts as well.  Planted moves by 1 / 127 / 128 rows,
+    op by op: tests/test_moe_ops_gpu.py::test_rows_do_not_depend_on_their_position"""
     _need_gpu()
     (x, w, Wgu, Wd, G), idx = make(700, 8, 64, 512, 256, dtype, seed=3)
     a = run(x, idx, w, Wgu, Wd, G)
@@ -145,6 +148,10 @@ def test_deterministic_and_row_independent(dtype):
     n = 300
     c = run(x[:n], idx[:n], w[:n], Wgu, Wd, G[:n])
     assert all(torch.equal(u[:n], v) for u, v in zip(a, c))
+    d = run(x[-n:], idx[-n:], w[-n:], Wgu, Wd, G[-n:])
+    assert all(torch.equal(u[-n:], v) for u, v in zip(a, d))
+    rank = lambda i: (i.flatten()[:, None] == i.flatten()[None, :]).tril(-1).sum(1)      # noqa: E731  (a slot's row index inside its expert)
+    assert bool((rank(idx)[-n * idx.shape[1]:] != rank(idx[-n:])).any())
 
 
 @pytest.mark.parametrize("case", ["tiny", "fanout", "padded"])
