@@ -8,12 +8,12 @@
 // the order of every sum is fixed: bitwise repeatable.
 //
 // bf16 (moe_wgrad_bf16_kernel): wgrad_rel_bf16_kernel's form -- a 128 (n) x 128 (k) tile per 4-wave workgroup, blockIdx.z = expert, the
-// expert's rows walked in tiles of 64, both MFMA operands ds_read_b64_tr_b16 reads of the xor-swizzled row-major LDS images (same offsets
-// as wgrad.hip: see the bank argument there), v_mfma_f32_16x16x32_bf16 into one fp32 accumulator set.  Rows past the expert's count are
-// staged as ZEROS under a full EXEC mask; the row index (plan row or gathered token) and the scale are resolved ONE TILE AHEAD of the
-// loads that use them (perm -> row is a dependent load chain: resolved a tile early it is off the loop's critical path), the loads one
-// tile ahead of their LDS stores.  s is folded into G while staging, G' = bf16(float(G) s): one extra bf16 rounding (1/2 w is exact).
-// A separate kernel, not a shared template with wgrad.hip: the dense kernel compiles exactly as it did.
+// expert's rows walked in tiles of 64.  The LDS operand images, the transposed fragment read, the staging store, the MFMA block of a staged
+// tile and the walk over a lane's accumulators are wgrad_tiles.hpp's (the dense kernel shares the first three and keeps the others written
+// out: see that header); this file owns the row resolution, the global loads, the token loop and the epilogues.  Rows past the expert's count are staged as ZEROS; the row index (plan row or gathered token) and the
+// scale are resolved ONE TILE AHEAD of the loads that use them (perm -> row is a dependent load chain: resolved a tile early it is off the
+// loop's critical path), the loads one tile ahead of their LDS stores.  s is folded into G while staging (the down mode), G' = bf16(float(G)
+// s): one extra bf16 rounding (1/2 w is exact).
 // An expert WITHOUT rows (a branch that is uniform over the workgroup): accumulate = 0 -> its block is written as exact zeros whatever out
 // and W hold; accumulate != 0 -> the block is not touched (and nothing of it is read).
 // _q (W held as MXFP4, include/lrp_hip_moe_mxfp4.h): the epilogue reads one scale byte and two code bytes per 4 outputs and decodes them
@@ -22,44 +22,52 @@
 // fp32 (moe_wgrad_f32_kernel, the parity path): the grouped form of wgrad_rel_f32_kernel: 64 x 64 outputs per workgroup, rows in tiles of
 // 16, s G X formed exactly and summed in fp64, W acc rounded ONCE to fp32.
 #include "moe_gemm.hpp"
+#include "wgrad_tiles.hpp"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) short mw_s16x4;
-typedef __attribute__((ext_vector_type(8))) short mw_s16x8;
-typedef __attribute__((address_space(3))) mw_s16x4* mw_lds_s16x4_t;
-
-constexpr int MW_TILE = 128;                      // output rows (n) and columns (k) of a workgroup's tile
-constexpr int MW_TT = 64;                         // expert rows per staging tile
-constexpr int MW_OPND = MW_TT * 256;              // bytes of one operand image
-constexpr int MW_LDS = 2 * MW_OPND;
 constexpr int MW_GATE_UP = 0, MW_DOWN = 1;        // (LRP_MOE_WGRAD_GATE_UP / _DOWN)
 
-LRP_DEVICE uint32_t mw_off(int row, int ch) { return 256u * (uint32_t)row + 16u * (uint32_t)(ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
+// 4 of the 8 values of one code word times its block scale, as fp32 (every decoded value is exact in T)
+template <typename T> LRP_DEVICE void mw_decode4(uint32_t word, uint32_t sc, float* w) {
+    T v[8];
+    mx_decode8(word, sc, v);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w[e] = (float)v[e];
+}
 
-LRP_DEVICE bf16x8 mw_frag_tr(const char* img, uint32_t off0, uint32_t off1) {
-    const mw_s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((mw_lds_s16x4_t)(img + off0));
-    const mw_s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((mw_lds_s16x4_t)(img + off1));
-    const mw_s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(bf16x8, v);
+// what an epilogue needs once per output row n of expert ex: row n of W[e] (Q: of its code and scale bytes) and of out[e]
+struct MwRow {
+    const void* w;
+    const uint8_t* sc;
+    float* out;
+};
+template <typename T, bool Q>
+LRP_DEVICE MwRow mw_row(const void* W, const uint8_t* scales, float* out, int ex, int N, int K, int n) {
+    const int64_t row = (int64_t)ex * N + n;
+    if constexpr (Q) return MwRow{reinterpret_cast<const uint8_t*>(W) + row * (K >> 1), scales + row * (K >> 5), out + row * K};
+    else return MwRow{reinterpret_cast<const T*>(W) + row * K, nullptr, out + row * K};
 }
 
 // W[e][n, k .. k + 3] as fp32: read as stored, or decoded from one scale byte and two code bytes (k is a multiple of 4, K of 128)
 template <typename T, bool Q>
-LRP_DEVICE void mw_weight4(const void* W, const uint8_t* scales, int64_t row, int K, int k, float* w) {
+LRP_DEVICE void mw_weight4(const MwRow& r, int k, float* w) {
     if constexpr (Q) {
-        const uint8_t* codes = reinterpret_cast<const uint8_t*>(W);
-        const uint32_t word = *reinterpret_cast<const uint16_t*>(codes + row * (K >> 1) + (k >> 1));
-        const uint32_t sc = scales[row * (K >> 5) + (k >> 5)];
-        T v[8];
-        mx_decode8(word, sc, v);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = (float)v[e];
+        const uint32_t word = *reinterpret_cast<const uint16_t*>(reinterpret_cast<const uint8_t*>(r.w) + (k >> 1));
+        mw_decode4<T>(word, r.sc[k >> 5], w);
     } else {
-        const T* p = reinterpret_cast<const T*>(W) + row * K + k;
+        const T* p = reinterpret_cast<const T*>(r.w) + k;
 #pragma unroll
         for (int e = 0; e < 4; ++e) w[e] = (float)p[e];
     }
+}
+
+// the fp32 kernel's form: the 4 weights around column k of row `row` of the whole [E N, K] MXFP4 tensor, addressed from its base (with the
+// row pointers of mw_row the fp32 MXFP4 epilogue grew by 118 instructions; in this form the fp32 kernels compile to their previous text)
+LRP_DEVICE void mw_weight4_q(const void* W, const uint8_t* scales, int64_t row, int K, int k, float* w) {
+    const uint8_t* codes = reinterpret_cast<const uint8_t*>(W);
+    const uint32_t word = *reinterpret_cast<const uint16_t*>(codes + row * (K >> 1) + (k >> 1));
+    mw_decode4<float>(word, scales[row * (K >> 5) + (k >> 5)], w);
 }
 
 template <int MODE, bool Q>
@@ -68,25 +76,17 @@ __global__ __launch_bounds__(256) void moe_wgrad_bf16_kernel(const bf16_t* __res
                                                              const int* __restrict__ plan, float* __restrict__ out, int R, int kslots, int E,
                                                              int N, int K, int64_t ldg, int64_t ldx, int accumulate) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n0 = blockIdx.y * MW_TILE, k0 = blockIdx.x * MW_TILE, ex = blockIdx.z;
+    const int tid = threadIdx.x;
+    const int n0 = blockIdx.y * WG_TILE, k0 = blockIdx.x * WG_TILE, ex = blockIdx.z;
     const PlanView P = plan_view(plan, R, E);
     const int M = P.cnt[ex], p0 = P.off[ex];
-    const int wn = wave >> 1, wk = wave & 1;
-    const int i16 = lane & 15, hi = lane >> 4, q = i16 >> 2, p = i16 & 3;
-    float* oute = out + (int64_t)ex * N * K;
+    const WgLane L = wg_lane(tid);
+    f32x4 acc[4][4];
     if (M == 0) {                                                          // (uniform: the whole workgroup leaves here)
         if (accumulate) return;
-#pragma unroll
-        for (int jg = 0; jg < 4; ++jg) {
-            const int n = n0 + 64 * wn + 16 * jg + i16;
-            if (n >= N) continue;
-#pragma unroll
-            for (int jx = 0; jx < 4; ++jx) {
-                const int k = k0 + 64 * wk + 16 * jx + 4 * hi;
-                if (k < K) *reinterpret_cast<f32x4*>(oute + (int64_t)n * K + k) = f32x4{0.f, 0.f, 0.f, 0.f};
-            }
-        }
+        wg_for_each(
+            n0, k0, L, N, K, acc, [&](int n) { return out + ((int64_t)ex * N + n) * K; },
+            [&](float* orow, int k, const f32x4&) { *reinterpret_cast<f32x4*>(orow + k) = f32x4{0.f, 0.f, 0.f, 0.f}; });     // (acc is not read)
         return;
     }
     // ---- staging: thread -> 16-byte chunk sch of the expert rows srow + 16 i
@@ -125,103 +125,57 @@ __global__ __launch_bounds__(256) void moe_wgrad_bf16_kernel(const bf16_t* __res
             sv[i] = svn[i];
         }
     };
-    auto store = [&]() {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t o = mw_off(srow + 16 * i, sch);
-            u32x4 g = gr[i];
-            if constexpr (MODE == MW_DOWN) {
-                bf16x8 v = __builtin_bit_cast(bf16x8, g);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = (bf16_t)((float)v[e] * sv[i]);
-                g = __builtin_bit_cast(u32x4, v);
-            }
-            *reinterpret_cast<u32x4*>(smem + o) = g;
-            *reinterpret_cast<u32x4*>(smem + MW_OPND + o) = xr[i];
-        }
-    };
-    f32x4 acc[4][4];                                                   // [k tile jx][n tile jg]
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    wg_clear(acc);
 
     resolve(0);
     load();
-    resolve(MW_TT);
-    for (int t0 = 0; t0 < M; t0 += MW_TT) {
+    resolve(WG_TT);
+    for (int t0 = 0; t0 < M; t0 += WG_TT) {
         __syncthreads();                                               // the previous tile's fragment reads are done
-        store();
+        wg_stage<MODE == MW_DOWN>(smem, srow, sch, gr, xr, sv);
         __syncthreads();
-        if (t0 + MW_TT < M) {                                          // (uniform branch) in flight under the MFMAs below
+        if (t0 + WG_TT < M) {                                          // (uniform branch) in flight under the MFMAs below
             load();
-            resolve(t0 + 2 * MW_TT);
+            resolve(t0 + 2 * WG_TT);
         }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int r0 = 32 * ks + 8 * hi + q, r1 = r0 + 4;
-            bf16x8 fg[4], fx[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int cg = 8 * wn + 2 * j + (p >> 1), cx = 8 * wk + 2 * j + (p >> 1);
-                fg[j] = mw_frag_tr(smem, mw_off(r0, cg) + 8 * (p & 1), mw_off(r1, cg) + 8 * (p & 1));
-                fx[j] = mw_frag_tr(smem + MW_OPND, mw_off(r0, cx) + 8 * (p & 1), mw_off(r1, cx) + 8 * (p & 1));
-            }
-#pragma unroll
-            for (int jx = 0; jx < 4; ++jx)
-#pragma unroll
-                for (int jg = 0; jg < 4; ++jg) acc[jx][jg] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fx[jx], fg[jg], acc[jx][jg], 0, 0, 0);
-        }
+        wg_mma_tile(smem, L, acc);
     }
     // ---- epilogue: out[e][n, k .. k + 3] (+)= W[e][n, k .. k + 3] acc
+    auto row = [&](int n) { return mw_row<bf16_t, Q>(W, scales, out, ex, N, K, n); };
+    wg_for_each(n0, k0, L, N, K, acc, row, [&](const MwRow& r, int k, const f32x4& a) {
+        float wv[4];
+        mw_weight4<bf16_t, Q>(r, k, wv);
+        float* dst = r.out + k;
+        f32x4 v;
 #pragma unroll
-    for (int jg = 0; jg < 4; ++jg) {
-        const int n = n0 + 64 * wn + 16 * jg + i16;
-        if (n >= N) continue;
-        const int64_t wrow = (int64_t)ex * N + n;
+        for (int e = 0; e < 4; ++e) v[e] = wv[e] * a[e];
+        if (accumulate) {
+            const f32x4 old = *reinterpret_cast<const f32x4*>(dst);
 #pragma unroll
-        for (int jx = 0; jx < 4; ++jx) {
-            const int k = k0 + 64 * wk + 16 * jx + 4 * hi;
-            if (k >= K) continue;                                      // (K is a multiple of 8: k < K means k + 3 < K)
-            float wv[4];
-            mw_weight4<bf16_t, Q>(W, scales, wrow, K, k, wv);
-            float* dst = oute + (int64_t)n * K + k;
-            f32x4 v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = wv[e] * acc[jx][jg][e];
-            if (accumulate) {
-                const f32x4 old = *reinterpret_cast<const f32x4*>(dst);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += old[e];
-            }
-            *reinterpret_cast<f32x4*>(dst) = v;
+            for (int e = 0; e < 4; ++e) v[e] += old[e];
         }
-    }
+        *reinterpret_cast<f32x4*>(dst) = v;
+    });
 }
-
-constexpr int MF_TILE = 64, MF_TT = 16;
 
 template <int MODE, bool Q>
 __global__ __launch_bounds__(256) void moe_wgrad_f32_kernel(const float* __restrict__ G, const float* __restrict__ X, const void* __restrict__ W,
                                                             const uint8_t* __restrict__ scales, const float* __restrict__ w,
                                                             const int* __restrict__ plan, float* __restrict__ out, int R, int kslots, int E,
                                                             int N, int K, int64_t ldg, int64_t ldx, int accumulate) {
-    __shared__ float Gs[MF_TT][MF_TILE], Xs[MF_TT][MF_TILE], Ss[MF_TT];
-    __shared__ int Gi[MF_TT], Xi[MF_TT];
+    __shared__ float Gs[WF_TT][WF_TILE], Xs[WF_TT][WF_TILE], Ss[WF_TT];
+    __shared__ int Gi[WF_TT], Xi[WF_TT];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const int n0 = blockIdx.y * MF_TILE, k0 = blockIdx.x * MF_TILE, ex = blockIdx.z;
+    const int n0 = blockIdx.y * WF_TILE, k0 = blockIdx.x * WF_TILE, ex = blockIdx.z;
     const PlanView P = plan_view(plan, R, E);
     const int M = P.cnt[ex], p0 = P.off[ex];
     float* oute = out + (int64_t)ex * N * K;
     if (M == 0 && accumulate) return;                                  // (uniform)
     double acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
-    for (int t0 = 0; t0 < M; t0 += MF_TT) {
+    wf_clear(acc);
+    for (int t0 = 0; t0 < M; t0 += WF_TT) {
         __syncthreads();
-        if (tid < MF_TT) {
+        if (tid < WF_TT) {
             const int t = t0 + tid;
             int gi = -1, xi = -1;
             float s = 0.f;
@@ -245,7 +199,7 @@ __global__ __launch_bounds__(256) void moe_wgrad_f32_kernel(const float* __restr
         }
         __syncthreads();
 #pragma unroll 4
-        for (int tt = 0; tt < MF_TT; ++tt) {
+        for (int tt = 0; tt < WF_TT; ++tt) {
             const double r = (double)Ss[tt];
             double g[4], x[4];
 #pragma unroll
@@ -275,7 +229,7 @@ __global__ __launch_bounds__(256) void moe_wgrad_f32_kernel(const float* __restr
             float wv;
             if constexpr (Q) {                                         // (K is a multiple of 128: k - b is a multiple of 4 inside one block)
                 float w4[4];
-                mw_weight4<float, true>(W, scales, wrow, K, k - b, w4);
+                mw_weight4_q(W, scales, wrow, K, k - b, w4);
                 wv = w4[b];
             } else {
                 wv = reinterpret_cast<const float*>(W)[wrow * K + k];
@@ -288,15 +242,13 @@ __global__ __launch_bounds__(256) void moe_wgrad_f32_kernel(const float* __restr
 }
 
 int mw_check(int T, int k, int E, int N, int K, int64_t ldg, int64_t ldx, int mode, int dtype, int quantised) {
-    if (dtype != LRP_F32 && dtype != LRP_BF16) return LRP_EINVAL;
     if (mode != MW_GATE_UP && mode != MW_DOWN) return LRP_EINVAL;
+    const int ok = wg_shape_ok(N, K, dtype);                               // (LRP_EINVAL or LRP_ESHAPE: both are judged before any LRP_EALIGN)
+    if (ok != 1) return ok;
     if (T < 1 || k < 1 || E < 1 || N < 1 || K < 1) return LRP_ESHAPE;
     if (E > MOE_EMAX || (int64_t)T * k >= (1ll << 30)) return LRP_ESHAPE;
     if (ldg < N || ldx < K) return LRP_ESHAPE;
-    const int tile = dtype == LRP_BF16 ? MW_TILE : MF_TILE;
-    if (((int64_t)N + tile - 1) / tile > 65535) return LRP_ESHAPE;
-    if (dtype == LRP_BF16 && (N % 8 || K % 8)) return LRP_ESHAPE;          // 16-byte chunks of G and X rows: inside or outside as a whole
-    if (quantised && K % 128) return LRP_ESHAPE;                           // rows of scale bytes on the 4-byte grid (lrp_hip_moe_mxfp4.h)
+    if (quantised && K % 128) return LRP_ESHAPE;                          // rows of scale bytes on the 4-byte grid (lrp_hip_moe_mxfp4.h)
     if ((ldg * esz(dtype)) % 16 || (ldx * esz(dtype)) % 16) return LRP_EALIGN;
     return 1;
 }
@@ -313,14 +265,14 @@ int mw_launch(const void* G, const void* X, const void* W, const void* scales, c
     const uint8_t* sc = reinterpret_cast<const uint8_t*>(scales);
     const int R = T * k;
     if (dtype == LRP_BF16) {
-        const dim3 grid((unsigned)((K + MW_TILE - 1) / MW_TILE), (unsigned)((N + MW_TILE - 1) / MW_TILE), (unsigned)E);
+        const dim3 grid((unsigned)((K + WG_TILE - 1) / WG_TILE), (unsigned)((N + WG_TILE - 1) / WG_TILE), (unsigned)E);
         lrp_with_bool(mode == MW_DOWN, [&](auto DOWN) {
             constexpr int MODE = decltype(DOWN)::value ? MW_DOWN : MW_GATE_UP;
-            hipLaunchKernelGGL((moe_wgrad_bf16_kernel<MODE, Q>), grid, dim3(256), MW_LDS, st, (const bf16_t*)G, (const bf16_t*)X, W, sc,
+            hipLaunchKernelGGL((moe_wgrad_bf16_kernel<MODE, Q>), grid, dim3(256), WG_LDS, st, (const bf16_t*)G, (const bf16_t*)X, W, sc,
                                (const bf16_t*)w, plan, out, R, k, E, N, K, ldg, ldx, accumulate);
         });
     } else {
-        const dim3 grid((unsigned)((K + MF_TILE - 1) / MF_TILE), (unsigned)((N + MF_TILE - 1) / MF_TILE), (unsigned)E);
+        const dim3 grid((unsigned)((K + WF_TILE - 1) / WF_TILE), (unsigned)((N + WF_TILE - 1) / WF_TILE), (unsigned)E);
         lrp_with_bool(mode == MW_DOWN, [&](auto DOWN) {
             constexpr int MODE = decltype(DOWN)::value ? MW_DOWN : MW_GATE_UP;
             hipLaunchKernelGGL((moe_wgrad_f32_kernel<MODE, Q>), grid, dim3(256), 0, st, (const float*)G, (const float*)X, W, sc, (const float*)w,

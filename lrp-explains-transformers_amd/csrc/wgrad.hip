@@ -1,51 +1,24 @@
 // wgrad.hip -- the per-weight relevance of a Linear, out[r(n), k] (+)= W[n, k] sum_t G[t, n] rs[t] X[t, k]  (include/lrp_hip_wgrad.h):
 // the one GEMM form of the library that contracts over the TOKEN dimension, with the product by W and the accumulate in its epilogue.
+// The LDS operand images (layout and bank argument), the transposed fragment read, the staging store and the tile constants are
+// wgrad_tiles.hpp's, shared with the grouped form (moe_wgrad.hip).  The accumulator clear, the MFMA block of a staged tile and the epilogue
+// loops are WRITTEN OUT here although that header has them as functions: see its head for the measurement that decided it.
 //
-// bf16 (wgrad_rel_bf16_kernel): one workgroup of 4 waves owns a 128 (n) x 128 (k) tile of the result and walks the tokens in tiles of 64.
-// G and X are token-major, so the contraction index is the ROW of both operand tiles: both MFMA operands (8 consecutive tokens of one
-// column) are gathered out of row-major LDS images by two ds_read_b64_tr_b16 each (4 token rows per read).
-//   LDS (32 KiB, dynamic, nothing static in front of it): [G image][X image], each 64 token rows x 256 B; the 16-byte chunk ch of row r sits
-//   at 256 r + 16 (ch ^ (((r & 3) << 2) | ((r >> 2) & 3))).  A 16-lane group of a transposed read takes 4 rows x 32 B, the two groups of a
-//   32-lane half are 8 rows apart in the same columns: by the bank rule (bank = (addr / 4) % 64) the xor maps those 8 rows to 64 distinct banks --
-//   worked out on paper, not confirmed with a bank-conflict counter.  Every lane's address is 8-byte
-//   aligned (chunk base + 0 / 8) and the reads run under a full EXEC mask: rows past M and chunks past N / K are staged as ZEROS, never
-//   masked out.
+// bf16 (wgrad_rel_bf16_kernel): a 128 (n) x 128 (k) tile per 4-wave workgroup, the tokens in tiles of 64.
 //   Staging goes through registers (4 + 4 global 16-byte loads per thread and token tile, issued one tile ahead of their LDS stores, so the
 //   loads of tile t + 1 can be in flight under the MFMAs of tile t -- the intent; no trace confirms the overlap, and the measured rate in DESIGN.md
-//   section 16 says the token loop is what binds); rs is folded into G here: G' = bf16(float(G) rs[t]), one extra rounding.
-//   Wave w: n rows 64 (w >> 1) .., k columns 64 (w & 1) ..: 4 x 4 tiles of v_mfma_f32_16x16x32_bf16, acc = mfma(X fragment, G fragment), so
-//   lane l holds out[n = .. + (l & 15)][k = .. + 4 (l >> 4) + 0..3]: the epilogue reads 4 bf16 of W, multiplies in fp32 and stores (or
-//   adds to) one float4 per 16 x 16 tile.
-// fp32 (wgrad_rel_f32_kernel, the parity path): a plain LDS-tiled kernel, 64 x 64 outputs per workgroup, 4 x 4 per thread, tokens in tiles
-// of 16.  The token sum runs in fp64 (G rs X is formed exactly, the sum carries 2^-53 per step) and W acc is rounded ONCE to fp32, so the
-// parity path's own error is one fp32 rounding whatever M is.
+//   section 16 says the token loop is what binds); rs is folded into G while staging: G' = bf16(float(G) rs[t]), one extra rounding.
+//   The epilogue reads 4 bf16 of W, multiplies in fp32 and stores (or adds to) one float4 per 16 x 16 tile.
+// fp32 (wgrad_rel_f32_kernel, the parity path): 64 x 64 outputs per workgroup, tokens in tiles of 16.  The token sum runs in fp64 (G rs X is
+// formed exactly) and W acc is rounded ONCE to fp32, so the parity path's own error is one fp32 rounding whatever M is.
 // Both kernels: one launch, no workspace, no atomics; a result element is formed by one thread in token order -- bitwise repeatable.
 //
 // lrp_wgrad (PLAIN = true of both kernels): the plain weight.grad of the same Linear, out[n, k] = sum_t G[t, n] X[t, k], in the operands' dtype.
 // The token loops are the ones above (one body, two epilogues); the plain epilogue reads nothing: bf16 rounds the fp32 accumulator once
 // (round-to-nearest-even) and stores one 8-byte bf16x4 per 16 x 16 tile and lane, fp32 rounds the fp64 sum once.
-#include "common.hpp"
+#include "wgrad_tiles.hpp"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) short wg_s16x4;
-typedef __attribute__((ext_vector_type(8))) short wg_s16x8;
-typedef __attribute__((address_space(3))) wg_s16x4* wg_lds_s16x4_t;
-
-constexpr int WG_TILE = 128;                      // output rows (n) and columns (k) of a workgroup's tile
-constexpr int WG_TT = 64;                         // tokens per staging tile
-constexpr int WG_OPND = WG_TT * 256;              // bytes of one operand image
-constexpr int WG_LDS = 2 * WG_OPND;
-
-LRP_DEVICE uint32_t wg_off(int row, int ch) { return 256u * (uint32_t)row + 16u * (uint32_t)(ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-
-// 8 consecutive tokens (rows r0 .. r0 + 7 of this lane's 16-lane group) of one column, as the MFMA operand
-LRP_DEVICE bf16x8 wg_frag_tr(const char* img, uint32_t off0, uint32_t off1) {
-    const wg_s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wg_lds_s16x4_t)(img + off0));
-    const wg_s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wg_lds_s16x4_t)(img + off1));
-    const wg_s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(bf16x8, v);
-}
 
 template <bool RS, bool PLAIN>
 __global__ __launch_bounds__(256) void wgrad_rel_bf16_kernel(const bf16_t* __restrict__ G, const bf16_t* __restrict__ X,
@@ -72,21 +45,6 @@ __global__ __launch_bounds__(256) void wgrad_rel_bf16_kernel(const bf16_t* __res
             if constexpr (RS) rsv[i] = ok ? rs[t] : 0.f;
         }
     };
-    auto store = [&]() {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const uint32_t o = wg_off(srow + 16 * i, sch);
-            u32x4 g = gr[i];
-            if constexpr (RS) {
-                bf16x8 v = __builtin_bit_cast(bf16x8, g);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = (bf16_t)((float)v[e] * rsv[i]);
-                g = __builtin_bit_cast(u32x4, v);
-            }
-            *reinterpret_cast<u32x4*>(smem + o) = g;
-            *reinterpret_cast<u32x4*>(smem + WG_OPND + o) = xr[i];
-        }
-    };
     // ---- fragment addresses: lane 4 q + p of a 16-lane group supplies row q, columns 4 p .. 4 p + 3 of the group's 4 x 16 block
     const int wn = wave >> 1, wk = wave & 1;
     const int i16 = lane & 15, hi = lane >> 4, q = i16 >> 2, p = i16 & 3;
@@ -99,7 +57,7 @@ __global__ __launch_bounds__(256) void wgrad_rel_bf16_kernel(const bf16_t* __res
     load(0);
     for (int t0 = 0; t0 < M; t0 += WG_TT) {
         __syncthreads();                                               // the previous tile's fragment reads are done
-        store();
+        wg_stage<RS>(smem, srow, sch, gr, xr, rsv);
         __syncthreads();
         if (t0 + WG_TT < M) load(t0 + WG_TT);                          // (uniform branch) in flight under the MFMAs below
 #pragma unroll
@@ -163,8 +121,6 @@ __global__ __launch_bounds__(256) void wgrad_rel_bf16_kernel(const bf16_t* __res
     }
 }
 
-constexpr int WF_TILE = 64, WF_TT = 16;
-
 template <bool PLAIN>
 __global__ __launch_bounds__(256) void wgrad_rel_f32_kernel(const float* __restrict__ G, const float* __restrict__ X, const float* __restrict__ W,
                                                             float* __restrict__ out, const float* __restrict__ rs, const int* __restrict__ rmap,
@@ -174,10 +130,7 @@ __global__ __launch_bounds__(256) void wgrad_rel_f32_kernel(const float* __restr
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int n0 = blockIdx.y * WF_TILE, k0 = blockIdx.x * WF_TILE;
     double acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
+    wf_clear(acc);
     for (int t0 = 0; t0 < M; t0 += WF_TT) {
         __syncthreads();
 #pragma unroll
@@ -226,14 +179,10 @@ __global__ __launch_bounds__(256) void wgrad_rel_f32_kernel(const float* __restr
 }  // namespace
 
 extern "C" int lrp_wgrad_rel_ok(int M, int N, int K, int64_t ldg, int64_t ldx, int64_t ldw, int64_t ldo, int dtype) {
-    if (dtype != LRP_F32 && dtype != LRP_BF16) return LRP_EINVAL;
+    const int ok = wg_shape_ok(N, K, dtype);                              // (LRP_EINVAL or LRP_ESHAPE: both are judged before any LRP_EALIGN)
+    if (ok != 1) return ok;
     if (M < 1 || N < 1 || K < 1 || ldg < N || ldx < K || ldw < K || ldo < K) return LRP_ESHAPE;
-    const int tile = dtype == LRP_BF16 ? WG_TILE : WF_TILE;
-    if (((int64_t)N + tile - 1) / tile > 65535) return LRP_ESHAPE;
-    if (dtype == LRP_BF16) {
-        if (N % 8 || K % 8) return LRP_ESHAPE;                            // 16-byte chunks of G and X rows: inside or outside as a whole
-        if (ldg % 8 || ldx % 8 || ldw % 8 || ldo % 4) return LRP_EALIGN;
-    }
+    if (dtype == LRP_BF16 && (ldg % 8 || ldx % 8 || ldw % 8 || ldo % 4)) return LRP_EALIGN;
     return 1;
 }
 
@@ -260,14 +209,10 @@ extern "C" int lrp_wgrad_rel(const void* G, const void* X, const void* W, float*
 }
 
 extern "C" int lrp_wgrad_ok(int M, int N, int K, int64_t ldg, int64_t ldx, int64_t ldo, int dtype) {
-    if (dtype != LRP_F32 && dtype != LRP_BF16) return LRP_EINVAL;
+    const int ok = wg_shape_ok(N, K, dtype);
+    if (ok != 1) return ok;
     if (M < 1 || N < 1 || K < 1 || ldg < N || ldx < K || ldo < K) return LRP_ESHAPE;
-    const int tile = dtype == LRP_BF16 ? WG_TILE : WF_TILE;
-    if (((int64_t)N + tile - 1) / tile > 65535) return LRP_ESHAPE;
-    if (dtype == LRP_BF16) {
-        if (N % 8 || K % 8) return LRP_ESHAPE;                            // 16-byte chunks of G and X rows: inside or outside as a whole
-        if (ldg % 8 || ldx % 8 || ldo % 4) return LRP_EALIGN;             // out: one 8-byte bf16x4 store per lane
-    }
+    if (dtype == LRP_BF16 && (ldg % 8 || ldx % 8 || ldo % 4)) return LRP_EALIGN;      // out: one 8-byte bf16x4 store per lane
     return 1;
 }
 
