@@ -96,10 +96,12 @@ def gemm_nt(a, b, bias=None, out=None, out_dtype=None):
         if b3.stride(-1) != 1 or b3.stride(-2) % e or (batch > 1 and b3.stride(0) % e) or b3.data_ptr() % 16:
             b3 = b3.contiguous()
         sB, ldb = (b3.stride(0) if batch > 1 else 0), b3.stride(1)
-    odt = out_dtype or a.dtype
+    odt = out_dtype or (out.dtype if out is not None else a.dtype)
     bias = aux(bias, a, N)
     if out is None:
         out = torch.empty(*lead, M, N, device=a.device, dtype=odt)
+    if out.dtype != odt:
+        raise TypeError(f"gemm_nt: out is {out.dtype}, out_dtype {odt}")
     o3 = out.view(-1, M, N)
     assert o3.stride(-1) == 1
     rc = lib.lrp_gemm_nt(p(a3), p(b3), p(o3), p(bias), M, N, K, a3.stride(1), ldb, o3.stride(1), batch,

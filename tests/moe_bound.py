@@ -282,11 +282,13 @@ def act_arith(g_abs, a_abs, act, dtype):
     return a_abs * (C_W[act] * w_abs + 6) * F
 
 
-def bounds_gate_up_fwd(R, H, act, dtype):
-    """R: gate_up_fwd(...) -> dict(m, cu, cg: bounds; held: where the cg bound holds; E_g, E_u)"""
-    u = unit(dtype)
+def bounds_gate_up_fwd(R, H, act, dtype, eps=EPS, E_g=None, E_u=None):
+    """R: gate_up_fwd(...) -> dict(m, cu, cg: bounds; held: where the cg bound holds; E_g, E_u).  eps, E_g, E_u: the stabiliser of s and the errors
+    of g, u where they are not this module's (tests/gemm_bound.py: the dense gate/up GEMM takes eps_g as an argument and scales its rows)"""
+    u, EPS = unit(dtype), eps      # noqa: N806  (the forms below are written in the docstring's EPS)
     g, uu, a, s = R["g"].abs(), R["u"].abs(), R["a"].abs(), R["s"].abs()
-    E_g, E_u = (H + 8) * F * R["A_g"], (H + 8) * F * R["A_u"]
+    E_g = (H + 8) * F * R["A_g"] if E_g is None else E_g
+    E_u = (H + 8) * F * R["A_u"] if E_u is None else E_u
     arith = act_arith(g + E_g, a + L_ACT[act] * E_g, act, dtype)
     da = L_ACT[act] * E_g + arith
     e_m = uu * da + (a + da) * E_u

@@ -2,7 +2,8 @@
 on odd head counts (a 256-column tile that holds the last k head and the first v head), the attention kernels at exact multiples of their
 128-row query block / below one MFMA row block / at window = block size, on strided operands as the engines pass them, the q_begin argument
 (top-layer sparsity) and the row intervals of the D-forming dQ kernel.  References: fp64 restatements of the same op; bars: those of
-tests/test_kernels_gpu.py, plus per-block bars so that a wrong block of small values cannot hide behind the global maximum."""
+tests/test_kernels_gpu.py, plus per-block bars so that a wrong block of small values cannot hide behind the global maximum (the GEMM forms are
+held element by element to a derived rounding bound in tests/test_gemm_bound_gpu.py; the edges here keep the odd head counts and the row chunks)."""
 import pytest
 import torch
 

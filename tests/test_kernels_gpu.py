@@ -3,6 +3,8 @@ a plain PyTorch fp64 restatement of the same op, on seeded inputs.  fp32 kernels
 max error <= 2e-5 (fp32 MFMA is an exact fma chain; the slack is accumulation order);
 bf16 kernels: <= 2e-2 (bf16 storage rounding of inputs/outputs).
 
+The dense GEMMs (plain, split-K, fused epilogues, small-M and streaming Linears) are held element by element to a derived rounding bound in
+tests/test_gemm_bound_gpu.py (tests/gemm_bound.py); the GEMM tests here keep the big shapes, the row chunks and the 2^30 offsets under nmax.
 The dispatch edges of the GEMM / attention / RoPE / MoE kernels are in tests/test_kernel_edges_gpu.py; the encoder-family row and
 element-wise kernels (LayerNorm, stand-alone activations, softmax on materialised rows, add_bcast, eps_scale2d, the flat element-wise
 kernels past their grid cap, readout / head_seed off the vector path) have their fp64 parity net in tests/test_rowops_gpu.py --
