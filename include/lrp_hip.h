@@ -173,6 +173,10 @@ int lrp_linear_smallm_dgrad(const void* g, const void* z, const void* W, const v
  *           A  = Gs (*) branch/(branch+eps_lin)     (eps-rule scale for the branch's last Linear)
  *           rel_out[row] (optional, fp32) = sum_h hsum*Gh  (latent relevance per token)
  *   branch == NULL means "no residual below" (embedding): Gs_out = Gh, A_out untouched.
+ *   NO ROW PITCH: h, branch, hsum_out, y and Gres, Gx, hsum, branch, Gs_out, A_out are CONTIGUOUS [M, H] (element (m, c) at m * H + c); rstd and
+ *   rel_out hold M entries.  The same holds for x, res, hsum_out, y of lrp_sandwich_norm_fwd and every activation operand of
+ *   lrp_sandwich_norm_bwd.  A column slice of a wider buffer must be copied first (lxt_amd.ops refuses it).  hsum_out may be h itself.
+ *   Where hsum + eps_add or branch + eps_lin is exactly 0 the quotient is not defined (the result is +-inf or NaN).
  * --------------------------------------------------------------------------------------- */
 /* per-head RMSNorm (HF Gemma3Attention q_norm / k_norm: rows of head_dim elements inside a fused projection output [rows, >= heads*d],
  * row pitches ldx / ldy in elements): y = (w + w_offset) (*) x * rstd, rstd[rows*heads] = rsqrt(mean_d(x^2) + eps); the backward treats
@@ -241,7 +245,9 @@ int lrp_layernorm_bwd_plain(const void* Gy, const void* x, const void* w, const 
  * backward: Gact = Gm*u/2 ; Gu = Gm*act/2
  *           Ag = Gact * act/(g + eps_g)            (identity rule (*) gate Linear eps scale;
  *                                                   eps_g = 1e-10 efficient / eps_lin explicit)
- *           Au = Gu * u/(u + eps_lin)              (eps_lin==0 -> Gu)
+ *           Au = Gu * u/(u + eps_lin)              (eps_lin==0 -> Gu; not defined where u + eps_lin is exactly 0)
+ *           Ag = 0 where g + eps_g is exactly 0.
+ * Every operand is a [M, I] view with unit column stride and a row pitch >= I.
  * --------------------------------------------------------------------------------------- */
 int lrp_gated_act_fwd(const void* g, const void* u, void* m, int M, int I, int64_t ldg,
                       int64_t ldu, int64_t ldm, int act, int dtype, void* stream);
@@ -255,6 +261,8 @@ int lrp_gated_act_bwd(const void* Gm, const void* g, const void* u, void* Ag, vo
  *                                    refuses: the caller runs them behind the Linear entry that fits its row count -- lrp_linear_stream_fwd,
  *                                    lrp_gemm_skinny, lrp_gemm_nt / _nn; the pair entries lrp_gemm_gated_fwd / _bwd[_ws] of ABI 3-7, which hard-wired
  *                                    the large-M GEMM, are gone in ABI 8: the host never called them)
+ *   gu and Agu are [M, 2 I] with row pitches ldgu, ldagu >= 2 I, m and Gm [M, I] with ldm, ldgm >= I (LRP_ESHAPE otherwise), I a multiple
+ *   of LRP_GATED_IL.
  * ref: lxt/efficient/patches.py:145-157, lxt/explicit/models/llama.py:84-86,273-281. */
 #define LRP_GATED_IL 32
 int lrp_gated_act_fwd_il(const void* gu, void* m, int M, int I, int64_t ldgu, int64_t ldm, int act, int dtype, void* stream);
@@ -356,10 +364,12 @@ int lrp_add_bcast(const void* x, const void* y, void* out, int M, int H, int per
 /* ---------------------------------------------------------------------------------------
  * K5  RoPE (rotate-half convention).  ref: HF apply_rotary_pos_emb;
  *     explicit eps: lxt/explicit/models/llama.py:226-260 (add2 eps=1e-8 on the rotated sum).
- * x [S, n_heads, d] with row stride ldx (elements); cos/sin fp32 [S, d].
+ * x [S, n_heads, d] with row stride ldx (elements) and unit column stride; cos/sin fp32 [>= seq, d], CONTIGUOUS (row pitch d: the ABI
+ * carries neither a count nor a pitch for them; row p is position p, both halves of a row are read).
  * forward : xr = x*cos + rotate_half(x)*sin
  * backward: Gp = Gr (*) xr/(xr+eps_rope) ; Gx = Gp*cos + rotate_half^T(Gp*sin) ;
- *           A = Gx (*) x/(x+eps_lin)     (xr / x may be NULL when the matching eps is 0)
+ *           A = Gx (*) x/(x+eps_lin)     (xr / x may be NULL when the matching eps is 0; not defined where xr + eps_rope or
+ *                                         x + eps_lin is exactly 0)
  * pos0: position of row 0; rows are positions pos0 + (row % S_per_seq).
  * --------------------------------------------------------------------------------------- */
 int lrp_rope_fwd(const void* x, void* xr, const float* cos_t, const float* sin_t, int rows,
@@ -455,7 +465,7 @@ int lrp_softmax_fwd(const void* x, void* p, int64_t rows, int n, float inv_temp,
                     void* stream);
 int lrp_softmax_rule_bwd(const void* x, const void* p, const void* Rp, void* Rx, int64_t rows,
                          int n, float inv_temp, int dtype, void* stream);
-/* add2 rule: s = R/(a+b+eps) ; Ra = s*a ; Rb = s*b (Rb may be NULL). ref: functional.py:430-459 */
+/* add2 rule: s = R/(a+b+eps) ; Ra = s*a ; Rb = s*b (Rb may be NULL; not defined where a+b+eps is exactly 0). ref: functional.py:430-459 */
 int lrp_add2_rule_bwd(const void* a, const void* b, const void* R, void* Ra, void* Rb,
                       int64_t n, float eps, int dtype, void* stream);
 

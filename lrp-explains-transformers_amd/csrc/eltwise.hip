@@ -574,12 +574,14 @@ extern "C" int lrp_gated_act_bwd(const void* Gm, const void* g, const void* u, v
 // [gate 32 b .. 32 b + 31 | up 32 b .. 32 b + 31]; Agu in the same layout
 extern "C" int lrp_gated_act_fwd_il(const void* gu, void* m, int M, int I, int64_t ldgu, int64_t ldm, int act, int dtype, void* stream) {
     const size_t es = dtype == LRP_F32 ? 4 : 2;
+    if (gu && m && M > 0 && I > 0 && (ldgu < 2 * (int64_t)I || ldm < I)) return LRP_ESHAPE;          // a row of gu holds gate AND up: 2 I columns
     return gated_fwd_launch(gu, gu ? (const char*)gu + 32 * es : nullptr, m, M, I, ldgu, ldgu, ldm, act, LRP_GATED_IL, dtype, (hipStream_t)stream);
 }
 
 extern "C" int lrp_gated_act_bwd_il(const void* Gm, const void* gu, void* Agu, int M, int I, int64_t ldgm, int64_t ldgu, int64_t ldagu,
                                     float eps_g, float eps_lin, int act, int dtype, void* stream) {
     const size_t es = dtype == LRP_F32 ? 4 : 2;
+    if (Gm && gu && Agu && M > 0 && I > 0 && (ldgm < I || ldgu < 2 * (int64_t)I || ldagu < 2 * (int64_t)I)) return LRP_ESHAPE;
     return gated_bwd_launch(Gm, gu, gu ? (const char*)gu + 32 * es : nullptr, Agu, Agu ? (char*)Agu + 32 * es : nullptr, M, I, ldgm, ldgu, ldgu,
                             ldagu, ldagu, eps_g, eps_lin, act, LRP_GATED_IL, dtype, (hipStream_t)stream);
 }

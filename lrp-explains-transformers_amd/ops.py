@@ -65,6 +65,29 @@ def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _rows_contiguous(name, M, H, **ts):
+    """operands of an entry whose C ABI has no row pitch (it indexes row * H): every one must be a contiguous [M, H] tensor -- a column slice or
+    a tensor of another shape would be read and written at the wrong addresses, and past its end"""
+    for k, t in ts.items():
+        if t is not None and (tuple(t.shape) != (M, H) or not t.is_contiguous()):
+            raise ValueError(f"{name}: {k} must be a contiguous [{M}, {H}] tensor (the C ABI has no row pitch), got {tuple(t.shape)} with "
+                             f"strides {t.stride()}")
+
+
+def _row_stats(name, M, **ts):
+    """per-row fp32 statistics: contiguous, at least M entries"""
+    for k, t in ts.items():
+        if t is not None and (t.numel() < M or not t.is_contiguous()):
+            raise ValueError(f"{name}: {k} must be contiguous with at least {M} entries, got {tuple(t.shape)} with strides {t.stride()}")
+
+
+def _pitched(name, rows, cols, **ts):
+    """2-D views [rows, >= cols] with a row pitch (stride(0)) and unit column stride, as the element-wise 2-D entries index them"""
+    for k, t in ts.items():
+        if t is not None and (t.dim() != 2 or t.shape[0] != rows or t.shape[1] < cols or t.stride(1) != 1 or (rows > 1 and t.stride(0) < cols)):
+            raise ValueError(f"{name}: {k} must be a [{rows}, >= {cols}] view with unit column stride, got {tuple(t.shape)} with strides {t.stride()}")
+
+
 # ------------------------------------------------------------------------------------------- GEMM
 def gemm_nt(a, b, bias=None, out=None, out_dtype=None):
     """out[..., M, N] = a[..., M, K] @ b[..., N, K]^T (+bias).  a/b: last dim contiguous, 2-D or
@@ -410,6 +433,7 @@ def gated_act_fwd(g, u, out=None, act="silu"):
     M, I = g.shape
     out = torch.empty(M, I, device=g.device, dtype=g.dtype) if out is None else out
     same(g, u, out)
+    _pitched("lrp_gated_act_fwd", M, I, g=g, u=u, out=out)
     check(lib.lrp_gated_act_fwd(p(g), p(u), p(out), M, I, g.stride(0), u.stride(0), out.stride(0), ACT[act], dt(g), stream()),
           "lrp_gated_act_fwd")
     return out
@@ -418,6 +442,7 @@ def gated_act_fwd(g, u, out=None, act="silu"):
 def gated_act_bwd(Gm, g, u, Ag, Au, eps_g, eps_lin, act="silu"):
     M, I = g.shape
     same(g, Gm, u, Ag, Au)
+    _pitched("lrp_gated_act_bwd", M, I, Gm=Gm, g=g, u=u, Ag=Ag, Au=Au)
     check(lib.lrp_gated_act_bwd(p(Gm), p(g), p(u), p(Ag), p(Au), M, I, Gm.stride(0), g.stride(0), u.stride(0), Ag.stride(0),
                                 Au.stride(0), eps_g, eps_lin, ACT[act], dt(g), stream()), "lrp_gated_act_bwd")
     return Ag, Au
@@ -443,6 +468,8 @@ def interleave_gate_up(wg, wu, out=None):
 def gated_act_fwd_il(gu, out, act="silu"):
     M, I = out.shape
     same(gu, out)
+    _pitched("lrp_gated_act_fwd_il", M, I, out=out)
+    _pitched("lrp_gated_act_fwd_il", M, 2 * I, gu=gu)
     check(lib.lrp_gated_act_fwd_il(p(gu), p(out), M, I, gu.stride(0), out.stride(0), ACT[act], dt(gu), stream()), "lrp_gated_act_fwd_il")
     return out
 
@@ -450,6 +477,8 @@ def gated_act_fwd_il(gu, out, act="silu"):
 def gated_act_bwd_il(Gm, gu, Agu, eps_g, eps_lin, act="silu"):
     M, I = Gm.shape
     same(gu, Gm, Agu)
+    _pitched("lrp_gated_act_bwd_il", M, I, Gm=Gm)
+    _pitched("lrp_gated_act_bwd_il", M, 2 * I, gu=gu, Agu=Agu)
     check(lib.lrp_gated_act_bwd_il(p(Gm), p(gu), p(Agu), M, I, Gm.stride(0), gu.stride(0), Agu.stride(0), eps_g, eps_lin, ACT[act], dt(gu),
                                    stream()), "lrp_gated_act_bwd_il")
     return Agu
@@ -459,6 +488,8 @@ def gated_cp_bwd_il(Gm, gu, Agu, act="silu"):
     """CP-LRP through the gated MLP (the gate is detached): up slots of Agu = act(g) * Gm, gate slots = 0, interleaved layout of gated_act_bwd_il"""
     M, I = Gm.shape
     same(gu, Gm, Agu)
+    _pitched("lrp_gated_cp_bwd_il", M, I, Gm=Gm)
+    _pitched("lrp_gated_cp_bwd_il", M, 2 * I, gu=gu, Agu=Agu)
     check(lib.lrp_gated_cp_bwd_il(p(Gm), p(gu), p(Agu), M, I, Gm.stride(0), gu.stride(0), Agu.stride(0), ACT[act], dt(gu), stream()),
           "lrp_gated_cp_bwd_il")
     return Agu
@@ -522,6 +553,8 @@ def rope_fwd(x, out, cos, sin, seq, n_heads, d):
     rows = x.shape[0]
     same(x, out)
     f32(cos, sin)
+    _rope_tables(cos, sin, seq, d, "lrp_rope_fwd")
+    _pitched("lrp_rope_fwd", rows, n_heads * d, x=x, out=out)
     check(lib.lrp_rope_fwd(p(x), p(out), p(cos), p(sin), rows, seq, n_heads, d, x.stride(0), out.stride(0), dt(x), stream()),
           "lrp_rope_fwd")
     return out
@@ -531,6 +564,8 @@ def rope_bwd(Gr, xr, x, A, cos, sin, seq, n_heads, d, eps_rope, eps_lin):
     rows = Gr.shape[0]
     same(Gr, xr, x, A)
     f32(cos, sin)
+    _rope_tables(cos, sin, seq, d, "lrp_rope_bwd")
+    _pitched("lrp_rope_bwd", rows, n_heads * d, Gr=Gr, xr=xr, x=x, A=A)
     check(lib.lrp_rope_bwd(p(Gr), p(xr), p(x), p(A), p(cos), p(sin), rows, seq, n_heads, d, Gr.stride(0),
                            xr.stride(0) if xr is not None else 0, x.stride(0) if x is not None else 0, A.stride(0),
                            eps_rope, eps_lin, dt(Gr), stream()), "lrp_rope_bwd")
@@ -688,6 +723,8 @@ def add_rmsnorm_fwd(h, branch, w, eps, w_offset=0.0, hsum_out=None, y=None, rstd
     rstd = torch.empty(M, device=h.device, dtype=torch.float32) if rstd is None else rstd
     same(h, branch, hsum_out, y)
     f32(rstd)
+    _rows_contiguous("lrp_add_rmsnorm_fwd", M, H, h=h, branch=branch, hsum_out=hsum_out, y=y)
+    _row_stats("lrp_add_rmsnorm_fwd", M, rstd=rstd)
     w = aux(w, h, H)
     check(lib.lrp_add_rmsnorm_fwd(p(h), p(branch), p(w), p(hsum_out), p(y), p(rstd), M, H, eps, w_offset, dt(h), stream()),
           "lrp_add_rmsnorm_fwd")
@@ -698,6 +735,8 @@ def rmsnorm_bwd_add2(Gres, Gx, w, rstd, hsum, branch, Gs_out, A_out, rel_out=Non
     M, H = (Gx if Gx is not None else Gres).shape
     same(Gs_out, Gres, Gx, hsum, branch, A_out)
     f32(rstd, rel_out)
+    _rows_contiguous("lrp_rmsnorm_bwd_add2", M, H, Gres=Gres, Gx=Gx, hsum=hsum, branch=branch, Gs_out=Gs_out, A_out=A_out)
+    _row_stats("lrp_rmsnorm_bwd_add2", M, rstd=rstd, rel_out=rel_out)
     w = aux(w, Gs_out, H)
     check(lib.lrp_rmsnorm_bwd_add2(p(Gres), p(Gx), p(w), p(rstd), p(hsum), p(branch), p(Gs_out), p(A_out), p(rel_out), M, H,
                                    w_offset, eps_add, eps_lin, dt(Gs_out), stream()), "lrp_rmsnorm_bwd_add2")
@@ -752,6 +791,8 @@ def sandwich_norm_fwd(x, res, w_post, w_pre, eps, w_offset, hsum_out, y, rstd_po
     M, H = x.shape
     same(x, res, hsum_out, y)
     f32(rstd_post, rstd_pre)
+    _rows_contiguous("lrp_sandwich_norm_fwd", M, H, x=x, res=res, hsum_out=hsum_out, y=y)
+    _row_stats("lrp_sandwich_norm_fwd", M, rstd_post=rstd_post, rstd_pre=rstd_pre)
     w_post = aux(w_post, x, H)
     w_pre = aux(w_pre, x, H) if w_pre is not None else None
     check(lib.lrp_sandwich_norm_fwd(p(x), p(res), p(w_post), p(w_pre), p(hsum_out), p(y), p(rstd_post), p(rstd_pre), M, H, eps, w_offset, dt(x),
@@ -1479,6 +1520,7 @@ ROPE_BWD_FUSION = True   # module attribute (A/B): False = the stand-alone lrp_r
 def gqa_reduce_rope(x, out, rows, seq, Hkv, rep, d, cos, sin):
     """out[r, hk, :] = RoPE^T(sum_j x[r, hk rep + j, :]) -- the GQA group sum of dK and RoPE's backward in one pass"""
     f32(cos, sin)
+    _rope_tables(cos, sin, seq, d, "lrp_gqa_reduce_rope")
     check(lib.lrp_gqa_reduce_rope(p(x), p(out), rows, seq, Hkv, rep, d, x.stride(0), out.stride(0), p(cos), p(sin), dt(x), stream()),
           "lrp_gqa_reduce_rope")
     return out
