@@ -557,5 +557,6 @@ int lrp_moe_gate_up_dgrad(const void* Agu, const void* Wgu, const int* plan, voi
 #include "lrp_hip_decode_site.h"
 #include "lrp_hip_mxfp4_stream.h"
 #include "lrp_hip_sample.h"
+#include "lrp_hip_penalty.h"
 #include "lrp_hip_attn_cp.h"
 #endif /* LRP_HIP_H */

@@ -573,6 +573,54 @@ def sample_request(do_sample, temperature, top_k, top_p, min_p, seed, B, force_t
     return SampleSpec(temperature, top_k, top_p, min_p, torch.tensor(seeds, dtype=torch.int64), torch.tensor(streams, dtype=torch.int32))
 
 
+PenaltySpec = collections.namedtuple("PenaltySpec", "repetition_penalty presence_penalty frequency_penalty bias")
+PenaltyState = collections.namedtuple("PenaltyState", "spec hist out bias")
+
+
+def penalty_request(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, vocab, force_tokens):
+    """generate(repetition_penalty=..., presence_penalty=..., frequency_penalty=..., logit_bias=...) -> None when all four are neutral
+    (1.0, 0.0, 0.0, None), else a PenaltySpec: the three scalars as ops.logit_penalty takes them and bias, fp32 [vocab] on the host or None.
+    logit_bias: a {token: float} dict or an fp32 [vocab] tensor; -inf bans a token.  No device, no weights; ValueError before a kernel runs:
+    repetition_penalty <= 0 or not finite, a presence / frequency penalty that is not finite, a bias key outside [0, vocab), a bias value
+    that is NaN or +inf, a bias that bans every column, a tensor that is not fp32 [vocab], any non-neutral setting with force_tokens."""
+    def real(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+        return float(v)
+
+    rp, pp, fp = (real(n, v) for n, v in (("repetition_penalty", repetition_penalty), ("presence_penalty", presence_penalty),
+                                          ("frequency_penalty", frequency_penalty)))
+    if rp <= 0.0:
+        raise ValueError(f"repetition_penalty must be > 0 (1: off), got {rp}")
+    bias = None
+    if torch.is_tensor(logit_bias):
+        if logit_bias.dtype != torch.float32 or tuple(logit_bias.shape) != (vocab,):
+            raise ValueError(f"logit_bias as a tensor must be float32 [{vocab}], got {logit_bias.dtype} {tuple(logit_bias.shape)}")
+        bias = logit_bias.detach().cpu().contiguous()
+    elif isinstance(logit_bias, dict):
+        if logit_bias:
+            bias = torch.zeros(vocab, dtype=torch.float32)
+            for k, v in logit_bias.items():
+                if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k < vocab:
+                    raise ValueError(f"logit_bias keys must be vocabulary indices in [0, {vocab}), got {k!r}")
+                if isinstance(v, bool) or not isinstance(v, (int, float)):
+                    raise ValueError(f"logit_bias[{k}] must be a number, got {v!r}")
+                bias[k] = float(v)
+    elif logit_bias is not None:
+        raise ValueError(f"logit_bias must be a {{token: float}} dict or a float32 [{vocab}] tensor, got {type(logit_bias).__name__}")
+    if bias is not None:
+        if bool(torch.isnan(bias).any()) or bool((bias == float("inf")).any()):
+            raise ValueError("logit_bias values must not be NaN or +inf (-inf bans a token)")
+        if bool((bias == -float("inf")).all()):
+            raise ValueError(f"logit_bias bans all {vocab} columns: nothing is left to choose")
+    if (rp, pp, fp) == (1.0, 0.0, 0.0) and bias is None:
+        return None
+    if force_tokens is not None:
+        raise ValueError("repetition_penalty, presence_penalty, frequency_penalty and logit_bias together with force_tokens: scoring a given "
+                         "answer has nothing to penalise")
+    return PenaltySpec(rp, pp, fp, bias)
+
+
 OBJECTIVES = ("logit", "logprob")
 
 SpanRequest = collections.namedtuple("SpanRequest", "T rows idx auto w w_each objective per_position")
@@ -930,27 +978,37 @@ class GraphCache:
         return out
 
 
-def greedy_decode(logits, step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits, sampler=None):
+def greedy_decode(logits, step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits, penalty=None, sampler=None):
     """the token loop of generate(), shared by the drivers: logits fp32 [B, V] of the prefill's last rows; step(tok int64 [B], pos int32 [1])
     -> (logits, arg-max idx) of one decode step (eager or a GraphCache replay); cols int32 [max_new_tokens]: cols[t - 1: t] is the column of
     step t's input token; ids int64 [B, S] on the device, lens int64 [B] on the host; eos / pad as generate_request returns them; forced
     int32 [B, max_new_tokens] or None.  -> generate()'s dict.  B flags are read back per token with eos, nothing without.
     sampler: a SampleSpec (sample_request) -- token t is ops.sample_rows of step t's logits at Philox counter t in place of the arg-max, one
     launch per token next to span_seed's (outside the captured step); logit / logprob stay the model's own, untempered values of the drawn
-    token, and the dict gains sample_logprob [B, T'] = log(q_tok / Z) under the temperature and the filters"""
+    token, and the dict gains sample_logprob [B, T'] = log(q_tok / Z) under the temperature and the filters
+    penalty: a PenaltyState (generate_cached: the PenaltySpec, the history table of the prompt, the processed-logits buffer, the bias on the
+    device) -- ops.logit_penalty turns step t's raw logits into processed ones, counting the token fed into step t first, one launch per token
+    outside the captured step; the token is the arg-max or the draw of the PROCESSED logits, while logit / logprob / return_logits stay the
+    model's raw values and sample_logprob is under the processed distribution"""
     dev, B = ids.device, ids.shape[0]
     eos_t = torch.tensor(eos, device=dev, dtype=torch.int32) if eos else None
     fin = torch.zeros(B, device=dev, dtype=torch.bool)
     n_new = torch.zeros(B, device=dev, dtype=torch.long)
     toks, logit, logprob, rows = [], [], [], []
-    idx = ops.argmax_rows(logits)[0]
+    idx = ops.argmax_rows(logits)[0] if penalty is None else None
     if sampler is not None:
         seeds, streams, slp = sampler.seeds.to(dev), sampler.streams.to(dev), []
+    last = None
     for t in range(max_new_tokens):
         if t:
             logits, idx = step(toks[-1], cols[t - 1: t])
+        scores = logits
+        if penalty is not None:
+            scores = ops.logit_penalty(logits, penalty.hist, last, *penalty.spec[:3], bias=penalty.bias, out=penalty.out)
+            if sampler is None:
+                idx = ops.argmax_rows(scores)[0]
         if sampler is not None:
-            idx, lq, _, _ = ops.sample_rows(logits, sampler.temperature, sampler.top_k, sampler.top_p, sampler.min_p, seeds, streams, step=t)
+            idx, lq, _, _ = ops.sample_rows(scores, sampler.temperature, sampler.top_k, sampler.top_p, sampler.min_p, seeds, streams, step=t)
             slp.append(lq)
         if forced is not None:
             idx = forced[:, t]
@@ -958,6 +1016,8 @@ def greedy_decode(logits, step, cols, ids, lens, max_new_tokens, eos, pad, force
             idx = torch.where(fin, torch.full_like(idx, pad), idx)          # (a copy: idx may be a graph's static output)
         lg, lp, _, _ = ops.span_seed(logits, idx.contiguous())
         toks.append(idx.long())
+        if penalty is not None:
+            last = idx.contiguous()
         logit.append(lg)
         logprob.append(lp)
         if return_logits:
@@ -1133,7 +1193,8 @@ def explain_pipeline(drv, forward, backward, emb, B, S, idx, attn_scale, rope_sc
 
 
 def generate_cached(drv, embed, prefill_kv, graph_key, input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph, return_logits,
-                    inputs_embeds, force_tokens, do_sample, temperature, top_k, top_p, min_p, seed):
+                    inputs_embeds, force_tokens, do_sample, temperature, top_k, top_p, min_p, seed, repetition_penalty=1.0, presence_penalty=0.0,
+                    frequency_penalty=0.0, logit_bias=None):
     """the body of the drivers' generate() (its arguments and its dict): the requests, the prefill -- the forward explain() runs --, the KV
     caches [L, B, cap, nk d] of the arena with the prefill's rows copied in, cap = S + max_new_tokens, and the token loop on
     drv._decode_step, eager or one GraphCache graph per graph_key(B, cap).  The driver supplies that key, embed(ids [n]) -> its embedding
@@ -1143,6 +1204,7 @@ def generate_cached(drv, embed, prefill_kv, graph_key, input_ids, max_new_tokens
     ids, lens, eos, pad = generate_request(input_ids, inputs_embeds, max_new_tokens, lengths, eos_token_id, pad_token_id, c["vocab"], drv.max_seq)
     B, S = ids.shape
     sampler = sample_request(do_sample, temperature, top_k, top_p, min_p, seed, B, force_tokens)
+    spec = penalty_request(repetition_penalty, presence_penalty, frequency_penalty, logit_bias, c["vocab"], force_tokens)
     dev, ar, L, nkd, nq, d = drv.device, drv._arena, len(drv.layers), c["n_kv"] * c["head_dim"], c["n_heads"], c["head_dim"]
     cap = S + max_new_tokens
     forced = force_request(force_tokens, B, max_new_tokens, c["vocab"], dev)
@@ -1161,15 +1223,22 @@ def generate_cached(drv, embed, prefill_kv, graph_key, input_ids, max_new_tokens
         step = lambda tok, pos: drv._graphs(graph_key(B, cap), lambda t_, p_: drv._decode_step(t_, p_, lo, kc, vc, ws), tok, pos)      # noqa: E731
     else:
         step = lambda tok, pos: drv._decode_step(tok, pos, lo, kc, vc, ws)      # noqa: E731
-    return greedy_decode(fw["logits"], step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits, sampler=sampler)
+    kw = {}
+    if spec is not None:          # the history of the prompt (its pads are none), one table and one processed-logits buffer per call
+        V = c["vocab"]
+        hist = ops.token_hist_init(ids, lo, V, hist=ar.get("pen_hist", (B, V), torch.int32))
+        kw["penalty"] = PenaltyState(spec, hist, ar.get("pen_logits", (B, V), torch.float32), None if spec.bias is None else spec.bias.to(dev))
+    return greedy_decode(fw["logits"], step, cols, ids, lens, max_new_tokens, eos, pad, forced, return_logits, sampler=sampler, **kw)
 
 
 def explain_answer(drv, input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph, objective, position_weights, do_sample,
-                   temperature, top_k, top_p, min_p, seed, readout_kw):
+                   temperature, top_k, top_p, min_p, seed, readout_kw, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0,
+                   logit_bias=None):
     """the body of the drivers' explain_generated(): drv.generate(), then drv.explain() on the rows that predict the new tokens
     (generated_span) -> explain's dict plus sequences, new_tokens, n_new"""
     out = drv.generate(input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph=graph, do_sample=do_sample,
-                       temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, seed=seed)
+                       temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p, seed=seed, repetition_penalty=repetition_penalty,
+                       presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, logit_bias=logit_bias)
     positions, w = generated_span(out, position_weights)
     res = drv.explain(out["sequences"], lengths=out["lengths"], positions=positions, position_weights=w, objective=objective, **readout_kw)
     res.update(sequences=out["sequences"], new_tokens=out["new_tokens"], n_new=out["n_new"])
@@ -1886,7 +1955,8 @@ class LlamaLRP:
 
     @torch.no_grad()
     def generate(self, input_ids=None, max_new_tokens=1, lengths=None, eos_token_id=None, pad_token_id=None, graph=False, return_logits=False,
-                 inputs_embeds=None, force_tokens=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, seed=None):
+                 inputs_embeds=None, force_tokens=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, seed=None, repetition_penalty=1.0,
+                 presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None):
         """Continuation of input_ids [B, S] on the resident weights, forward only, with a KV cache, greedy by default:
         -> dict(sequences int64 [B, S + T'], new_tokens int64 [B, T'], n_new int64 [B], logit / logprob fp32 [B, T'] = the step's logit and
         log-probability of new_tokens[b, t], lengths int64 [B] = the input lengths + T'[, logits fp32 [B, T', V] with return_logits]).
@@ -1909,24 +1979,35 @@ class LlamaLRP:
         is required: an int (prompt b draws from Philox stream b of that seed) or a list of B ints (prompt b draws from its own seed: its
         continuation does not depend on the batch).  Same seed, same tokens, eager or graph.  logit / logprob stay the model's untempered values
         of the drawn tokens (what explain_generated explains); the dict gains sample_logprob [B, T'], the log-probability under the
-        temperature and the filters.  No beam search, repetition penalty or per-prompt settings.
+        temperature and the filters.
+        repetition_penalty / presence_penalty / frequency_penalty / logit_bias: lrp_logit_penalty turns step t's raw
+        logits into processed ones, and token t is the arg-max (or, with do_sample, the draw) of those.  repetition_penalty > 0 (1: off) is HF's
+        RepetitionPenaltyLogitsProcessor over the prompt (its left pads are no history) and the generated tokens: x < 0 ? x rp : x / rp;
+        frequency_penalty and presence_penalty are the OpenAI / vLLM ones over the generated tokens only: x - fp count - pp; logit_bias is a
+        {token: float} dict or an fp32 [vocab] tensor added last, -inf bans a token.  logit / logprob / logits stay the model's raw values of
+        the chosen tokens (what explain_generated explains); sample_logprob is under the processed distribution.  At the neutral values
+        nothing is launched or allocated.  No beam search, n-gram blocking, min_new_tokens or per-prompt settings.
         ValueError before any kernel runs: inputs_embeds, max_new_tokens < 1, S + max_new_tokens > max_seq, bad lengths, an eos_token_id,
         pad_token_id or forced token outside [0, vocab), and what sample_request refuses (a sampling argument without do_sample, do_sample
-        without seed or with force_tokens, a setting outside its range)."""
+        without seed or with force_tokens, a setting outside its range) and what penalty_request refuses (a penalty outside its range, a bad
+        logit_bias, any of them with force_tokens)."""
         return generate_cached(self, self._embed, self._prefill_kv, lambda B, cap: ("decode", B, cap, self.mode), input_ids, max_new_tokens,
                                lengths, eos_token_id, pad_token_id, graph, return_logits, inputs_embeds, force_tokens, do_sample, temperature,
-                               top_k, top_p, min_p, seed)
+                               top_k, top_p, min_p, seed, repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
 
     @torch.no_grad()
     def explain_generated(self, input_ids=None, max_new_tokens=1, lengths=None, eos_token_id=None, pad_token_id=None, graph=False,
                           objective="logprob", position_weights=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0,
-                          seed=None, **readout_kw):
+                          seed=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None,
+                          **readout_kw):
         """Prompt in, the model's own answer and its attribution out, on one resident copy of the weights: generate() (greedy, or sampled with
-        do_sample=True and generate()'s sampling keywords), then
+        do_sample=True and generate()'s sampling keywords; repetition_penalty, presence_penalty, frequency_penalty and logit_bias as in
+        generate()), then
         explain(sequences, lengths=out["lengths"], positions=[S - 1 .. S + T' - 2], position_weights=w, objective=objective, **readout_kw) --
         row S - 1 + t predicts new token t, so the default targets of positions ARE the generated tokens.  w[b, t] = 1 for t < n_new[b], else 0
         (the slots after an EOS are the zero-weight spare slots positions defines); position_weights="mean": 1 / n_new[b] instead; or an
         explicit fp32 [B, T'].  The last column is no explained row: R_tok is exactly 0 there, as at pads.  -> explain's dict plus sequences,
         new_tokens, n_new.  graph applies to the generation; per_position=True and every read-out keyword pass through to explain()."""
         return explain_answer(self, input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph, objective, position_weights,
-                              do_sample, temperature, top_k, top_p, min_p, seed, readout_kw)
+                              do_sample, temperature, top_k, top_p, min_p, seed, readout_kw, repetition_penalty, presence_penalty,
+                              frequency_penalty, logit_bias)

@@ -508,26 +508,31 @@ class Gemma3LRP:
 
     @torch.no_grad()
     def generate(self, input_ids=None, max_new_tokens=1, lengths=None, eos_token_id=None, pad_token_id=None, graph=False, return_logits=False,
-                 inputs_embeds=None, force_tokens=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, seed=None):
+                 inputs_embeds=None, force_tokens=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, seed=None, repetition_penalty=1.0,
+                 presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None):
         """Continuation of input_ids [B, S] on the resident weights, forward only, with a KV cache, greedy by default: LlamaLRP.generate's signature,
         returned dict (sequences, new_tokens, n_new, logit, logprob, lengths[, logits]) and EOS / pad / force_tokens / lengths behaviour
         (DESIGN.md sections 21 and 23).  The prefill is the forward explain() runs; every layer's normed, rotated K and its V are copied into
         caches [L, B, cap, nk d] of the arena, cap = S + max_new_tokens <= max_seq (sliding layers keep all cap rows: no ring buffer); the
         first new token is the lrp_argmax_rows of the prefill's logits, each further one costs one _decode_step.  graph=True: the step is
         captured once per (B, cap) and replayed, bitwise the eager result.  do_sample=True with temperature / top_k / top_p / min_p / seed: the
-        seeded sampling of LlamaLRP.generate (the dict gains sample_logprob).  ValueError before any kernel runs:
+        seeded sampling of LlamaLRP.generate (the dict gains sample_logprob).  repetition_penalty / presence_penalty / frequency_penalty /
+        logit_bias: the penalties of LlamaLRP.generate, applied by lrp_logit_penalty before the arg-max or the draw.
+        ValueError before any kernel runs:
         inputs_embeds, max_new_tokens < 1, S + max_new_tokens > max_seq, bad lengths, an eos_token_id, pad_token_id or forced token outside
-        [0, vocab), and what sample_request refuses."""
+        [0, vocab), and what sample_request and penalty_request refuse."""
         return generate_cached(self, self._embed, self._prefill_kv, lambda B, cap: ("decode", B, cap), input_ids, max_new_tokens, lengths,
                                eos_token_id, pad_token_id, graph, return_logits, inputs_embeds, force_tokens, do_sample, temperature, top_k, top_p,
-                               min_p, seed)
+                               min_p, seed, repetition_penalty, presence_penalty, frequency_penalty, logit_bias)
 
     @torch.no_grad()
     def explain_generated(self, input_ids=None, max_new_tokens=1, lengths=None, eos_token_id=None, pad_token_id=None, graph=False,
                           objective="logprob", position_weights=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0,
-                          seed=None, **readout_kw):
-        """generate() (greedy, or sampled with do_sample=True and generate()'s sampling keywords), then explain(sequences, lengths=out["lengths"], positions=[S - 1 .. S + T' - 2], position_weights=w,
+                          seed=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None,
+                          **readout_kw):
+        """generate() (greedy, or sampled with do_sample=True and generate()'s sampling keywords; generate()'s penalties apply), then explain(sequences, lengths=out["lengths"], positions=[S - 1 .. S + T' - 2], position_weights=w,
         objective=objective, **readout_kw) with the weight rules of LlamaLRP.explain_generated (1 for t < n_new[b] else 0; "mean";
         or explicit) -> explain's dict plus sequences, new_tokens, n_new.  The last column is no explained row: R_tok is exactly 0 there"""
         return explain_answer(self, input_ids, max_new_tokens, lengths, eos_token_id, pad_token_id, graph, objective, position_weights,
-                              do_sample, temperature, top_k, top_p, min_p, seed, readout_kw)
+                              do_sample, temperature, top_k, top_p, min_p, seed, readout_kw, repetition_penalty, presence_penalty,
+                              frequency_penalty, logit_bias)

@@ -1198,7 +1198,80 @@ def sample_rows(logits, temperature=1.0, top_k=0, top_p=1.0, min_p=0.0, seeds=No
     return idx, slp, n_kept, u_out
 
 
-SMALLM_MAX = 16          # rows the W-streaming small-M kernels serve (above: the skinny split-K path, then the MFMA GEMM)
+def _pitch(t, rows, cols):
+    return t.stride(0) if rows > 1 else max(t.stride(0), cols)
+
+
+def token_hist_init(ids, lo, V, hist=None):
+    """the history table of one generate() call (include/lrp_hip_penalty.h): ids int64 [B, S] (unit column stride, any row pitch), lo int32 [B]
+    or None -> hist int32 [B, V], zeroed, with bit 31 set at ids[b, s] for s >= lo[b] (the columns before lo[b] are the pads of a left-padded
+    prompt; an id outside [0, V) is skipped).  hist: a [B, >= V] int32 view with unit column stride to fill (columns >= V are left alone)."""
+    if not torch.is_tensor(ids) or ids.dim() != 2 or ids.stride(1) != 1 and ids.shape[1] > 1:
+        raise ValueError("token_hist_init: ids must be an int64 [B, S] tensor with contiguous rows")
+    B, S = ids.shape
+    if ids.dtype != torch.int64:
+        raise TypeError(f"token_hist_init: ids must be int64, got {ids.dtype}")
+    pi = p(ids)                         # (device tensors only: raises before anything is allocated)
+    if isinstance(V, bool) or not isinstance(V, int) or V < 1:
+        raise ValueError(f"token_hist_init: V must be an integer >= 1, got {V!r}")
+    if lo is not None:
+        if not torch.is_tensor(lo) or lo.dtype != torch.int32:
+            raise TypeError("token_hist_init: lo must be an int32 tensor")
+        if lo.numel() != B or not lo.is_contiguous() or lo.device != ids.device:
+            raise ValueError(f"token_hist_init: lo must be a contiguous [{B}] tensor on {ids.device}")
+    if hist is not None:
+        if not torch.is_tensor(hist) or hist.dtype != torch.int32:
+            raise TypeError("token_hist_init: hist must be an int32 tensor")
+        _pitched("token_hist_init", B, V, hist=hist)
+        if hist.device != ids.device:
+            raise ValueError(f"token_hist_init: hist must live on {ids.device}")
+    else:
+        hist = torch.empty(B, V, device=ids.device, dtype=torch.int32)
+    if B == 0:                          # (empty tensors have no address to hand over)
+        return hist
+    check(lib.lrp_token_hist_init(pi, _pitch(ids, B, S), p(lo), B, S, V, p(hist), _pitch(hist, B, V), stream()), "lrp_token_hist_init")
+    return hist
+
+
+def logit_penalty(logits, hist, last=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, bias=None, out=None):
+    """the processed logits of one step, one launch (include/lrp_hip_penalty.h): logits fp32 [B, V] (unit column stride, any row pitch), hist
+    int32 [B, >= V] as token_hist_init leaves it -> out fp32 [B, V] (a buffer of its own; logits are not written).  last int32 [B] or None:
+    the token fed into this step -- its generated count in hist goes up by one first (a value outside [0, V) is ignored).  Then, per column,
+    in individually rounded fp32 operations: repetition_penalty (> 0; 1: off) on the columns in the prompt or generated, x < 0 ? x rp : x / rp;
+    x - frequency_penalty c, then x - presence_penalty, on the generated ones (count c > 0); x + bias[j] (fp32 [V]; -inf bans a column)."""
+    if not torch.is_tensor(logits) or logits.dim() != 2 or logits.stride(1) != 1 or logits.shape[1] < 1:
+        raise ValueError("logit_penalty: logits must be [B, V >= 1] with contiguous rows")
+    B, V = logits.shape
+    f32(logits, bias, out)
+    if not torch.is_tensor(hist) or hist.dtype != torch.int32:
+        raise TypeError("logit_penalty: hist must be an int32 tensor")
+    pl = p(logits)                      # (device tensors only: raises before anything is allocated)
+    _pitched("logit_penalty", B, V, hist=hist, out=out)
+    if last is not None:
+        if not torch.is_tensor(last) or last.dtype != torch.int32:
+            raise TypeError("logit_penalty: last must be an int32 tensor")
+        if last.numel() != B or not last.is_contiguous():
+            raise ValueError(f"logit_penalty: last must be a contiguous [{B}] tensor")
+    if bias is not None and (not torch.is_tensor(bias) or tuple(bias.shape) != (V,) or not bias.is_contiguous()):
+        raise ValueError(f"logit_penalty: bias must be a contiguous [{V}] tensor")
+    for t in (hist, last, bias, out):
+        if t is not None and t.device != logits.device:
+            raise ValueError(f"logit_penalty: every operand must live on {logits.device}")
+    rp, pp, fp = float(repetition_penalty), float(presence_penalty), float(frequency_penalty)
+    if not (0.0 < rp < float("inf")) or not abs(pp) < float("inf") or not abs(fp) < float("inf"):
+        raise ValueError(f"logit_penalty: repetition_penalty > 0 and finite, presence / frequency penalty finite; got {rp}, {pp}, {fp}")
+    if out is None:
+        out = torch.empty(B, V, device=logits.device, dtype=torch.float32)
+    elif out.data_ptr() == logits.data_ptr():
+        raise ValueError("logit_penalty: out must be a buffer of its own (the raw logits stay what span_seed reads)")
+    if B == 0:                          # (empty tensors have no address to hand over)
+        return out
+    check(lib.lrp_logit_penalty(pl, _pitch(logits, B, V), p(out), _pitch(out, B, V), B, V, p(hist), _pitch(hist, B, V), p(last), rp, pp, fp, p(bias),
+                                stream()), "lrp_logit_penalty")
+    return out
+
+
+SMALLM_MAX = 16         # rows the W-streaming small-M kernels serve (above: the skinny split-K path, then the MFMA GEMM)
 
 
 def _smallm_ws(M, N, K, ref):
